@@ -20,11 +20,20 @@ Prints ONE JSON line on rank 0. `value` = algorithmic FLOPs of all ranks' steps
 sides). Before the W warm-up steps the GPU is additionally warmed BY TIME (>= WARM_MS of
 back-to-back launches): a handful of 0.1 ms launches ends before the clocks have settled, and the
 timed region would measure the ramp. `roofline.achieved` is measured with HIP events on the launch
-stream over the same K launches (events bracket blocks of 10 launches). `cpu_baseline` times the
+stream over the same K launches (events bracket blocks of 10 launches).
+
+A plain run does only that: set up, warm up, time the K steps, print the line. `--full` adds the
+measurements beyond the headline, each with work of its own: `value_public_api` (the same K launches
+through flash_attention_forward), `c4_slice`, `c5_fp8`, `sweep` and `cpu_baseline` (--no-c4,
+--no-sweep and --no-cpu-baseline leave parts of it out). `cpu_baseline` times the
 reference's own CPU loop (oracle/_ref, kind "reference") or our C port of it (kind "port") on
 the host cores, rank 0 at N=1 only, on a bounded sample. `c4_slice` is BASELINE configs[3]'s
 per-GPU shard (32 (batch,head) slices of seqlen 16384, head_dim 128): with --gpus 8 the ranks
 together run config 4 itself.
+
+`--dump-outputs DIR` writes what the last timed step computed on rank 0 to DIR as float32 .npy files
+(see dump_outputs). The inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -47,6 +56,7 @@ PEAK_TFLOPS_BF16 = 2500.0  # MI355X_MICROARCH.md: ~2.5 PF dense bf16/f16
 PEAK_HBM_GBS = 8000.0      # 8 TB/s spec
 WARM_MS = 300.0            # time-based warm-up in front of the counted warm-up steps
 C4_SLICES, C4_N, C4_D = 32, 16384, 128  # BASELINE configs[3] per GPU: 8*32 heads over 8 GPUs
+DUMP_ROWS, DUMP_SEED = 1 << 17, 1234   # --dump-outputs: half of the 64*4096 query rows of O (32 MiB in fp32)
 
 
 def cpu_baseline(target_s: float = 15.0) -> dict:
@@ -170,17 +180,46 @@ def warm_by_time(torch, dev, step, ms=WARM_MS):
     return n
 
 
+def workload_qkv(torch, dev, slices, rank):
+    """Q, K, V of a rank's shard: [1, slices, N, D] bf16, uniform(-1,1) from a generator seeded by the rank (same in every run)."""
+    g = torch.Generator(device=dev).manual_seed(1000 + rank)
+    mk = lambda: (torch.rand(1, slices, N, D, generator=g, device=dev, dtype=torch.float32) * 2 - 1).to(torch.bfloat16)  # noqa: E731
+    return mk(), mk(), mk()
+
+
+def dump_outputs(path, torch, o, lse, rows=DUMP_ROWS, seed=DUMP_SEED):
+    """What a caller of the timed path receives, as float32 .npy files under `path` (33 MiB in all):
+    lse.npy           LSE [1, B*H, N], whole
+    o_rows_sample.npy O [1, B*H, N, D] (bf16, exact in fp32) viewed as [B*H*N, D] rows: the rows at the sorted indices
+                      numpy.random.default_rng(seed).choice(B*H*N, rows, replace=False) -- the same rows in every run."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    flat = o.reshape(-1, o.shape[-1])
+    idx = np.sort(np.random.default_rng(seed).choice(flat.shape[0], size=min(rows, flat.shape[0]), replace=False))
+    sample = flat[torch.from_numpy(idx).to(o.device)].float().cpu().numpy()
+    np.save(os.path.join(path, "o_rows_sample.npy"), sample)
+    np.save(os.path.join(path, "lse.npy"), lse.float().cpu().numpy())
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true")
-    ap.add_argument("--no-c4", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure beyond the headline: public-API launches, config 4 shard, config 5 fp8, seqlen sweep, "
+                         "CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: no seqlen sweep")
+    ap.add_argument("--no-c4", action="store_true", help="with --full: no config 4 shard and config 5 fp8 blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0) to DIR/<name>.npy, float32")
     ap.add_argument("--cpu-gloo-rehearsal", action="store_true",
                     help="rank plumbing only, on CPU over gloo (tests): no kernel is launched, no throughput is claimed")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         return spawn_ranks(args)
@@ -206,9 +245,7 @@ def main() -> int:
     # ---- this rank's shard of the global (batch*head) slices -------------------------------
     lo, hi = ranks.my_slices(info, B_PER_GPU * H)
     my = hi - lo  # = B_PER_GPU * H
-    g = torch.Generator(device=dev).manual_seed(1000 + rank)
-    mk = lambda: (torch.rand(1, my, N, D, generator=g, device=dev, dtype=torch.float32) * 2 - 1).to(torch.bfloat16)  # noqa: E731
-    q, k, v = mk(), mk(), mk()  # random, never zeros (DVFS: zero data inflates MFMA clocks)
+    q, k, v = workload_qkv(torch, dev, my, rank)  # random, never zeros (DVFS: zero data inflates MFMA clocks)
     o = torch.empty_like(q)
     lse = torch.empty(1, my, N, dtype=torch.float32, device=dev)
     stream = torch.cuda.current_stream(dev)
@@ -238,14 +275,18 @@ def main() -> int:
         elapsed = time.perf_counter() - t0
         if rehearsal_pass:
             elapsed_first = elapsed
-    # the same K launches through the public entry point (per-call validation included): what a caller without a plan sees
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        fa.flash_attention_forward(q, k, v, is_causal=CAUSAL, out=o, lse=lse)
-    torch.cuda.synchronize(dev)
-    barrier()
-    elapsed_public = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, o, lse)
+    elapsed_public = None
+    if args.full:
+        # the same K launches through the public entry point (per-call validation included): what a caller without a plan sees
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            fa.flash_attention_forward(q, k, v, is_causal=CAUSAL, out=o, lse=lse)
+        torch.cuda.synchronize(dev)
+        barrier()
+        elapsed_public = time.perf_counter() - t0
     kern_ms = sorted(a.elapsed_time(b) / (hi_i - lo_i) for (lo_i, hi_i), (a, b) in zip(blocks, evs))
     launches_total = sum(a.elapsed_time(b) for a, b in evs)  # ms over all K launches
     flops_step_rank = fa.algorithmic_flops(1, my, N, D, CAUSAL)
@@ -255,7 +296,7 @@ def main() -> int:
     value = flops_per_s / 1e12
     per_rank = ranks.gather_over_ranks(info, my_tflops, dev)  # imbalance across the GPUs of the node
 
-    c4 = None if args.no_c4 else c4_slice(fa, torch, ranks, info, dev)
+    c4 = c4_slice(fa, torch, ranks, info, dev) if args.full and not args.no_c4 else None
 
     if rank == 0:
         avg_ms = launches_total / args.steps  # average launch duration over the K timed launches
@@ -277,9 +318,8 @@ def main() -> int:
             "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 5),
             # rank 0's own clock: the FIRST pass of the timed-region code in this process (its first event record costs ~0.12 ms of
-            # host time: round-over-round comparisons should use roofline.kernel_ms_avg), and K calls of flash_attention_forward
+            # host time: round-over-round comparisons should use roofline.kernel_ms_avg)
             "value_first_pass": round(flops_step_rank * args.steps / elapsed_first / 1e12, 3),
-            "value_public_api": round(flops_step_rank * args.steps / elapsed_public / 1e12, 3),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -304,16 +344,18 @@ def main() -> int:
                          "kernel_ms_min": round(kern_ms[0], 5),
                          "hbm_frac": round(bytes_step_rank / (avg_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)},
         }
+        if elapsed_public is not None:  # rank 0's own clock, K calls of flash_attention_forward
+            out["value_public_api"] = round(flops_step_rank * args.steps / elapsed_public / 1e12, 3)
         if c4 is not None:
             out["c4_slice"] = c4
-        if world == 1 and not args.no_c4:
+        if args.full and world == 1 and not args.no_c4:
             out["c5_fp8"] = c5_fp8(fa, torch, dev)
-        if world == 1 and not args.no_sweep:
+        if args.full and world == 1 and not args.no_sweep:
             out["sweep"] = sweep(fa, torch, dev)
             at = [r for r in out["sweep"] if r["seqlen"] == N]
             if at:  # the sweep's N=4096 row is the same workload: a ratio far from 1 means the timed region ramped
                 out["sweep_vs_value"] = round(at[0]["tflops"] / value, 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     ranks.finalize(info)

@@ -4,7 +4,9 @@ container on CSV files our driver wrote, and store what it returned. Data only i
   benchmark_results_mi355x.csv   written by driver/fa_driver on an MI355X (gpurun)
   csv_synthetic.csv              hand-made edge cases (naive = 0 row, short row, junk row, extra columns)
   csv_expected.json              parse_results() outputs for both
+  csv_sources.json               sha256 of the two CSV files parse_results() read
 """
+import hashlib
 import importlib.util
 import json
 import os
@@ -29,6 +31,8 @@ out = {}
 for name in ("benchmark_results_mi355x.csv", "csv_synthetic.csv"):
     out[name] = [list(x) for x in ref.parse_results(os.path.join(HERE, name))]
 json.dump(out, open(os.path.join(HERE, "csv_expected.json"), "w"), indent=1)
+src = {name: hashlib.sha256(open(os.path.join(HERE, name), "rb").read()).hexdigest() for name in out}
+json.dump(src, open(os.path.join(HERE, "csv_sources.json"), "w"), indent=1)
 print({k: [len(x) for x in v] for k, v in out.items()})
 ref.generate_svg(*ref.parse_results(os.path.join(HERE, "benchmark_results_mi355x.csv")), filename="/tmp/speedup_plot_test.svg")
 print("reference generate_svg ok:", os.path.getsize("/tmp/speedup_plot_test.svg"), "bytes")

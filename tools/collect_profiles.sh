@@ -6,11 +6,11 @@ set -o pipefail
 out=gpurun_out/${1:-prof}
 mkdir -p $out
 export TMPDIR=/tmp
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_n1_steps20_warmup5.json 2> $out/bench20.err || exit 1
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_n1_steps20_warmup5.json 2> $out/bench20.err || exit 1
 echo "bench (driver flags) done"; head -c 300 $out/bench_n1_steps20_warmup5.json; echo
-python3 bench.py --gpus 1 --steps 200 --warmup 20 > $out/bench_n1.json 2> $out/bench_n1.err || exit 1
+python3 bench.py --gpus 1 --steps 200 --warmup 20 --full > $out/bench_n1.json 2> $out/bench_n1.err || exit 1
 echo "bench (default) done"; head -c 300 $out/bench_n1.json; echo
-rocprofv3 --kernel-trace --stats -d $out/kt --output-format csv -- python3 bench.py --gpus 1 --steps 50 --warmup 10 --no-cpu-baseline --no-sweep > $out/bench_under_rocprof.json 2> $out/rocprof_kt.err || exit 1
+rocprofv3 --kernel-trace --stats -d $out/kt --output-format csv -- python3 bench.py --gpus 1 --steps 50 --warmup 10 --full --no-cpu-baseline --no-sweep > $out/bench_under_rocprof.json 2> $out/rocprof_kt.err || exit 1
 find $out/kt -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \;
 echo "kernel trace done"
 python3 tools/pmc.py $out/pmc_c3 4 16 4096 64 bf16 1 auto --sets sq1,sq2,mem1,mem2 > $out/pmc_c3.log 2>&1 || exit 1
