@@ -16,9 +16,11 @@ from .ops import (  # noqa: F401
     ForwardPlan,
     algorithmic_bytes,
     algorithmic_flops,
+    decode_paged_workspace_bytes,
     decode_workspace_bytes,
     flash_attention_backward,
     flash_attention_decode,
+    flash_attention_decode_paged,
     flash_attention_forward,
     forward_kernel_name,
     supported,

@@ -371,6 +371,66 @@ static int decode_impl(const void *q, const void *k, const void *v, void *o, flo
   return FA_OK;
 }
 
+int fa_fwd_decode_paged_supported(int q_dtype, int kv_dtype, int D, int Hq, int Hkv, int Nq, int page_size) {
+  const bool pair = (q_dtype == kv_dtype && (q_dtype == FA_DTYPE_F16 || q_dtype == FA_DTYPE_BF16 || q_dtype == FA_DTYPE_FP8_E4M3)) ||
+                    (q_dtype == FA_DTYPE_BF16 && kv_dtype == FA_DTYPE_FP8_E4M3);
+  const bool pow2 = page_size >= 16 && page_size <= 256 && (page_size & (page_size - 1)) == 0;
+  return pair && pow2 && fa_fwd_decode_supported(q_dtype, D, Hq, Hkv, Nq);
+}
+long long fa_fwd_decode_paged_workspace_bytes(int B, int Hq, int Hkv, int Nq, int D, int page_size, int max_pages_per_seq) {
+  if (page_size < 1 || max_pages_per_seq < 1 || (long long)page_size * max_pages_per_seq > (1 << 30)) return 0;
+  return fa_fwd_decode_workspace_bytes(B, Hq, Hkv, Nq, page_size * max_pages_per_seq, D);  // the dense decode's at the capacity
+}
+int fa_fwd_decode_paged(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *block_table,
+                        const int *seqlens_k, int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages, int max_pages_per_seq,
+                        float scale, long long q_batch_stride, long long q_head_stride, long long kv_page_stride, long long kv_head_stride,
+                        long long kv_row_stride, long long block_table_stride, int is_causal, int q_dtype, int kv_dtype, void *workspace,
+                        long long workspace_bytes, void *hip_stream) {
+  g_err[0] = 0;
+  if (!q || !k_pages || !v_pages || !o || !block_table || !seqlens_k || !workspace) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: null pointer");
+  if (B < 1 || Hq < 1 || Hkv < 1 || Nq < 1 || D < 1 || page_size < 1 || num_pages < 1 || max_pages_per_seq < 1)
+    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: sizes must be >= 1");
+  if (Hq % Hkv) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: Hq=%d must be a multiple of Hkv=%d", Hq, Hkv);
+  if (!(scale > 0.0f)) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: scale=%g must be > 0", (double)scale);
+  if (!fa_fwd_decode_paged_supported(q_dtype, kv_dtype, D, Hq, Hkv, Nq, page_size))
+    return fail(FA_ERR_UNSUPPORTED, "fa_fwd_decode_paged: needs (q, kv) dtypes f16/f16, bf16/bf16, e4m3/e4m3 or bf16/e4m3, D = 64 | 128, (Hq / Hkv) * Nq "
+                "<= 32 packed query rows and a page size of 16, 32, 64, 128 or 256; got q=%s kv=%s D=%d Hq=%d Hkv=%d Nq=%d page_size=%d",
+                fa_dtype_name(q_dtype), fa_dtype_name(kv_dtype), D, Hq, Hkv, Nq, page_size);
+  if (block_table_stride < max_pages_per_seq)
+    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: block_table_stride=%lld < max_pages_per_seq=%d", block_table_stride, max_pages_per_seq);
+  const int kv8 = kv_dtype == FA_DTYPE_FP8_E4M3, eb = kv8 ? 1 : 2;
+  const int dsm = q_dtype == FA_DTYPE_FP8_E4M3 ? 16 : 8, ksm = kv8 ? 16 : 8;  // keeps every row 16-byte aligned
+  if (q_head_stride < (long long)Nq * D || (q_batch_stride % dsm) || (q_head_stride % dsm) || q_batch_stride < 0 ||
+      (Hq > 1 && B > 1 && q_batch_stride < q_head_stride) || kv_row_stride < D || kv_head_stride < D || kv_page_stride < D ||
+      (kv_page_stride % ksm) || (kv_head_stride % ksm) || (kv_row_stride % ksm) || block_table_stride > 0x7fffffffLL)
+    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: bad strides");
+  // a page's rows of one head are addressed by 32-bit offsets from the page's own 64-bit base
+  if ((double)page_size * kv_row_stride * eb >= 2147483648.0) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: one page of one head exceeds 2 GiB");
+  if (((uintptr_t)q | (uintptr_t)k_pages | (uintptr_t)v_pages | (uintptr_t)o | (uintptr_t)workspace) & 15)
+    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: tensors and workspace must be 16-byte aligned");
+  if (((uintptr_t)block_table | (uintptr_t)seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: block_table / seqlens_k must be int32-aligned");
+  if ((long long)page_size * max_pages_per_seq > (1 << 30)) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: capacity above 2^30 keys");
+  const int cap = page_size * max_pages_per_seq;
+  const long long need = fa::decode_workspace_bytes(B, Hq, Hkv, Nq, cap, D);
+  if (workspace_bytes < need)
+    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: workspace of %lld bytes, fa_fwd_decode_paged_workspace_bytes() asks for %lld", workspace_bytes, need);
+  if ((long long)B * Hq * Nq > 0x7fffffffLL || (long long)B * Hkv * 256 > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: grid too large");
+  fa::DecodePagedParams p;
+  p.q = q; p.k = k_pages; p.v = v_pages; p.o = o; p.lse = lse; p.ws = (float *)workspace;
+  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Nq = Nq; p.Nk = cap; p.scale = scale;
+  p.q_bs = q_batch_stride; p.q_hs = q_head_stride; p.kv_bs = 0; p.kv_hs = kv_head_stride;
+  p.is_causal = is_causal ? 1 : 0;
+  p.S = fa::decode_splits(B, Hkv, cap, D, kv8);  // the dense decode's split rule at the capacity: bit-identical to it on full caches
+  p.block_table = block_table; p.seqlens = seqlens_k;
+  p.page_stride = kv_page_stride; p.row_stride = kv_row_stride;
+  p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
+  p.lp = 0;
+  while ((1 << p.lp) < page_size) ++p.lp;
+  const hipError_t e = fa::launch_decode_paged(p, D, q_dtype, kv8, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "fa_fwd_decode_paged: launch failed: %s", hipGetErrorString(e));
+  return FA_OK;
+}
+
 long long fa_bwd_workspace_bytes(int B, int H, int N) { return (long long)B * H * N * 4; }
 // elements from the first to one past the last of a [B,H,N,D] tensor under (batch, head) strides, rounded up to 16
 static long long extent16(int B, int H, int N, int D, long long bs, long long hs) {

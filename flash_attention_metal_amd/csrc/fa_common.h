@@ -60,6 +60,15 @@ struct DecodeParams {
   int q8 = 0;  // e4m3 K / V: the queries are e4m3 too (else 16-bit)
 };
 
+// one fa_fwd_decode_paged call: k / v are the page pools, kv_hs their head stride, Nk the capacity max_pages * page size (kv_bs unused).
+// Key j of sequence b is slot j % P of page block_table[b * bt_stride + j / P]; both tables are device memory read by the kernels.
+struct DecodePagedParams : DecodeParams {
+  const int *block_table, *seqlens;
+  long long page_stride, row_stride;  // elements
+  int bt_stride, num_pages, max_pages;
+  int lp;  // log2 of the page size (16 .. 256)
+};
+
 // dtype tags
 struct F32 {};
 struct F16 {};
@@ -86,6 +95,7 @@ hipError_t launch_decode(const DecodeParams &p, int D, int dtype, int kv8, hipSt
 bool decode_supported(int dtype, int D);
 int decode_splits(int B, int Hkv, int Nk, int D, int kv8);  // kv8: e4m3 inputs (one LDS image per item: twice the items per CU)
 long long decode_workspace_bytes(int B, int Hq, int Hkv, int Nq, int Nk, int D);
+hipError_t launch_decode_paged(const DecodePagedParams &p, int D, int dtype, int kv8, hipStream_t s);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "fa_mfma_common.h"
 
@@ -63,8 +64,17 @@ __device__ __forceinline__ u32x4 widen8(unsigned w0, unsigned w1) {
   return u32x4{r[0], r[1], r[2], r[3]};
 }
 
-template <typename Tag, int D, int QT, bool CAUSAL, bool KV8>
-__global__ __launch_bounds__(64) void decode_partial_kernel(DecodeParams p) {
+// PRM = DecodePagedParams (PAGED: fa_fwd_decode_paged; the DecodeParams instantiations are fa_fwd_decode's kernels, unchanged): the
+// item's sequence has its own length L_b
+// (read once from device memory, clamped to the capacity p.Nk) in place of Nk, and every K / V piece comes from the page the block
+// table names for it, through a descriptor built on that page's 64-bit base whose range covers only the page's valid rows -- so rows
+// >= L_b, out-of-range pages and whatever a page holds past L_b read as hardware zeros (the whole offset sits in voffset, inside the
+// range check), 32-bit offsets never leave a page, and the pool may exceed 4 GiB. Pages hold >= 16 rows and start at multiples of
+// their size: every 1-KiB LDS-DMA piece (4 / 8 rows) and every 16-byte-per-lane register load (<= 16 rows) lies inside ONE page,
+// whose table entry is wave-uniform. The entries of the next tile to stage are loaded one tile ahead.
+template <typename Tag, int D, int QT, bool CAUSAL, bool KV8, typename PRM = DecodeParams>
+__global__ __launch_bounds__(64) void decode_partial_kernel(PRM p) {
+  constexpr bool PAGED = std::is_same<PRM, DecodePagedParams>::value;
   using M = MD16<Tag>;
   using vec8 = typename M::vec8;
   using elem = typename M::elem;
@@ -88,13 +98,15 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(DecodeParams p) {
   const int bkv = item / S, s = item - bkv * S;
   const int b = bkv / p.Hkv, hkv = bkv - b * p.Hkv;
   const int G = p.Hq / p.Hkv, R = G * p.Nq;
-  const int coff = p.Nk - p.Nq;
-  const int nT = (p.Nk + BN - 1) / BN;
+  int Nk = p.Nk;  // keys of this item's sequence
+  if constexpr (PAGED) Nk = min(max(__builtin_amdgcn_readfirstlane(p.seqlens[b]), 0), p.max_pages << p.lp);
+  const int coff = Nk - p.Nq;
+  const int nT = (Nk + BN - 1) / BN;
   const int t0 = (int)((long long)s * nT / S), t1 = (int)((long long)(s + 1) * nT / S);
 
-  const long long base_kv = (long long)b * p.kv_bs + (long long)hkv * p.kv_hs;
+  const long long base_kv = PAGED ? 0 : (long long)b * p.kv_bs + (long long)hkv * p.kv_hs;
   constexpr int EB = KV8 ? 1 : 2;  // bytes per input element
-  const unsigned kv_bytes = (unsigned)p.Nk * D * EB;
+  const unsigned kv_bytes = (unsigned)Nk * D * EB;
   const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.k + base_kv * EB), 0, kv_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.v + base_kv * EB), 0, kv_bytes, 0x00020000);
 
@@ -107,7 +119,7 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(DecodeParams p) {
     const int r = 16 * qt + c;
     const int gi = r / p.Nq, iq = r - gi * p.Nq;
     const bool valid = r < R;
-    rlim[qt] = (CAUSAL && valid) ? iq + coff : p.Nk - 1;
+    rlim[qt] = (CAUSAL && valid) ? iq + coff : Nk - 1;
     const long long qoff = (long long)b * p.q_bs + (long long)(hkv * G + gi) * p.q_hs + (long long)iq * D;
     const elem *qp = (const elem *)p.q + qoff;
 #pragma unroll
@@ -145,7 +157,70 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(DecodeParams p) {
   const int drow = lane / CPR, dpc = lane % CPR;
   const unsigned dma_k0 = (unsigned)(drow * RB + ((dpc ^ ((D == 64) ? ((drow >> 1) & 7) : (drow & 15))) << 4));
   const unsigned dma_v0 = (unsigned)(drow * RB + ((dpc ^ ((D == 64) ? (((drow >> 1) & 3) << 1) : ((drow & 7) << 1))) << 4));
-  auto stage_dma = [&](int t, int buf) {
+
+  // ---- PAGED: pg[] holds the table entries of the next tile to stage (its pages: max(1, 64 / P), at most four), loaded one tile
+  // ahead; tile_pages() turns them into wave-uniform page offsets and descriptor ranges, page_rsrc() gives the descriptors of the
+  // page that holds key kj of the tile and the byte offset of that key's slot in it
+  int lp = 0, pg[4] = {-1, -1, -1, -1};
+  long long poff[4] = {0, 0, 0, 0};  // elements, page base + key head of entry k
+  unsigned prec[4] = {0u, 0u, 0u, 0u}, rsb = 0u;  // descriptor range of entry k (bytes); row stride in bytes
+  auto fetch_pages = [&](int t) __attribute__((always_inline)) {
+    if constexpr (PAGED) {
+      const int *tbl = p.block_table + (long long)b * p.bt_stride;
+      const int i0 = (t * BN) >> lp, npg = max(1, BN >> lp);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) pg[k] = k < npg ? tbl[min(i0 + k, p.max_pages - 1)] : -1;  // (never past the row's max_pages entries)
+    }
+  };
+  auto tile_pages = [&](int t) __attribute__((always_inline)) {
+    if constexpr (PAGED) {
+      const int P = 1 << lp, key0 = (t * BN) & -P;  // first key of the tile's first page
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int page = __builtin_amdgcn_readfirstlane(pg[k]);
+        const int nv = min(Nk - (key0 + k * P), P);  // valid rows of the page
+        const bool ok = nv > 0 && (unsigned)page < (unsigned)p.num_pages;  // an index outside the pool reads as zeros
+        poff[k] = ok ? (long long)page * p.page_stride + (long long)hkv * p.kv_hs : 0;
+        prec[k] = ok ? (unsigned)(nv - 1) * rsb + D * EB : 0u;
+      }
+    }
+  };
+  auto page_rsrc = [&](int t, int kj, __amdgpu_buffer_rsrc_t &rkp, __amdgpu_buffer_rsrc_t &rvp) __attribute__((always_inline)) -> unsigned {
+    // entry kj >> lp: kj is a compile-time constant, so this selects between (at most) three fixed entries: lp = 4, 5, >= 6
+    const int e4 = (kj >> 4) & 3, e5 = (kj >> 5) & 3;
+    const long long off = lp == 4 ? poff[e4] : lp == 5 ? poff[e5] : poff[0];
+    const unsigned nrec = lp == 4 ? prec[e4] : lp == 5 ? prec[e5] : prec[0];
+    rkp = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.k + off * EB), 0, nrec, 0x00020000);
+    rvp = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.v + off * EB), 0, nrec, 0x00020000);
+    return (unsigned)((t * BN + kj) & ((1 << lp) - 1)) * rsb;
+  };
+  unsigned pdma_row = 0u;  // PAGED: drow rows at the pool's row stride
+  if constexpr (PAGED) {
+    lp = p.lp;
+    rsb = (unsigned)p.row_stride * EB;
+    pdma_row = (unsigned)drow * rsb;
+  }
+  auto stage_dma_paged = [&](int t, int buf) __attribute__((always_inline)) {
+    tile_pages(t);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const unsigned kxo = (D == 64) ? (unsigned)((j & 1) << 6) : (unsigned)((j & 3) << 6);
+      const unsigned vxo = (D == 64) ? 0u : (unsigned)((j & 1) << 7);
+      __amdgpu_buffer_rsrc_t rkp, rvp;
+      const unsigned so = page_rsrc(t, j * RPP, rkp, rvp) + pdma_row;  // (the whole offset in voffset: inside the range check)
+      const unsigned lk = (unsigned)(__UINTPTR_TYPE__)Kbuf + buf * TILE + j * 1024;
+      const unsigned lv = (unsigned)(__UINTPTR_TYPE__)Vbuf + buf * TILE + j * 1024;
+      const unsigned ko = so + ((dma_k0 % RB) ^ kxo), vo = so + ((dma_v0 % RB) ^ vxo);
+      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lk), "v"(ko), "s"(rkp) : "memory");
+      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lv), "v"(vo), "s"(rvp) : "memory");
+    }
+    fetch_pages(t + 1);
+  };
+  auto stage_dma = [&](int t, int buf) __attribute__((always_inline)) {
+    if constexpr (PAGED) {
+      stage_dma_paged(t, buf);
+      return;
+    }
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
       const unsigned kxo = (D == 64) ? (unsigned)((j & 1) << 6) : (unsigned)((j & 3) << 6);  // ((row >> 1) & 7) gains 4 on odd pieces / (row & 15) gains 4 (j & 3)
@@ -166,8 +241,23 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(DecodeParams p) {
   constexpr int DEPTH = (KV8 && D == 64) ? FA_DECODE_KV8_DEPTH : 1;
   static_assert(EB == 1 || EB == 2, "");
   u32x4 kraw[DEPTH][NL], vraw[DEPTH][NL];
-  auto load_raw = [&](int t, auto slotc) {
+  auto load_raw = [&](int t, auto slotc) __attribute__((always_inline)) {
     constexpr int slot = decltype(slotc)::value;
+    if constexpr (PAGED) {  // load i: rows RPL i .. RPL i + RPL - 1 of the tile (<= 16: one page), lane -> row lane / LPR, byte 16 (lane % LPR)
+      static_assert(DEPTH == 1, "the paged path stages one tile ahead");
+      constexpr int LPR = D * EB / 16, RPL = 64 / LPR;
+      tile_pages(t);
+      const unsigned lo = (unsigned)(lane / LPR) * rsb + (unsigned)(lane % LPR) * 16;
+#pragma unroll
+      for (int i = 0; i < NL; ++i) {
+        __amdgpu_buffer_rsrc_t rkp, rvp;
+        const unsigned off = page_rsrc(t, i * RPL, rkp, rvp) + lo;
+        kraw[slot][i] = __builtin_amdgcn_raw_buffer_load_b128(rkp, off, 0, 0);
+        vraw[slot][i] = __builtin_amdgcn_raw_buffer_load_b128(rvp, off, 0, 0);
+      }
+      fetch_pages(t + 1);
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const unsigned off = (unsigned)t * (BN * D * EB) + (unsigned)(i * 64 + lane) * 16;
@@ -241,10 +331,10 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(DecodeParams p) {
         }
       }
       // ---- mask: key > the row's limit (causal, bottom-right aligned) or key >= Nk
-      if (kv0 + BN > p.Nk || (CAUSAL && kv0 + BN - 1 > coff)) {
+      if (kv0 + BN > Nk || (CAUSAL && kv0 + BN - 1 > coff)) {
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-          const int lim = min(rlim[qt], p.Nk - 1) - kv0 - 4 * g;
+          const int lim = min(rlim[qt], Nk - 1) - kv0 - 4 * g;
 #pragma unroll
           for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
@@ -300,6 +390,7 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(DecodeParams p) {
       }
   };
   if (t0 < t1) {
+    fetch_pages(t0);
     if constexpr (RS) {
       load_raw(t0, std::integral_constant<int, 0>{});
       if constexpr (DEPTH == 2) {
@@ -339,7 +430,8 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(DecodeParams p) {
 // parallel (wave reductions for M and l), the weights 2^(m_s - M) go through LDS, and thread d folds element d (and d + 64) of the S
 // partial rows with eight loads in flight (a serial loop over the splits -- one dependent ~0.4 us read each -- cost more than the
 // streaming kernel itself: 47 us at S = 128).
-template <typename Tag, int D, int QT>
+// PAGED: a row that saw no visible key at all (L_b = 0, or causal with i + L_b < Nq) has lsum = 0: O = 0 exactly and LSE = -inf
+template <typename Tag, int D, int QT, bool PAGED = false>
 __global__ __launch_bounds__(64) void decode_combine_kernel(DecodeParams p) {
   using elem = typename MD16<Tag>::elem;
   __shared__ float wgt[256];
@@ -393,11 +485,11 @@ __global__ __launch_bounds__(64) void decode_combine_kernel(DecodeParams p) {
   for (; s < S; ++s)
 #pragma unroll
     for (int e = 0; e < D / 64; ++e) acc[e] += wr[(size_t)s * IST + 64 * e] * wgt[s];
-  const float inv = 1.0f / lsum;
+  const float inv = (PAGED && !(lsum > 0.0f)) ? 0.0f : 1.0f / lsum;
   elem *op = (elem *)p.o + (long long)b * p.q_bs + (long long)hq * p.q_hs + (long long)iq * D;
 #pragma unroll
   for (int e = 0; e < D / 64; ++e) op[lane + 64 * e] = (elem)(acc[e] * inv);
-  if (p.lse != nullptr && lane == 0) p.lse[row_id] = (M + log2f(lsum)) * 0.6931471805599453f;
+  if (p.lse != nullptr && lane == 0) p.lse[row_id] = (PAGED && !(lsum > 0.0f)) ? -INFINITY : (M + log2f(lsum)) * 0.6931471805599453f;
 }
 
 // ---------------------------------------------------------------------------
@@ -445,6 +537,37 @@ static hipError_t launch_decode_q(const DecodeParams &p, hipStream_t s) {
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((decode_combine_kernel<Tag, D, QT>), dim3(p.B * p.Hq * p.Nq), dim3(64), 0, s, p);
   return hipGetLastError();
+}
+
+template <typename Tag, int D, int QT, bool KV8 = false>
+static hipError_t launch_decode_paged_q(const DecodePagedParams &p, hipStream_t s) {
+  const size_t smem = ((KV8 || FA_DECODE_REGSTAGE) ? 2 : 4) * (size_t)BN * D * 2;
+  (void)hipGetLastError();
+  auto kern = p.is_causal ? decode_partial_kernel<Tag, D, QT, true, KV8, DecodePagedParams> : decode_partial_kernel<Tag, D, QT, false, KV8, DecodePagedParams>;
+  if (smem > 48 * 1024) { hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem); if (e != hipSuccess) return e; }
+  hipLaunchKernelGGL(kern, dim3(p.B * p.Hkv * p.S), dim3(64), smem, s, p);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((decode_combine_kernel<Tag, D, QT, true>), dim3(p.B * p.Hq * p.Nq), dim3(64), 0, s, (const DecodeParams &)p);
+  return hipGetLastError();
+}
+
+hipError_t launch_decode_paged(const DecodePagedParams &p0, int D, int dtype, int kv8, hipStream_t s) {
+  DecodePagedParams p = p0;
+  p.q8 = (dtype == FA_DTYPE_FP8_E4M3);
+  const int R = (p.Hq / p.Hkv) * p.Nq, QT = (R + 15) / 16;
+  auto go = [&](auto tag) -> hipError_t {
+    using Tag = decltype(tag);
+    if (D == 64) return QT == 1 ? launch_decode_paged_q<Tag, 64, 1>(p, s) : launch_decode_paged_q<Tag, 64, 2>(p, s);
+    if (D == 128) return QT == 1 ? launch_decode_paged_q<Tag, 128, 1>(p, s) : launch_decode_paged_q<Tag, 128, 2>(p, s);
+    return hipErrorInvalidValue;
+  };
+  if (kv8 || dtype == FA_DTYPE_FP8_E4M3) {
+    if (D == 64) return QT == 1 ? launch_decode_paged_q<BF16, 64, 1, true>(p, s) : launch_decode_paged_q<BF16, 64, 2, true>(p, s);
+    if (D == 128) return QT == 1 ? launch_decode_paged_q<BF16, 128, 1, true>(p, s) : launch_decode_paged_q<BF16, 128, 2, true>(p, s);
+    return hipErrorInvalidValue;
+  }
+  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
 }
 
 // dtype: of the queries (and of K / V unless kv8); kv8: K and V are e4m3 (dtype FP8: so are the queries; BF16: an e4m3 cache under

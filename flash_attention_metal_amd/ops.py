@@ -247,6 +247,88 @@ def flash_attention_decode(
     return out, lse
 
 
+def decode_paged_workspace_bytes(B: int, Hq: int, Hkv: int, Nq: int, D: int, page_size: int, max_pages_per_seq: int) -> int:
+    return int(load_library().fa_fwd_decode_paged_workspace_bytes(B, Hq, Hkv, Nq, D, page_size, max_pages_per_seq))
+
+
+def flash_attention_decode_paged(
+    q: torch.Tensor,
+    k_pages: torch.Tensor,
+    v_pages: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens_k: torch.Tensor,
+    is_causal: bool = False,
+    scale: Optional[float] = None,
+    layout: str = "HND",
+    return_lse: bool = True,
+    out: Optional[torch.Tensor] = None,
+    lse: Optional[torch.Tensor] = None,
+    workspace: Optional[torch.Tensor] = None,
+    stream: Optional[int] = None,
+) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """A decode step against a paged KV cache (include/fa_mi355.h fa_fwd_decode_paged): q [B,Hq,Nq,D]; k_pages / v_pages one pool
+    each, [num_pages, Hkv, P, D] (layout "HND") or [num_pages, P, Hkv, D] ("NHD"), P in {16, 32, 64, 128, 256}; block_table int32
+    [B, max_pages_per_seq] and seqlens_k int32 [B], both contiguous on q's device and read by the kernels only -- nothing here
+    synchronises or reads device values, so the call can be captured in a graph and replayed after the tables change in place.
+    dtypes as flash_attention_decode (f16, bf16, e4m3, or bf16 queries on an e4m3 pool). A row with no visible key gets O = 0 and
+    LSE = -inf. `workspace`: a uint8 device tensor of at least decode_paged_workspace_bytes(...) bytes (allocated here if None)."""
+    lib = load_library()
+    if q.dim() != 4 or k_pages.dim() != 4 or k_pages.shape != v_pages.shape:
+        raise ValueError("q [B,Hq,Nq,D], k_pages / v_pages one [num_pages,Hkv,P,D] (HND) or [num_pages,P,Hkv,D] (NHD) shape")
+    if layout not in ("HND", "NHD"):
+        raise ValueError(f"layout must be 'HND' or 'NHD', got {layout!r}")
+    if not all(t.is_cuda and t.device == q.device for t in (q, k_pages, v_pages, block_table, seqlens_k)):
+        raise ValueError("flash_attention_decode_paged needs q, the pools and both tables on one device: there is no CPU path")
+    B, Hq, Nq, D = q.shape
+    if layout == "HND":
+        num_pages, Hkv, P, Dk = k_pages.shape
+        ps, hs, rs, es = k_pages.stride()
+    else:
+        num_pages, P, Hkv, Dk = k_pages.shape
+        ps, rs, hs, es = k_pages.stride()
+    if Dk != D or Hq % Hkv or es != 1 or v_pages.stride() != k_pages.stride():
+        raise ValueError(f"incompatible q {tuple(q.shape)} and pools {tuple(k_pages.shape)} (same D, Hq % Hkv == 0, unit element stride, "
+                         "k_pages and v_pages with one set of strides)")
+    if (block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or not block_table.is_contiguous()
+            or seqlens_k.dtype != torch.int32 or seqlens_k.shape != (B,) or not seqlens_k.is_contiguous()):
+        raise ValueError("block_table must be a contiguous int32 [B, max_pages_per_seq] tensor and seqlens_k a contiguous int32 [B] one")
+    fp8 = getattr(torch, "float8_e4m3fn", None)
+    pairs = {(torch.float16, torch.float16), (torch.bfloat16, torch.bfloat16), (fp8, fp8), (torch.bfloat16, fp8)}
+    if v_pages.dtype != k_pages.dtype or (q.dtype, k_pages.dtype) not in pairs:
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k_pages.dtype} {v_pages.dtype} (one of f16 / bf16 / e4m3, or bf16 queries on "
+                         "an e4m3 pool)")
+    odt = torch.bfloat16 if q.dtype == fp8 else q.dtype
+    qbs, qhs = _strides(q)
+    max_pages = block_table.shape[1]
+    if out is None:
+        out = torch.empty_strided((B, Hq, Nq, D), q.stride(), dtype=odt, device=q.device)
+    elif not out.is_cuda or out.device != q.device or out.dtype != odt or out.shape != q.shape or _strides(out) != (qbs, qhs):
+        raise ValueError("out must be a device tensor with q's shape/strides")
+    if return_lse and lse is None:
+        lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device)
+    if lse is not None and (not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or not lse.is_contiguous()
+                            or lse.numel() != B * Hq * Nq):
+        raise ValueError("lse must be contiguous fp32 [B,Hq,Nq] on q's device")
+    if workspace is None:
+        workspace = torch.empty(max(decode_paged_workspace_bytes(B, Hq, Hkv, Nq, D, P, max(max_pages, 1)), 16), dtype=torch.uint8,
+                                device=q.device)
+    elif not workspace.is_cuda or workspace.device != q.device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous uint8 device tensor")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if stream is None:
+        stream = torch.cuda.current_stream(q.device).cuda_stream
+    with torch.cuda.device(q.device):
+        st = lib.fa_fwd_decode_paged(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(),
+                                     lse.data_ptr() if lse is not None else None, block_table.data_ptr(), seqlens_k.data_ptr(),
+                                     B, Hq, Hkv, Nq, D, P, num_pages, max_pages, float(scale), qbs, qhs, ps, hs, rs,
+                                     block_table.stride(0), int(bool(is_causal)), _TORCH2FA[q.dtype], _TORCH2FA[k_pages.dtype],
+                                     workspace.data_ptr(), workspace.numel(), stream)
+    if st != 0:
+        raise FaError(st, lib.fa_last_error().decode())
+    return out, lse
+
+
 def flash_attention_backward(
     q: torch.Tensor,
     k: torch.Tensor,

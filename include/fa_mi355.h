@@ -190,6 +190,34 @@ int fa_fwd_decode_kv8(const void *q, const void *k, const void *v, void *o, floa
                       int is_causal, int q_dtype, void *workspace, long long workspace_bytes, void *hip_stream);
 long long fa_fwd_decode_workspace_bytes(int B, int Hq, int Hkv, int Nq, int Nk, int D);
 int fa_fwd_decode_supported(int dtype, int D, int Hq, int Hkv, int Nq);
+/*
+ * The same decode step against a PAGED KV cache with a length per sequence (the block-table layout of serving engines; not in the
+ * reference). k_pages / v_pages are page pools of num_pages pages of page_size (P) key slots each, sharing one set of element strides:
+ * element d of slot r of key head h in page p sits at p * kv_page_stride + h * kv_head_stride + r * kv_row_stride + d. Both usual layouts
+ * work: HND [num_pages, Hkv, P, D] (strides Hkv*P*D, P*D, D) and NHD [num_pages, P, Hkv, D] (strides P*Hkv*D, D, Hkv*D); strides are
+ * multiples of 8 elements (16 for e4m3), bases 16-byte aligned; the pool may exceed 4 GiB. block_table (int32, [B, block_table_stride],
+ * block_table_stride >= max_pages_per_seq) and seqlens_k (int32, [B]) are DEVICE memory read by the kernels -- the host never reads
+ * them, so one captured graph serves every step: key j < L_b = seqlens_k[b] of sequence b is slot j % P of page block_table[b][j / P].
+ * Lengths are clamped to [0, max_pages_per_seq * P]. q, o, lse as in fa_fwd_decode; causal is bottom-right aligned PER SEQUENCE (key j
+ * visible to query i iff j <= i + L_b - Nq). A row with no visible key (L_b = 0, or causal with i + L_b < Nq) gets O = 0 exactly and
+ * LSE = -inf. Results depend neither on slots >= L_b of a sequence's last page (NaN there is harmless: they read as zeros), nor on table
+ * entries past ceil(L_b / P), nor on the workspace's prior contents, and are bitwise reproducible; a page index outside
+ * [0, num_pages) reads as zeros and touches nothing outside the pool. With every L_b at the capacity max_pages_per_seq * P the results
+ * are bit-identical to fa_fwd_decode / fa_fwd_decode_kv8 on the gathered dense cache (same key splits, same workspace size).
+ * (q_dtype, kv_dtype): (f16, f16), (bf16, bf16), (e4m3, e4m3) and (bf16, e4m3), the last two with bf16 O; D = 64 | 128;
+ * (Hq / Hkv) * Nq <= 32; P in {16, 32, 64, 128, 256}: anything else FA_ERR_UNSUPPORTED. Tolerances are those of fa_fwd_decode.
+ * Bad pointers, sizes or strides, a short workspace or block_table_stride < max_pages_per_seq: FA_ERR_INVALID_ARG before any launch.
+ */
+int fa_fwd_decode_paged(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                        const int *block_table, const int *seqlens_k,
+                        int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages, int max_pages_per_seq,
+                        float scale, long long q_batch_stride, long long q_head_stride,
+                        long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                        long long block_table_stride, int is_causal, int q_dtype, int kv_dtype,
+                        void *workspace, long long workspace_bytes, void *hip_stream);
+/* = fa_fwd_decode_workspace_bytes(B, Hq, Hkv, Nq, page_size * max_pages_per_seq, D): depends on the capacity only (0 if invalid) */
+long long fa_fwd_decode_paged_workspace_bytes(int B, int Hq, int Hkv, int Nq, int D, int page_size, int max_pages_per_seq);
+int fa_fwd_decode_paged_supported(int q_dtype, int kv_dtype, int D, int Hq, int Hkv, int Nq, int page_size);
 
 /*
  * Backward of the operator (row f1 of the scope table): the reference binds it as
