@@ -2,6 +2,7 @@
 // Validation + dispatch only; every kernel lives in its own file.
 #include <stdarg.h>
 #include <algorithm>
+#include <initializer_list>
 #include <stdio.h>
 #include <string.h>
 
@@ -16,6 +17,65 @@ int fail(int code, const char *fmt, ...) {
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
+}
+
+// ---- argument rules shared by the launch entry points: each returns FA_OK, or fails with a message that names the entry point `fn`.
+// What the entry points require differently is the caller's argument or a line of its own (making it one rule would change what
+// is accepted, which is for a later change):
+//  - batch_stride >= head_stride: fa_fwd whenever H > 1, the backward whenever H > 1 (and on k / v whenever Hkv > 1); fa_fwd_exv
+//    and the dense and paged decode only when B > 1 as well;
+//  - the head-size guards: fa_fwd / fa_fwd_exv (max(Nq, Nk) + 128) * D * in_bytes < 4 GiB, the decode (Nk + 128) * D * 2 < 4 GiB,
+//    the backward max(Nq, Nk) * D * 2 < 4 GiB (no +128) and (max(Nq, Nk) + 128) * D * 2 < 2 GiB for its padded head dims, the
+//    paged decode 2 GiB per page of one head;
+//  - the grid guards: B * H * ceil(Nq / 128) (fa_fwd, fa_fwd_exv) or B * H * ceil(max(Nq, Nk) / 128) (backward) below 2^31;
+//    B * Hq * Nq and B * Hkv * 256 for the decodes;
+//  - a missing device: FA_ERR_NO_DEVICE from fa_fwd, FA_ERR_LAUNCH from every other entry point.
+#define TRY(check) do { if (const int st_ = (check)) return st_; } while (0)
+
+int nonnull(const char *fn, std::initializer_list<const void *> ptrs) {
+  for (const void *p : ptrs)
+    if (!p) return fail(FA_ERR_INVALID_ARG, "%s: null pointer", fn);
+  return FA_OK;
+}
+int positive(const char *fn, std::initializer_list<int> sizes) {
+  for (int n : sizes)
+    if (n < 1) return fail(FA_ERR_INVALID_ARG, "%s: sizes must be >= 1", fn);
+  return FA_OK;
+}
+int grouped(const char *fn, int Hq, int Hkv) {
+  return Hkv >= 1 && Hq % Hkv == 0 ? FA_OK : fail(FA_ERR_INVALID_ARG, "%s: Hq=%d must be a multiple of Hkv=%d", fn, Hq, Hkv);
+}
+int causal_fits(const char *fn, int is_causal, int Nq, int Nk) {
+  return !is_causal || Nk >= Nq ? FA_OK
+                                : fail(FA_ERR_UNSUPPORTED, "%s: causal needs Nk >= Nq (bottom-right alignment would leave empty rows)", fn);
+}
+int scale_ok(const char *fn, float scale) {
+  return scale > 0.0f ? FA_OK : fail(FA_ERR_INVALID_ARG, "%s: scale=%g must be > 0", fn, (double)scale);
+}
+int stride_mult(int dtype) { return dtype == FA_DTYPE_FP8_E4M3 ? 16 : 8; }  // elements: keeps every head 16-byte aligned
+// one [B, H, N, D] operand under (batch, head) element strides; `what` names it in the message ("" or "key/value ")
+int strides_ok(const char *fn, const char *what, int N, int D, long long bs, long long hs, int mult, bool batch_over_head) {
+  if (hs < (long long)N * D || bs < 0 || (batch_over_head && bs < hs) || (bs % mult) || (hs % mult))
+    return fail(FA_ERR_INVALID_ARG, "%s: bad %sstrides (batch %lld, head %lld): a head holds %lld elements, strides are multiples of %d",
+                fn, what, bs, hs, (long long)N * D, mult);
+  return FA_OK;
+}
+int aligned16(const char *fn, const char *what, std::initializer_list<const void *> ptrs) {
+  for (const void *p : ptrs)
+    if ((uintptr_t)p & 15) return fail(FA_ERR_INVALID_ARG, "%s: %s must be 16-byte aligned", fn, what);
+  return FA_OK;
+}
+int head_fits(const char *fn, double head_bytes, int gib, const char *why) {
+  return head_bytes < gib * 1073741824.0 ? FA_OK : fail(FA_ERR_INVALID_ARG, "%s: one head exceeds %d GiB%s", fn, gib, why);
+}
+int grid_fits(const char *fn, long long heads, int rows) {  // heads x blocks of 128 rows fit an int
+  return heads <= 0x7fffffffLL / ((rows + 127) / 128) ? FA_OK : fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+}
+int workspace_fits(const char *fn, long long bytes, long long need, const char *sizer) {
+  return bytes >= need ? FA_OK : fail(FA_ERR_INVALID_ARG, "%s: workspace of %lld bytes, %s() asks for %lld", fn, bytes, sizer, need);
+}
+int launched(const char *fn, hipError_t e) {
+  return e == hipSuccess ? FA_OK : fail(FA_ERR_LAUNCH, "%s: launch failed: %s", fn, hipGetErrorString(e));
 }
 }  // namespace
 
@@ -84,22 +144,30 @@ int fa_resolve_variant(int dtype, int D) {
   return FA_ERR_UNSUPPORTED;
 }
 
-// AUTO between the matrix-core kernels (interleaved A/B on MI355X): the split-KV kernel wins on
-// grids far smaller than the chip, the 64-row two-split form and the eight-wave form of the 128-row kernel on grids of up to
-// two / one workgroup(s) per CU; everywhere else the 128-row kernel is fastest.
-int fa_resolve_variant_for(int dtype, int D, int B, int H, int N, int is_causal) {
-  const int v = fa_resolve_variant(dtype, D);
-  if (v != FA_VARIANT_MFMA) return v;
-  // (round 2 sent long head_dim-128 sequences to the paired-block kernel; since the 128-row kernel stages its tiles by
-  // LDS-DMA it is 8-10 % ahead there too -- config 4 shard 1295 vs 1181 TFLOP/s, profiles/r03/ab_dma_late_and_d128_auto.log --
-  // and round 4 retired FA_VARIANT_MFMA_PP: the kernel is kept under tools/experiments/)
-  // small grids: fewer 128-row workgroups than a quarter of the CUs (or half, when each would walk >= 32 tiles):
-  // split the keys of every 32-row block over the waves of a workgroup instead (config 2: 15.9 -> 10.6 us)
-  const long long blocks128 = (long long)B * H * ((N + 127) / 128);
+// FA_VARIANT_AUTO of fa_fwd (what fa_resolve_variant_for returns) and of fa_fwd_exv (`ex`). The two rules differ: fa_fwd_exv takes the
+// 16x16x32 kernel on thresholds of its own and none of the other forms; making them one would change which kernel runs (a later change).
+// fa_fwd chooses between the matrix-core kernels (interleaved A/B on MI355X): the split-KV kernel wins on grids
+// far smaller than the chip, the 64-row two-split form and the eight-wave form of the 128-row kernel on grids of up to two / one
+// workgroup(s) per CU; everywhere else the 128-row kernel, its 16x16x32 form or (e4m3) the all-fp8 kernel is fastest.
+static int route_auto(int dtype, int D, int B, int H, int Nq, int Nk, int is_causal, bool ex) {
+  // small grids: fewer 128-row workgroups than a quarter of the CUs (or half, when each would walk >= 32 tiles), as in decode steps:
+  // split the keys of every 32-row block over the waves of a workgroup instead (config 2: 15.9 -> 10.6 us; 32 heads x 1 query x 16384
+  // keys: 165 -> 55 us, profiles/r03/decode_steps_splitkv_rule.log)
   // (head_dim 64 only: the head_dim-128 instantiation needs more than the 256 registers its eight-wave workgroup leaves a wave and
   // spills 820 B -- 8 heads x 1024: 73 us against 17-20 us for the kernels below, profiles/r03/ab_d128_small_grids.log; it stays
   // reachable by name)
-  if (D == 64 && fa::splitkv_supported(dtype, D) && N > 64 && blocks128 <= 64) return FA_VARIANT_MFMA_SPLITKV;
+  const long long blocks128 = (long long)B * H * ((Nq + 127) / 128);
+  if (D == 64 && fa::splitkv_supported(dtype, D) && Nk > 64 && blocks128 <= 64) return FA_VARIANT_MFMA_SPLITKV;
+  const int v = fa_resolve_variant(dtype, D);  // (fa_fwd_exv has refused the head dims without a matrix-core kernel)
+  if (v != FA_VARIANT_MFMA) return v;
+  if (ex)
+    return fa::mfma16_supported(dtype, D) && blocks128 > 512 && Nk >= (D == 64 ? (is_causal ? 1536 : 1024) : (is_causal ? 2048 : 1024))
+               ? FA_VARIANT_MFMA16
+               : FA_VARIANT_MFMA;
+  const int N = Nq;
+  // (round 2 sent long head_dim-128 sequences to the paired-block kernel; since the 128-row kernel stages its tiles by
+  // LDS-DMA it is 8-10 % ahead there too -- config 4 shard 1295 vs 1181 TFLOP/s, profiles/r03/ab_dma_late_and_d128_auto.log --
+  // and round 4 retired FA_VARIANT_MFMA_PP: the kernel is kept under tools/experiments/)
   // head_dim 64, 16-bit inputs, at most two 64-row workgroups per CU: 64-row blocks whose wave pairs take the even / odd
   // tiles -- twice the workgroups and half the sequential tiles (h=8, N=2048 causal: 20.0 (eight-wave form) -> 17.9 us;
   // 64 heads x 256: 6.6 -> 5.9 us; profiles/r03/ab_h64s2.log)
@@ -136,6 +204,9 @@ int fa_resolve_variant_for(int dtype, int D, int B, int H, int N, int is_causal)
   if (fa::fp8pv_supported(dtype, D)) return FA_VARIANT_MFMA_FP8PV;
   return FA_VARIANT_MFMA;
 }
+int fa_resolve_variant_for(int dtype, int D, int B, int H, int N, int is_causal) {
+  return route_auto(dtype, D, B, H, N, N, is_causal, false);
+}
 
 const char *fa_fwd_kernel_name(int dtype, int D, int B, int H, int N, int is_causal) {
   static thread_local char name[96];
@@ -171,34 +242,50 @@ double fa_algorithmic_bytes(int B, int H, int N, int D, int dtype) {
          4.0 * (double)B * H * N;
 }
 
+// the forward launch of fa_fwd and fa_fwd_exv (fa_fwd passes Hkv = H, Nk = N and its strides as the kv strides)
+static hipError_t launch_fwd(const void *q, const void *k, const void *v, void *o, float *lse, int B, int Hq, int Hkv, int Nq, int Nk,
+                             int D, float scale, long long q_batch_stride, long long q_head_stride, long long kv_batch_stride,
+                             long long kv_head_stride, int is_causal, int dtype, int variant, hipStream_t s) {
+  fa::Params p;
+  p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
+  p.B = B; p.H = Hq; p.N = Nq; p.D = D; p.scale = scale;
+  p.batch_stride = q_batch_stride; p.head_stride = q_head_stride;
+  p.is_causal = is_causal ? 1 : 0;
+  p.Nk = Nk; p.Hkv = Hkv; p.kv_batch_stride = kv_batch_stride; p.kv_head_stride = kv_head_stride;
+  p.exact = (variant == FA_VARIANT_MFMA_EXACT);
+  switch (variant) {
+    case FA_VARIANT_NAIVE: return fa::launch_naive(p, dtype, s);
+    case FA_VARIANT_TILED: return fa::launch_tiled(p, dtype, s);
+    case FA_VARIANT_TILED_V2: return fa::launch_tiled_v2(p, dtype, s);
+    case FA_VARIANT_MFMA_SPLITKV: return fa::launch_splitkv(p, dtype, s);
+    case FA_VARIANT_MFMA_SPLIT2: return fa::launch_mfma_split2(p, dtype, s);
+    case FA_VARIANT_MFMA_H64S2: return fa::launch_mfma_h64s2(p, dtype, s);
+    case FA_VARIANT_MFMA16: return fa::launch_mfma16(p, dtype, s);
+    case FA_VARIANT_MFMA_FP8PV: return fa::launch_fp8pv(p, dtype, s);
+    default: return fa::launch_mfma(p, dtype, s);  // FA_VARIANT_MFMA, FA_VARIANT_MFMA_EXACT
+  }
+}
+
 int fa_fwd(const void *q, const void *k, const void *v, void *o, float *lse, int B, int H, int N,
            int D, float scale, long long batch_stride, long long head_stride, int is_causal,
            int dtype, int variant, void *hip_stream) {
   g_err[0] = 0;
-  if (!q || !k || !v || !o) return fail(FA_ERR_INVALID_ARG, "fa_fwd: null tensor pointer");
-  if (B < 1 || H < 1 || N < 1 || D < 1)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd: B=%d H=%d N=%d D=%d must be >= 1", B, H, N, D);
-  if (!(scale > 0.0f)) return fail(FA_ERR_INVALID_ARG, "fa_fwd: scale=%g must be > 0", (double)scale);
+  const char *fn = "fa_fwd";
+  TRY(nonnull(fn, {q, k, v, o}));
+  TRY(positive(fn, {B, H, N, D}));
+  TRY(scale_ok(fn, scale));
   if (fa_dtype_in_bytes(dtype) == 0) return fail(FA_ERR_INVALID_ARG, "fa_fwd: bad dtype %d", dtype);
-  if (head_stride < (long long)N * D || batch_stride < 0 || (H > 1 && batch_stride < head_stride))
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd: strides (batch %lld, head %lld) smaller than a head (N*D=%lld)",
-                batch_stride, head_stride, (long long)N * D);
-  const int stride_mult = dtype == FA_DTYPE_FP8_E4M3 ? 16 : 8;  // keeps every head 16-byte aligned
-  if ((batch_stride % stride_mult) || (head_stride % stride_mult))
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd: strides must be multiples of %d elements", stride_mult);
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd: tensors must be 16-byte aligned");
+  TRY(strides_ok(fn, "", N, D, batch_stride, head_stride, stride_mult(dtype), H > 1));
+  TRY(aligned16(fn, "tensors", {q, k, v, o}));
   // 32-bit byte offsets inside a head; the staging loops may address up to two 64-key tiles past its end (range-checked
   // by the buffer descriptor, but the offset itself must not wrap)
-  if ((double)(N + 128) * D * fa_dtype_in_bytes(dtype) >= 4294967296.0)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd: one head exceeds 4 GiB");
+  TRY(head_fits(fn, (double)(N + 128) * D * fa_dtype_in_bytes(dtype), 4, ""));
   // head dims without a kernel of their own run on zero-padded rows whose padding is fetched from offset 2^31 + ... (fa_mfma16_kernel.hip, PAD)
-  if (!fa::mfma_supported(dtype, D) && fa::mfma16_supported(dtype, D) && (double)(N + 128) * D * 2 >= 2147483648.0)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd: one head exceeds 2 GiB (head dims on padded rows)");
-  if ((long long)B * H > 0x7fffffffLL / ((N + 127) / 128))
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd: grid too large");
+  if (!fa::mfma_supported(dtype, D) && fa::mfma16_supported(dtype, D))
+    TRY(head_fits(fn, (double)(N + 128) * D * 2, 2, " (head dims on padded rows)"));
+  TRY(grid_fits(fn, (long long)B * H, N));
   if (variant == FA_VARIANT_AUTO) {
-    variant = fa_resolve_variant_for(dtype, D, B, H, N, is_causal);
+    variant = route_auto(dtype, D, B, H, N, N, is_causal, false);
     if (variant < 0)
       return fail(FA_ERR_UNSUPPORTED, "fa_fwd: no kernel for dtype=%s D=%d", fa_dtype_name(dtype), D);
   }
@@ -208,33 +295,11 @@ int fa_fwd(const void *q, const void *k, const void *v, void *o, float *lse, int
   if ((variant == FA_VARIANT_NAIVE || variant == FA_VARIANT_TILED || variant == FA_VARIANT_TILED_V2) &&
       (H > 65535 || B > 65535))
     return fail(FA_ERR_INVALID_ARG, "fa_fwd: B,H must be <= 65535 for variant %s", fa_variant_name(variant));
-
-  fa::Params p;
-  p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
-  p.B = B; p.H = H; p.N = N; p.D = D;
-  p.scale = scale;
-  p.batch_stride = batch_stride; p.head_stride = head_stride;
-  p.is_causal = is_causal ? 1 : 0;
-  p.Nk = N; p.Hkv = H;
-  p.kv_batch_stride = batch_stride; p.kv_head_stride = head_stride;
-  p.exact = (variant == FA_VARIANT_MFMA_EXACT);
-  hipStream_t s = (hipStream_t)hip_stream;
-  hipError_t e;
-  switch (variant) {
-    case FA_VARIANT_NAIVE: e = fa::launch_naive(p, dtype, s); break;
-    case FA_VARIANT_TILED: e = fa::launch_tiled(p, dtype, s); break;
-    case FA_VARIANT_TILED_V2: e = fa::launch_tiled_v2(p, dtype, s); break;
-    case FA_VARIANT_MFMA_SPLITKV: e = fa::launch_splitkv(p, dtype, s); break;
-    case FA_VARIANT_MFMA_SPLIT2: e = fa::launch_mfma_split2(p, dtype, s); break;
-    case FA_VARIANT_MFMA_H64S2: e = fa::launch_mfma_h64s2(p, dtype, s); break;
-    case FA_VARIANT_MFMA16: e = fa::launch_mfma16(p, dtype, s); break;
-    case FA_VARIANT_MFMA_FP8PV: e = fa::launch_fp8pv(p, dtype, s); break;
-    default: e = fa::launch_mfma(p, dtype, s); break;
-  }
+  const hipError_t e = launch_fwd(q, k, v, o, lse, B, H, H, N, N, D, scale, batch_stride, head_stride, batch_stride, head_stride,
+                                  is_causal, dtype, variant, (hipStream_t)hip_stream);
   if (e == hipErrorNoDevice || e == hipErrorInvalidDevice)
     return fail(FA_ERR_NO_DEVICE, "fa_fwd: %s", hipGetErrorString(e));
-  if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "fa_fwd: launch failed: %s", hipGetErrorString(e));
-  return FA_OK;
+  return launched(fn, e);
 }
 
 int fa_fwd_ex(const void *q, const void *k, const void *v, void *o, float *lse, int B, int Hq, int Hkv, int Nq, int Nk,
@@ -248,52 +313,24 @@ int fa_fwd_exv(const void *q, const void *k, const void *v, void *o, float *lse,
                int D, float scale, long long q_batch_stride, long long q_head_stride, long long kv_batch_stride,
                long long kv_head_stride, int is_causal, int dtype, int variant, void *hip_stream) {
   g_err[0] = 0;
-  if (!q || !k || !v || !o) return fail(FA_ERR_INVALID_ARG, "fa_fwd_ex: null tensor pointer");
-  if (B < 1 || Hq < 1 || Hkv < 1 || Nq < 1 || Nk < 1 || D < 1)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_ex: sizes must be >= 1");
-  if (Hq % Hkv) return fail(FA_ERR_INVALID_ARG, "fa_fwd_ex: Hq=%d must be a multiple of Hkv=%d", Hq, Hkv);
-  if (is_causal && Nk < Nq)
-    return fail(FA_ERR_UNSUPPORTED, "fa_fwd_ex: causal needs Nk >= Nq (bottom-right alignment would leave empty rows)");
-  if (!(scale > 0.0f)) return fail(FA_ERR_INVALID_ARG, "fa_fwd_ex: scale=%g must be > 0", (double)scale);
+  const char *fn = "fa_fwd_ex";
+  TRY(nonnull(fn, {q, k, v, o}));
+  TRY(positive(fn, {B, Hq, Hkv, Nq, Nk, D}));
+  TRY(grouped(fn, Hq, Hkv));
+  TRY(causal_fits(fn, is_causal, Nq, Nk));
+  TRY(scale_ok(fn, scale));
   const bool padded_dim = !fa::mfma_supported(dtype, D) && fa::mfma16_supported(dtype, D);  // (zero-padded rows of the 16x16x32 kernel)
   if (!fa::mfma_supported(dtype, D) && !padded_dim)
     return fail(FA_ERR_UNSUPPORTED, "fa_fwd_ex: needs a matrix-core kernel (f16/bf16: D a multiple of 8 up to 128, or 256; fp8: D=64|128|256), got dtype=%s D=%d",
                 fa_dtype_name(dtype), D);
-  if (padded_dim && (double)(std::max(Nq, Nk) + 128) * D * 2 >= 2147483648.0)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_ex: one head exceeds 2 GiB (head dims on padded rows)");
-  const int sm = dtype == FA_DTYPE_FP8_E4M3 ? 16 : 8;
-  if (q_head_stride < (long long)Nq * D || kv_head_stride < (long long)Nk * D || (q_batch_stride % sm) || (q_head_stride % sm) ||
-      (kv_batch_stride % sm) || (kv_head_stride % sm) || (Hq > 1 && B > 1 && q_batch_stride < q_head_stride) ||
-      (Hkv > 1 && B > 1 && kv_batch_stride < kv_head_stride))
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_ex: bad strides");
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_ex: tensors must be 16-byte aligned");
+  if (padded_dim) TRY(head_fits(fn, (double)(std::max(Nq, Nk) + 128) * D * 2, 2, " (head dims on padded rows)"));
+  TRY(strides_ok(fn, "", Nq, D, q_batch_stride, q_head_stride, stride_mult(dtype), Hq > 1 && B > 1));
+  TRY(strides_ok(fn, "key/value ", Nk, D, kv_batch_stride, kv_head_stride, stride_mult(dtype), Hkv > 1 && B > 1));
+  TRY(aligned16(fn, "tensors", {q, k, v, o}));
   // (as in fa_fwd: the staging loops may address up to two 64-key tiles past the end of a head)
-  if ((double)(std::max(Nq, Nk) + 128) * D * fa_dtype_in_bytes(dtype) >= 4294967296.0)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_ex: one head exceeds 4 GiB");
-  if (q_batch_stride < 0 || kv_batch_stride < 0) return fail(FA_ERR_INVALID_ARG, "fa_fwd_ex: negative batch stride");
-  if ((long long)B * Hq > 0x7fffffffLL / ((Nq + 127) / 128)) return fail(FA_ERR_INVALID_ARG, "fa_fwd_ex: grid too large");
-  fa::Params p;
-  p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
-  p.B = B; p.H = Hq; p.N = Nq; p.D = D; p.scale = scale;
-  p.batch_stride = q_batch_stride; p.head_stride = q_head_stride;
-  p.is_causal = is_causal ? 1 : 0;
-  p.Nk = Nk; p.Hkv = Hkv; p.kv_batch_stride = kv_batch_stride; p.kv_head_stride = kv_head_stride;
-  // few query blocks against many keys (decode steps, short prompts): the AUTO rule of fa_fwd for small grids -- the keys of every
-  // 32-row block are split over the waves of a workgroup (the split-KV kernel takes the same Params: Nk, key/value heads).
-  // head_dim 64 only: there it is 1.2-3x faster than the 128-row kernel at every key length (32 heads x 1 query x 16384 keys:
-  // 165 -> 55 us), at head_dim 128 its four private 32-KiB tiles make it 2-4x SLOWER (profiles/r03/decode_steps_splitkv_rule.log)
-  const long long blocks128 = (long long)B * Hq * ((Nq + 127) / 128);
-  if (variant == FA_VARIANT_AUTO) {
-    const bool small_grid = D == 64 && fa::splitkv_supported(dtype, D) && Nk > 64 && blocks128 <= 64;
-    // the 16x16x32 kernel where fa_fwd's AUTO takes it: head_dim 64, 16-bit inputs, long key sequences on a grid that fills the chip
-    variant = small_grid ? FA_VARIANT_MFMA_SPLITKV
-              : padded_dim ? FA_VARIANT_MFMA16
-              : (fa::mfma16_supported(dtype, D) && blocks128 > 512 &&
-                 Nk >= (D == 64 ? (is_causal ? 1536 : 1024) : (is_causal ? 2048 : 1024)))  // (fa_fwd's thresholds, fa_resolve_variant_for)
-                    ? FA_VARIANT_MFMA16
-                    : FA_VARIANT_MFMA;
-  }
+  TRY(head_fits(fn, (double)(std::max(Nq, Nk) + 128) * D * fa_dtype_in_bytes(dtype), 4, ""));
+  TRY(grid_fits(fn, (long long)B * Hq, Nq));
+  if (variant == FA_VARIANT_AUTO) variant = route_auto(dtype, D, B, Hq, Nq, Nk, is_causal, true);
   // the kernels that take the generalised problem (key/value heads, Nk): the 128-row kernel with / without its pre-scaled operand, its
   // 16x16x32 form, the split-KV kernel
   if (variant != FA_VARIANT_MFMA && variant != FA_VARIANT_MFMA_EXACT && variant != FA_VARIANT_MFMA16 && variant != FA_VARIANT_MFMA_SPLITKV)
@@ -301,13 +338,8 @@ int fa_fwd_exv(const void *q, const void *k, const void *v, void *o, float *lse,
                 fa_variant_name(variant));
   if (!fa_supported(dtype, variant, D))
     return fail(FA_ERR_UNSUPPORTED, "fa_fwd_ex: variant=%s does not support dtype=%s D=%d", fa_variant_name(variant), fa_dtype_name(dtype), D);
-  p.exact = (variant == FA_VARIANT_MFMA_EXACT);
-  hipStream_t s = (hipStream_t)hip_stream;
-  const hipError_t e = variant == FA_VARIANT_MFMA_SPLITKV ? fa::launch_splitkv(p, dtype, s)
-                       : variant == FA_VARIANT_MFMA16     ? fa::launch_mfma16(p, dtype, s)
-                                                          : fa::launch_mfma(p, dtype, s);
-  if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "fa_fwd_ex: launch failed: %s", hipGetErrorString(e));
-  return FA_OK;
+  return launched(fn, launch_fwd(q, k, v, o, lse, B, Hq, Hkv, Nq, Nk, D, scale, q_batch_stride, q_head_stride, kv_batch_stride,
+                                 kv_head_stride, is_causal, dtype, variant, (hipStream_t)hip_stream));
 }
 
 int fa_fwd_decode_supported(int dtype, int D, int Hq, int Hkv, int Nq) {
@@ -317,9 +349,42 @@ long long fa_fwd_decode_workspace_bytes(int B, int Hq, int Hkv, int Nq, int Nk, 
   if (B < 1 || Hq < 1 || Hkv < 1 || Nq < 1 || Nk < 1 || (D != 64 && D != 128) || Hq % Hkv) return 0;
   return fa::decode_workspace_bytes(B, Hq, Hkv, Nq, Nk, D);
 }
+// the decode grid guard and the DecodeParams of the dense and the paged decode alike: everything but how the cache is addressed
+// (kv_bs, kv_hs and the page tables, the caller's)
+static int decode_params(const char *fn, fa::DecodeParams &p, const void *q, const void *k, const void *v, void *o, float *lse,
+                         void *workspace, int B, int Hq, int Hkv, int Nq, int Nk, int D, float scale, long long q_batch_stride,
+                         long long q_head_stride, int is_causal, int kv8) {
+  if ((long long)B * Hq * Nq > 0x7fffffffLL || (long long)B * Hkv * 256 > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse; p.ws = (float *)workspace;
+  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Nq = Nq; p.Nk = Nk; p.scale = scale;
+  p.q_bs = q_batch_stride; p.q_hs = q_head_stride;
+  p.is_causal = is_causal ? 1 : 0;
+  p.S = fa::decode_splits(B, Hkv, Nk, D, kv8);
+  return FA_OK;
+}
 static int decode_impl(const void *q, const void *k, const void *v, void *o, float *lse, int B, int Hq, int Hkv, int Nq, int Nk, int D,
                        float scale, long long q_batch_stride, long long q_head_stride, long long kv_batch_stride, long long kv_head_stride,
-                       int is_causal, int dtype, int kv8, void *workspace, long long workspace_bytes, void *hip_stream);
+                       int is_causal, int dtype, int kv8, void *workspace, long long workspace_bytes, void *hip_stream) {
+  g_err[0] = 0;
+  const char *fn = "fa_fwd_decode";
+  TRY(nonnull(fn, {q, k, v, o, workspace}));
+  TRY(positive(fn, {B, Hq, Hkv, Nq, Nk, D}));
+  TRY(grouped(fn, Hq, Hkv));
+  TRY(causal_fits(fn, is_causal, Nq, Nk));
+  TRY(scale_ok(fn, scale));
+  if (!fa_fwd_decode_supported(dtype, D, Hq, Hkv, Nq))
+    return fail(FA_ERR_UNSUPPORTED, "fa_fwd_decode: needs f16 / bf16 / fp8_e4m3, D = 64 | 128 and (Hq / Hkv) * Nq <= 32 packed query rows; got dtype=%s D=%d "
+                "Hq=%d Hkv=%d Nq=%d (use fa_fwd_ex)", fa_dtype_name(dtype), D, Hq, Hkv, Nq);
+  TRY(strides_ok(fn, "", Nq, D, q_batch_stride, q_head_stride, stride_mult(dtype), Hq > 1 && B > 1));
+  TRY(strides_ok(fn, "key/value ", Nk, D, kv_batch_stride, kv_head_stride, kv8 ? 16 : stride_mult(dtype), Hkv > 1 && B > 1));
+  TRY(aligned16(fn, "tensors and workspace", {q, k, v, o, workspace}));
+  TRY(head_fits(fn, (double)(Nk + 128) * D * 2, 4, ""));
+  TRY(workspace_fits(fn, workspace_bytes, fa::decode_workspace_bytes(B, Hq, Hkv, Nq, Nk, D), "fa_fwd_decode_workspace_bytes"));
+  fa::DecodeParams p;
+  TRY(decode_params(fn, p, q, k, v, o, lse, workspace, B, Hq, Hkv, Nq, Nk, D, scale, q_batch_stride, q_head_stride, is_causal, kv8));
+  p.kv_bs = kv_batch_stride; p.kv_hs = kv_head_stride;
+  return launched(fn, fa::launch_decode(p, D, dtype, kv8, (hipStream_t)hip_stream));
+}
 int fa_fwd_decode(const void *q, const void *k, const void *v, void *o, float *lse, int B, int Hq, int Hkv, int Nq, int Nk, int D,
                   float scale, long long q_batch_stride, long long q_head_stride, long long kv_batch_stride, long long kv_head_stride,
                   int is_causal, int dtype, void *workspace, long long workspace_bytes, void *hip_stream) {
@@ -334,41 +399,6 @@ int fa_fwd_decode_kv8(const void *q, const void *k, const void *v, void *o, floa
     return fail(FA_ERR_UNSUPPORTED, "fa_fwd_decode_kv8: queries must be bf16 (or e4m3: then this is fa_fwd_decode), got %s", fa_dtype_name(q_dtype));
   return decode_impl(q, k, v, o, lse, B, Hq, Hkv, Nq, Nk, D, scale, q_batch_stride, q_head_stride, kv_batch_stride, kv_head_stride, is_causal,
                      q_dtype, 1, workspace, workspace_bytes, hip_stream);
-}
-static int decode_impl(const void *q, const void *k, const void *v, void *o, float *lse, int B, int Hq, int Hkv, int Nq, int Nk, int D,
-                       float scale, long long q_batch_stride, long long q_head_stride, long long kv_batch_stride, long long kv_head_stride,
-                       int is_causal, int dtype, int kv8, void *workspace, long long workspace_bytes, void *hip_stream) {
-  g_err[0] = 0;
-  if (!q || !k || !v || !o || !workspace) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode: null pointer");
-  if (B < 1 || Hq < 1 || Hkv < 1 || Nq < 1 || Nk < 1 || D < 1) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode: sizes must be >= 1");
-  if (Hq % Hkv) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode: Hq=%d must be a multiple of Hkv=%d", Hq, Hkv);
-  if (is_causal && Nk < Nq)
-    return fail(FA_ERR_UNSUPPORTED, "fa_fwd_decode: causal needs Nk >= Nq (bottom-right alignment would leave empty rows)");
-  if (!(scale > 0.0f)) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode: scale=%g must be > 0", (double)scale);
-  if (!fa_fwd_decode_supported(dtype, D, Hq, Hkv, Nq))
-    return fail(FA_ERR_UNSUPPORTED, "fa_fwd_decode: needs f16 / bf16 / fp8_e4m3, D = 64 | 128 and (Hq / Hkv) * Nq <= 32 packed query rows; got dtype=%s D=%d "
-                "Hq=%d Hkv=%d Nq=%d (use fa_fwd_ex)", fa_dtype_name(dtype), D, Hq, Hkv, Nq);
-  const int dsm = dtype == FA_DTYPE_FP8_E4M3 ? 16 : 8, ksm = kv8 ? 16 : dsm;  // keeps every head 16-byte aligned
-  if (q_head_stride < (long long)Nq * D || kv_head_stride < (long long)Nk * D || (q_batch_stride % dsm) || (q_head_stride % dsm) ||
-      (kv_batch_stride % ksm) || (kv_head_stride % ksm) || q_batch_stride < 0 || kv_batch_stride < 0 ||
-      (Hq > 1 && B > 1 && q_batch_stride < q_head_stride) || (Hkv > 1 && B > 1 && kv_batch_stride < kv_head_stride))
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode: bad strides");
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)workspace) & 15)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode: tensors and workspace must be 16-byte aligned");
-  if ((double)(Nk + 128) * D * 2 >= 4294967296.0) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode: one head exceeds 4 GiB");
-  const long long need = fa::decode_workspace_bytes(B, Hq, Hkv, Nq, Nk, D);
-  if (workspace_bytes < need)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode: workspace of %lld bytes, fa_fwd_decode_workspace_bytes() asks for %lld", workspace_bytes, need);
-  if ((long long)B * Hq * Nq > 0x7fffffffLL || (long long)B * Hkv * 256 > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode: grid too large");
-  fa::DecodeParams p;
-  p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse; p.ws = (float *)workspace;
-  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Nq = Nq; p.Nk = Nk; p.scale = scale;
-  p.q_bs = q_batch_stride; p.q_hs = q_head_stride; p.kv_bs = kv_batch_stride; p.kv_hs = kv_head_stride;
-  p.is_causal = is_causal ? 1 : 0;
-  p.S = fa::decode_splits(B, Hkv, Nk, D, kv8);
-  const hipError_t e = fa::launch_decode(p, D, dtype, kv8, (hipStream_t)hip_stream);
-  if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "fa_fwd_decode: launch failed: %s", hipGetErrorString(e));
-  return FA_OK;
 }
 
 int fa_fwd_decode_paged_supported(int q_dtype, int kv_dtype, int D, int Hq, int Hkv, int Nq, int page_size) {
@@ -387,48 +417,40 @@ int fa_fwd_decode_paged(const void *q, const void *k_pages, const void *v_pages,
                         long long kv_row_stride, long long block_table_stride, int is_causal, int q_dtype, int kv_dtype, void *workspace,
                         long long workspace_bytes, void *hip_stream) {
   g_err[0] = 0;
-  if (!q || !k_pages || !v_pages || !o || !block_table || !seqlens_k || !workspace) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: null pointer");
-  if (B < 1 || Hq < 1 || Hkv < 1 || Nq < 1 || D < 1 || page_size < 1 || num_pages < 1 || max_pages_per_seq < 1)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: sizes must be >= 1");
-  if (Hq % Hkv) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: Hq=%d must be a multiple of Hkv=%d", Hq, Hkv);
-  if (!(scale > 0.0f)) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: scale=%g must be > 0", (double)scale);
+  const char *fn = "fa_fwd_decode_paged";
+  TRY(nonnull(fn, {q, k_pages, v_pages, o, block_table, seqlens_k, workspace}));
+  TRY(positive(fn, {B, Hq, Hkv, Nq, D, page_size, num_pages, max_pages_per_seq}));
+  TRY(grouped(fn, Hq, Hkv));
+  TRY(scale_ok(fn, scale));
   if (!fa_fwd_decode_paged_supported(q_dtype, kv_dtype, D, Hq, Hkv, Nq, page_size))
     return fail(FA_ERR_UNSUPPORTED, "fa_fwd_decode_paged: needs (q, kv) dtypes f16/f16, bf16/bf16, e4m3/e4m3 or bf16/e4m3, D = 64 | 128, (Hq / Hkv) * Nq "
                 "<= 32 packed query rows and a page size of 16, 32, 64, 128 or 256; got q=%s kv=%s D=%d Hq=%d Hkv=%d Nq=%d page_size=%d",
                 fa_dtype_name(q_dtype), fa_dtype_name(kv_dtype), D, Hq, Hkv, Nq, page_size);
   if (block_table_stride < max_pages_per_seq)
     return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: block_table_stride=%lld < max_pages_per_seq=%d", block_table_stride, max_pages_per_seq);
-  const int kv8 = kv_dtype == FA_DTYPE_FP8_E4M3, eb = kv8 ? 1 : 2;
-  const int dsm = q_dtype == FA_DTYPE_FP8_E4M3 ? 16 : 8, ksm = kv8 ? 16 : 8;  // keeps every row 16-byte aligned
-  if (q_head_stride < (long long)Nq * D || (q_batch_stride % dsm) || (q_head_stride % dsm) || q_batch_stride < 0 ||
-      (Hq > 1 && B > 1 && q_batch_stride < q_head_stride) || kv_row_stride < D || kv_head_stride < D || kv_page_stride < D ||
-      (kv_page_stride % ksm) || (kv_head_stride % ksm) || (kv_row_stride % ksm) || block_table_stride > 0x7fffffffLL)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: bad strides");
+  TRY(strides_ok(fn, "", Nq, D, q_batch_stride, q_head_stride, stride_mult(q_dtype), Hq > 1 && B > 1));
+  const int kv8 = kv_dtype == FA_DTYPE_FP8_E4M3, ksm = stride_mult(kv_dtype);  // keeps every row 16-byte aligned
+  if (kv_row_stride < D || kv_head_stride < D || kv_page_stride < D || (kv_page_stride % ksm) || (kv_head_stride % ksm) ||
+      (kv_row_stride % ksm) || block_table_stride > 0x7fffffffLL)
+    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: bad page strides");
   // a page's rows of one head are addressed by 32-bit offsets from the page's own 64-bit base
-  if ((double)page_size * kv_row_stride * eb >= 2147483648.0) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: one page of one head exceeds 2 GiB");
-  if (((uintptr_t)q | (uintptr_t)k_pages | (uintptr_t)v_pages | (uintptr_t)o | (uintptr_t)workspace) & 15)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: tensors and workspace must be 16-byte aligned");
+  if ((double)page_size * kv_row_stride * (kv8 ? 1 : 2) >= 2147483648.0)
+    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: one page of one head exceeds 2 GiB");
+  TRY(aligned16(fn, "tensors and workspace", {q, k_pages, v_pages, o, workspace}));
   if (((uintptr_t)block_table | (uintptr_t)seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: block_table / seqlens_k must be int32-aligned");
   if ((long long)page_size * max_pages_per_seq > (1 << 30)) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: capacity above 2^30 keys");
   const int cap = page_size * max_pages_per_seq;
-  const long long need = fa::decode_workspace_bytes(B, Hq, Hkv, Nq, cap, D);
-  if (workspace_bytes < need)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: workspace of %lld bytes, fa_fwd_decode_paged_workspace_bytes() asks for %lld", workspace_bytes, need);
-  if ((long long)B * Hq * Nq > 0x7fffffffLL || (long long)B * Hkv * 256 > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: grid too large");
+  TRY(workspace_fits(fn, workspace_bytes, fa::decode_workspace_bytes(B, Hq, Hkv, Nq, cap, D), "fa_fwd_decode_paged_workspace_bytes"));
   fa::DecodePagedParams p;
-  p.q = q; p.k = k_pages; p.v = v_pages; p.o = o; p.lse = lse; p.ws = (float *)workspace;
-  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Nq = Nq; p.Nk = cap; p.scale = scale;
-  p.q_bs = q_batch_stride; p.q_hs = q_head_stride; p.kv_bs = 0; p.kv_hs = kv_head_stride;
-  p.is_causal = is_causal ? 1 : 0;
-  p.S = fa::decode_splits(B, Hkv, cap, D, kv8);  // the dense decode's split rule at the capacity: bit-identical to it on full caches
+  // Nk = the capacity, hence the dense decode's split rule there: bit-identical to it on full caches
+  TRY(decode_params(fn, p, q, k_pages, v_pages, o, lse, workspace, B, Hq, Hkv, Nq, cap, D, scale, q_batch_stride, q_head_stride, is_causal, kv8));
+  p.kv_bs = 0; p.kv_hs = kv_head_stride;
   p.block_table = block_table; p.seqlens = seqlens_k;
   p.page_stride = kv_page_stride; p.row_stride = kv_row_stride;
   p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
   p.lp = 0;
   while ((1 << p.lp) < page_size) ++p.lp;
-  const hipError_t e = fa::launch_decode_paged(p, D, q_dtype, kv8, (hipStream_t)hip_stream);
-  if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "fa_fwd_decode_paged: launch failed: %s", hipGetErrorString(e));
-  return FA_OK;
+  return launched(fn, fa::launch_decode_paged(p, D, q_dtype, kv8, (hipStream_t)hip_stream));
 }
 
 long long fa_bwd_workspace_bytes(int B, int H, int N) { return (long long)B * H * N * 4; }
@@ -455,31 +477,24 @@ static int bwd_impl(const char *fn, const void *q, const void *k, const void *v,
                     float *dq, float *dk, float *dv, void *workspace, int B, int H, int Hkv, int N, int Nk, int D, float scale,
                     long long bs, long long hs, long long kbs, long long khs, int is_causal, int dtype, void *hip_stream) {
   g_err[0] = 0;
-  if (!q || !k || !v || !o || !d_o || !lse || !dq || !dk || !dv || !workspace)
-    return fail(FA_ERR_INVALID_ARG, "%s: null pointer", fn);
-  if (B < 1 || H < 1 || N < 1 || Nk < 1 || D < 1)
-    return fail(FA_ERR_INVALID_ARG, "%s: B=%d H=%d Nq=%d Nk=%d D=%d must be >= 1", fn, B, H, N, Nk, D);
-  if (is_causal && Nk < N)
-    return fail(FA_ERR_UNSUPPORTED, "%s: causal needs Nk >= Nq (bottom-right alignment would leave empty rows)", fn);
-  if (Hkv < 1 || H % Hkv) return fail(FA_ERR_INVALID_ARG, "%s: Hkv=%d must divide Hq=%d", fn, Hkv, H);
-  if (!(scale > 0.0f)) return fail(FA_ERR_INVALID_ARG, "%s: scale=%g must be > 0", fn, (double)scale);
-  const int smul = dtype == FA_DTYPE_FP8_E4M3 ? 16 : 8;  // keeps every head 16-byte aligned
-  if (hs < (long long)N * D || (H > 1 && bs < hs) || (bs % smul) || (hs % smul))
-    return fail(FA_ERR_INVALID_ARG, "%s: bad strides (batch %lld, head %lld)", fn, bs, hs);
-  if (khs < (long long)Nk * D || (Hkv > 1 && kbs < khs) || (kbs % smul) || (khs % smul))
-    return fail(FA_ERR_INVALID_ARG, "%s: bad key/value strides (batch %lld, head %lld)", fn, kbs, khs);
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 15)
-    return fail(FA_ERR_INVALID_ARG, "%s: tensors must be 16-byte aligned", fn);
+  TRY(nonnull(fn, {q, k, v, o, d_o, lse, dq, dk, dv, workspace}));
+  TRY(positive(fn, {B, H, N, Nk, D}));
+  TRY(causal_fits(fn, is_causal, N, Nk));
+  TRY(grouped(fn, H, Hkv));
+  TRY(scale_ok(fn, scale));
+  TRY(strides_ok(fn, "", N, D, bs, hs, stride_mult(dtype), H > 1));
+  TRY(strides_ok(fn, "key/value ", Nk, D, kbs, khs, stride_mult(dtype), Hkv > 1));
+  TRY(aligned16(fn, "tensors", {q, k, v, o, d_o, dq, dk, dv}));
   if (!fa::bwd_supported(dtype, D))
     return fail(FA_ERR_UNSUPPORTED, "%s: no kernel for dtype=%s D=%d (f16 / bf16 / fp8_e4m3, D a multiple of 8 up to 128)", fn, fa_dtype_name(dtype), D);
-  if ((double)(N > Nk ? N : Nk) * D * 2 >= 4294967296.0) return fail(FA_ERR_INVALID_ARG, "%s: one head exceeds 4 GiB", fn);
+  const int rows = std::max(N, Nk);
+  TRY(head_fits(fn, (double)rows * D * 2, 4, ""));
   // head dims other than 64 / 128 run on zero-padded rows whose padding is fetched from offset 2^31 + ... (fa_bwd_kernels.hip, PAD)
-  if (D != 64 && D != 128 && D != 256 && (double)((N > Nk ? N : Nk) + 128) * D * 2 >= 2147483648.0)  // (+128: rows past the end are addressed too)
-    return fail(FA_ERR_INVALID_ARG, "%s: one head exceeds 2 GiB (head dims other than 64 / 128)", fn);
-  if (bs < 0 || kbs < 0) return fail(FA_ERR_INVALID_ARG, "%s: negative batch stride", fn);
-  if ((long long)B * H > 0x7fffffffLL / (((N > Nk ? N : Nk) + 127) / 128)) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
-  if (dtype == FA_DTYPE_FP8_E4M3 && ((uintptr_t)workspace & 15)) return fail(FA_ERR_INVALID_ARG, "%s: workspace must be 16-byte aligned", fn);
+  if (D != 64 && D != 128 && D != 256)  // (+128: rows past the end are addressed too)
+    TRY(head_fits(fn, (double)(rows + 128) * D * 2, 2, " (head dims other than 64 / 128)"));
+  TRY(grid_fits(fn, (long long)B * H, rows));
   if (dtype == FA_DTYPE_FP8_E4M3) {
+    TRY(aligned16(fn, "workspace", {workspace}));
     // e4m3 Q, K, V (O and dO are bf16, as fa_fwd writes O for this dtype): widen them into the workspace behind delta
     // (layout of fa_bwd_workspace_bytes_ex) and run the bf16 kernels on the copies
     char *w = (char *)workspace + align256((long long)B * H * N * 4);
@@ -488,14 +503,12 @@ static int bwd_impl(const char *fn, const void *q, const void *k, const void *v,
     hipError_t ec = fa::launch_widen_e4m3(q, q16, eq, (hipStream_t)hip_stream);
     if (ec == hipSuccess) ec = fa::launch_widen_e4m3(k, k16, ek, (hipStream_t)hip_stream);
     if (ec == hipSuccess) ec = fa::launch_widen_e4m3(v, v16, ek, (hipStream_t)hip_stream);
-    if (ec != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: launch failed: %s", fn, hipGetErrorString(ec));
+    TRY(launched(fn, ec));
     q = q16; k = k16; v = v16;
     dtype = FA_DTYPE_BF16;
   }
-  hipError_t e = fa::launch_bwd(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, B, H, Hkv, N, Nk, D, scale, bs, hs, kbs, khs,
-                                is_causal ? 1 : 0, dtype, (hipStream_t)hip_stream);
-  if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: launch failed: %s", fn, hipGetErrorString(e));
-  return FA_OK;
+  return launched(fn, fa::launch_bwd(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, B, H, Hkv, N, Nk, D, scale, bs, hs, kbs, khs,
+                                     is_causal ? 1 : 0, dtype, (hipStream_t)hip_stream));
 }
 
 int fa_bwd(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq,

@@ -19,14 +19,15 @@ from ._lib import load_library
 DTYPES = {"f32": 0, "f16": 1, "bf16": 2, "fp8_e4m3": 3}
 VARIANTS = {"auto": 0, "naive": 1, "tiled": 2, "tiled_v2": 3, "mfma": 4, "mfma_pp": 5, "mfma_splitkv": 6, "mfma_split2": 7, "mfma_exact": 8, "mfma_h64s2": 9, "mfma16": 10, "mfma_fp8pv": 11}
 
+_FP8 = getattr(torch, "float8_e4m3fn", None)  # (None on torch builds without it)
 _TORCH2FA = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-if hasattr(torch, "float8_e4m3fn"):
-    _TORCH2FA[torch.float8_e4m3fn] = 3
+if _FP8 is not None:
+    _TORCH2FA[_FP8] = 3
 
 
 class FaError(RuntimeError):
-    def __init__(self, status: int, msg: str):
-        super().__init__(f"fa_fwd failed ({status}): {msg}")
+    def __init__(self, status: int, msg: str, entry: str = "fa_fwd"):
+        super().__init__(f"{entry} failed ({status}): {msg}")
         self.status = status
 
 
@@ -58,48 +59,95 @@ def _strides(t: torch.Tensor) -> Tuple[int, int]:
     return bs, hs
 
 
-def _prepare_forward(q, k, v, is_causal, scale, variant, return_lse, out, lse):
-    """Validate one (Q,K,V,O,LSE) call and return (argument tuple of fa_fwd without the stream, out, lse)."""
-    if q.dim() != 4 or q.shape != k.shape or q.shape != v.shape:
-        raise ValueError(f"q, k, v must share one [B,H,N,D] shape, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
-    if not (q.is_cuda and k.is_cuda and v.is_cuda):
-        raise RuntimeError("flash_attention_forward needs device tensors: there is no CPU path "
+def _kv_strides(k: torch.Tensor, v: torch.Tensor) -> Tuple[int, int]:
+    ks = _strides(k)
+    if _strides(v) != ks:
+        raise ValueError("k and v must share batch/head strides")
+    return ks
+
+
+def _on_device(entry: str, *tensors: torch.Tensor) -> None:
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError(f"{entry} needs device tensors: there is no CPU path "
                            "(the CPU oracle lives in oracle/ and is test infrastructure only)")
-    if q.dtype not in _TORCH2FA or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k.dtype} {v.dtype}")
-    B, H, N, D = q.shape
-    bs, hs = _strides(q)
-    if _strides(k) != (bs, hs) or _strides(v) != (bs, hs):
-        raise ValueError("q, k, v must share batch/head strides (one stride pair in the binding table)")
-    fa_dtype = _TORCH2FA[q.dtype]
-    out_dtype = torch.bfloat16 if fa_dtype == 3 else q.dtype
+
+
+def _out_dtype(dtype: torch.dtype) -> torch.dtype:
+    return torch.bfloat16 if dtype == _FP8 else dtype  # e4m3 inputs: bf16 output
+
+
+def _out(out: Optional[torch.Tensor], q: torch.Tensor, q_strides: Tuple[int, int]) -> torch.Tensor:
+    """O, allocated or checked: the kernels write it with q's shape and strides, anything else lands in the wrong place or out of bounds."""
     if out is None:
-        out = torch.empty_strided((B, H, N, D), q.stride(), dtype=out_dtype, device=q.device)
-    elif (not out.is_cuda or out.device != q.device or out.dtype != out_dtype or out.shape != q.shape
-          or _strides(out) != (bs, hs)):
+        return torch.empty_strided(q.shape, q.stride(), dtype=_out_dtype(q.dtype), device=q.device)
+    if (not out.is_cuda or out.device != q.device or out.dtype != _out_dtype(q.dtype) or out.shape != q.shape
+            or _strides(out) != q_strides):
         raise ValueError("out must be a device tensor with q's shape/strides (bf16 for fp8 inputs)")
-    if return_lse and lse is None:
-        lse = torch.empty((B, H, N), dtype=torch.float32, device=q.device)
-    if lse is not None and (not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32
-                            or not lse.is_contiguous() or lse.numel() != B * H * N):
+    return out
+
+
+def _lse(lse: Optional[torch.Tensor], return_lse: bool, q: torch.Tensor) -> Optional[torch.Tensor]:
+    B, H, N, _ = q.shape
+    if lse is None:
+        return torch.empty((B, H, N), dtype=torch.float32, device=q.device) if return_lse else None
+    if not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * H * N:
         raise ValueError("lse must be contiguous fp32 [B,H,N] on q's device")
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
-    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr() if lse is not None else None,
-            B, H, N, D, float(scale), bs, hs, int(bool(is_causal)), fa_dtype, VARIANTS[variant])
-    return args, out, lse
+    return lse
 
 
-def _launch_forward(lib, args, device, stream):
+def _workspace(workspace: Optional[torch.Tensor], need: int, device: torch.device) -> torch.Tensor:
+    if workspace is None:
+        return torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    if not workspace.is_cuda or workspace.device != device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous uint8 device tensor")
+    return workspace
+
+
+def _scale(scale: Optional[float], D: int) -> float:
+    return 1.0 / math.sqrt(D) if scale is None else float(scale)
+
+
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return t.data_ptr() if t is not None else None
+
+
+def _call(lib, entry: str, args: tuple, device: torch.device, stream: Optional[int]) -> None:
+    """Call the C entry point `entry` with `args` and the stream (default: the current torch stream of `device`); a refusal raises FaError."""
     if stream is None:
         stream = torch.cuda.current_stream(device).cuda_stream
+    fn = getattr(lib, entry)
     if device.index == torch.cuda.current_device():  # the common case: no device switch (it costs microseconds,
-        st = lib.fa_fwd(*args, stream)                # as much as a short-sequence kernel runs)
+        st = fn(*args, stream)                       # as much as a short-sequence kernel runs)
     else:
         with torch.cuda.device(device):
-            st = lib.fa_fwd(*args, stream)
+            st = fn(*args, stream)
     if st != 0:
-        raise FaError(st, lib.fa_last_error().decode())
+        raise FaError(st, lib.fa_last_error().decode(), entry)
+
+
+def _prepare_forward(q, k, v, is_causal, scale, variant, return_lse, out, lse):
+    """Validate one forward call and return (entry point, its arguments without the stream, out, lse). q [B,Hq,Nq,D], k / v
+    [B,Hkv,Nk,D]: equal shapes go to fa_fwd, grouped heads / Nq != Nk to fa_fwd_exv (include/fa_mi355.h; Hq % Hkv == 0, causal
+    bottom-right aligned: key j visible to query i iff j <= i + Nk - Nq), whose `variant` is auto, mfma, mfma_exact, mfma16 or
+    mfma_splitkv -- the kernels that take that problem; any other raises FaError (unsupported), never a silent substitute."""
+    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape:
+        raise ValueError(f"q [B,Hq,Nq,D] and k, v one [B,Hkv,Nk,D] shape, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
+    B, Hq, Nq, D = q.shape
+    Bk, Hkv, Nk, Dk = k.shape
+    if Bk != B or Dk != D or Hq % Hkv:
+        raise ValueError(f"incompatible shapes q {tuple(q.shape)} k/v {tuple(k.shape)}")
+    _on_device("flash_attention_forward", q, k, v)
+    if q.dtype not in _TORCH2FA or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k.dtype} {v.dtype}")
+    qs, ks = _strides(q), _kv_strides(k, v)
+    out, lse = _out(out, q, qs), _lse(lse, return_lse, q)
+    ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse))
+    tail = (int(bool(is_causal)), _TORCH2FA[q.dtype], VARIANTS[variant])
+    if q.shape != k.shape:
+        return "fa_fwd_exv", ptrs + (B, Hq, Hkv, Nq, Nk, D, _scale(scale, D), *qs, *ks) + tail, out, lse
+    if ks != qs:
+        raise ValueError("q, k, v must share batch/head strides (one stride pair in the binding table)")
+    return "fa_fwd", ptrs + (B, Hq, Nq, D, _scale(scale, D), *qs) + tail, out, lse
 
 
 def flash_attention_forward(
@@ -114,12 +162,11 @@ def flash_attention_forward(
     lse: Optional[torch.Tensor] = None,
     stream: Optional[int] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """Launch the gfx950 kernel on the current torch stream (asynchronous)."""
+    """Launch the gfx950 kernel on the current torch stream (asynchronous). k / v may carry fewer heads than q and another
+    sequence length (fa_fwd_exv, see _prepare_forward)."""
     lib = load_library()
-    if q.dim() == 4 and k.dim() == 4 and k.shape == v.shape and q.shape != k.shape:
-        return _forward_ex(lib, q, k, v, is_causal, scale, variant, return_lse, out, lse, stream)  # GQA / Nq != Nk
-    args, out, lse = _prepare_forward(q, k, v, is_causal, scale, variant, return_lse, out, lse)
-    _launch_forward(lib, args, q.device, stream)
+    entry, args, out, lse = _prepare_forward(q, k, v, is_causal, scale, variant, return_lse, out, lse)
+    _call(lib, entry, args, q.device, stream)
     return out, lse
 
 
@@ -132,54 +179,15 @@ class ForwardPlan:
 
     def __init__(self, q, k, v, is_causal=False, scale=None, variant="auto", return_lse=True, out=None, lse=None):
         self._lib = load_library()
-        self._args, self.out, self.lse = _prepare_forward(q, k, v, is_causal, scale, variant, return_lse, out, lse)
+        if q.shape != k.shape or q.shape != v.shape:
+            raise ValueError(f"q, k, v must share one [B,H,N,D] shape, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
+        _, self._args, self.out, self.lse = _prepare_forward(q, k, v, is_causal, scale, variant, return_lse, out, lse)
         self._keep = (q, k, v)
         self._device = q.device
 
     def launch(self, stream: Optional[int] = None) -> None:
         """Issue the kernel on ``stream`` (default: the current torch stream of the tensors' device); asynchronous."""
-        _launch_forward(self._lib, self._args, self._device, stream)
-
-
-def _forward_ex(lib, q, k, v, is_causal, scale, variant, return_lse, out, lse, stream):
-    """Generalised call (include/fa_mi355.h fa_fwd_exv): q [B,Hq,Nq,D], k/v [B,Hkv,Nk,D], Hq % Hkv == 0,
-    causal bottom-right aligned (key j visible to query i iff j <= i + Nk - Nq). `variant`: auto, mfma, mfma_exact, mfma16 or
-    mfma_splitkv -- the kernels that take grouped heads / Nq != Nk; any other raises FaError (unsupported), never a silent substitute."""
-    B, Hq, Nq, D = q.shape
-    Bk, Hkv, Nk, Dk = k.shape
-    if Bk != B or Dk != D or Hq % Hkv:
-        raise ValueError(f"incompatible shapes q {tuple(q.shape)} k/v {tuple(k.shape)}")
-    if not (q.is_cuda and k.is_cuda and v.is_cuda):
-        raise RuntimeError("flash_attention_forward needs device tensors: there is no CPU path")
-    if q.dtype not in _TORCH2FA or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k.dtype} {v.dtype}")
-    qbs, qhs = _strides(q)
-    kbs, khs = _strides(k)
-    if _strides(v) != (kbs, khs):
-        raise ValueError("k and v must share batch/head strides")
-    fa_dtype = _TORCH2FA[q.dtype]
-    out_dtype = torch.bfloat16 if fa_dtype == 3 else q.dtype
-    if out is None:
-        out = torch.empty_strided((B, Hq, Nq, D), q.stride(), dtype=out_dtype, device=q.device)
-    elif (not out.is_cuda or out.device != q.device or out.dtype != out_dtype or out.shape != q.shape
-          or _strides(out) != (qbs, qhs)):
-        # the kernel writes O with q's strides: anything else lands in the wrong place or out of bounds
-        raise ValueError("out must be a device tensor with q's shape/strides (bf16 for fp8 inputs)")
-    if return_lse and lse is None:
-        lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device)
-    if lse is not None and (not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32
-                            or not lse.is_contiguous() or lse.numel() != B * Hq * Nq):
-        raise ValueError("lse must be contiguous fp32 [B,Hq,Nq] on q's device")
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
-    if stream is None:
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-    with torch.cuda.device(q.device):
-        st = lib.fa_fwd_exv(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr() if lse is not None else None,
-                            B, Hq, Hkv, Nq, Nk, D, float(scale), qbs, qhs, kbs, khs, int(bool(is_causal)), fa_dtype, VARIANTS[variant], stream)
-    if st != 0:
-        raise FaError(st, lib.fa_last_error().decode())
-    return out, lse
+        _call(self._lib, "fa_fwd", self._args, self._device, stream)
 
 
 def decode_workspace_bytes(B: int, Hq: int, Hkv: int, Nq: int, Nk: int, D: int) -> int:
@@ -209,41 +217,16 @@ def flash_attention_decode(
     Bk, Hkv, Nk, Dk = k.shape
     if Bk != B or Dk != D or Hq % Hkv:
         raise ValueError(f"incompatible shapes q {tuple(q.shape)} k/v {tuple(k.shape)}")
-    if not (q.is_cuda and k.is_cuda and v.is_cuda):
-        raise RuntimeError("flash_attention_decode needs device tensors: there is no CPU path")
-    fp8 = getattr(torch, "float8_e4m3fn", None)
-    kv8 = fp8 is not None and k.dtype == fp8 and v.dtype == fp8 and q.dtype == torch.bfloat16  # an e4m3 KV cache under bf16 queries (fa_fwd_decode_kv8)
-    if q.dtype not in (torch.float16, torch.bfloat16, fp8) or v.dtype != k.dtype or (k.dtype != q.dtype and not kv8):
+    _on_device("flash_attention_decode", q, k, v)
+    kv8 = _FP8 is not None and k.dtype == _FP8 and v.dtype == _FP8 and q.dtype == torch.bfloat16  # an e4m3 KV cache under bf16 queries (fa_fwd_decode_kv8)
+    if q.dtype not in (torch.float16, torch.bfloat16, _FP8) or v.dtype != k.dtype or (k.dtype != q.dtype and not kv8):
         raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k.dtype} {v.dtype} (one of f16 / bf16 / e4m3, or bf16 queries on an e4m3 cache)")
-    odt = torch.bfloat16 if q.dtype == fp8 else q.dtype  # e4m3 inputs: bf16 output, as in flash_attention_forward
-    qbs, qhs = _strides(q)
-    kbs, khs = _strides(k)
-    if _strides(v) != (kbs, khs):
-        raise ValueError("k and v must share batch/head strides")
-    if out is None:
-        out = torch.empty_strided((B, Hq, Nq, D), q.stride(), dtype=odt, device=q.device)
-    elif not out.is_cuda or out.device != q.device or out.dtype != odt or out.shape != q.shape or _strides(out) != (qbs, qhs):
-        raise ValueError("out must be a device tensor with q's shape/strides")
-    if return_lse and lse is None:
-        lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device)
-    if lse is not None and (not lse.is_cuda or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * Hq * Nq):
-        raise ValueError("lse must be contiguous fp32 [B,Hq,Nq] on q's device")
-    need = decode_workspace_bytes(B, Hq, Hkv, Nq, Nk, D)
-    if workspace is None:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-    elif not workspace.is_cuda or workspace.device != q.device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise ValueError("workspace must be a contiguous uint8 device tensor")
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
-    if stream is None:
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-    with torch.cuda.device(q.device):
-        entry = lib.fa_fwd_decode_kv8 if kv8 else lib.fa_fwd_decode
-        st = entry(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr() if lse is not None else None,
-                   B, Hq, Hkv, Nq, Nk, D, float(scale), qbs, qhs, kbs, khs, int(bool(is_causal)), _TORCH2FA[q.dtype],
-                   workspace.data_ptr(), workspace.numel(), stream)
-    if st != 0:
-        raise FaError(st, lib.fa_last_error().decode())
+    qs, ks = _strides(q), _kv_strides(k, v)
+    out, lse = _out(out, q, qs), _lse(lse, return_lse, q)
+    ws = _workspace(workspace, decode_workspace_bytes(B, Hq, Hkv, Nq, Nk, D), q.device)
+    _call(lib, "fa_fwd_decode_kv8" if kv8 else "fa_fwd_decode",
+          (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), B, Hq, Hkv, Nq, Nk, D, _scale(scale, D), *qs, *ks,
+           int(bool(is_causal)), _TORCH2FA[q.dtype], ws.data_ptr(), ws.numel()), q.device, stream)
     return out, lse
 
 
@@ -292,40 +275,18 @@ def flash_attention_decode_paged(
     if (block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or not block_table.is_contiguous()
             or seqlens_k.dtype != torch.int32 or seqlens_k.shape != (B,) or not seqlens_k.is_contiguous()):
         raise ValueError("block_table must be a contiguous int32 [B, max_pages_per_seq] tensor and seqlens_k a contiguous int32 [B] one")
-    fp8 = getattr(torch, "float8_e4m3fn", None)
-    pairs = {(torch.float16, torch.float16), (torch.bfloat16, torch.bfloat16), (fp8, fp8), (torch.bfloat16, fp8)}
+    pairs = {(torch.float16, torch.float16), (torch.bfloat16, torch.bfloat16), (_FP8, _FP8), (torch.bfloat16, _FP8)}
     if v_pages.dtype != k_pages.dtype or (q.dtype, k_pages.dtype) not in pairs:
         raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k_pages.dtype} {v_pages.dtype} (one of f16 / bf16 / e4m3, or bf16 queries on "
                          "an e4m3 pool)")
-    odt = torch.bfloat16 if q.dtype == fp8 else q.dtype
-    qbs, qhs = _strides(q)
+    qs = _strides(q)
     max_pages = block_table.shape[1]
-    if out is None:
-        out = torch.empty_strided((B, Hq, Nq, D), q.stride(), dtype=odt, device=q.device)
-    elif not out.is_cuda or out.device != q.device or out.dtype != odt or out.shape != q.shape or _strides(out) != (qbs, qhs):
-        raise ValueError("out must be a device tensor with q's shape/strides")
-    if return_lse and lse is None:
-        lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device)
-    if lse is not None and (not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or not lse.is_contiguous()
-                            or lse.numel() != B * Hq * Nq):
-        raise ValueError("lse must be contiguous fp32 [B,Hq,Nq] on q's device")
-    if workspace is None:
-        workspace = torch.empty(max(decode_paged_workspace_bytes(B, Hq, Hkv, Nq, D, P, max(max_pages, 1)), 16), dtype=torch.uint8,
-                                device=q.device)
-    elif not workspace.is_cuda or workspace.device != q.device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise ValueError("workspace must be a contiguous uint8 device tensor")
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
-    if stream is None:
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-    with torch.cuda.device(q.device):
-        st = lib.fa_fwd_decode_paged(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(),
-                                     lse.data_ptr() if lse is not None else None, block_table.data_ptr(), seqlens_k.data_ptr(),
-                                     B, Hq, Hkv, Nq, D, P, num_pages, max_pages, float(scale), qbs, qhs, ps, hs, rs,
-                                     block_table.stride(0), int(bool(is_causal)), _TORCH2FA[q.dtype], _TORCH2FA[k_pages.dtype],
-                                     workspace.data_ptr(), workspace.numel(), stream)
-    if st != 0:
-        raise FaError(st, lib.fa_last_error().decode())
+    out, lse = _out(out, q, qs), _lse(lse, return_lse, q)
+    ws = _workspace(workspace, decode_paged_workspace_bytes(B, Hq, Hkv, Nq, D, P, max(max_pages, 1)), q.device)
+    _call(lib, "fa_fwd_decode_paged",
+          (q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(), _ptr(lse), block_table.data_ptr(), seqlens_k.data_ptr(),
+           B, Hq, Hkv, Nq, D, P, num_pages, max_pages, _scale(scale, D), *qs, ps, hs, rs, block_table.stride(0), int(bool(is_causal)),
+           _TORCH2FA[q.dtype], _TORCH2FA[k_pages.dtype], ws.data_ptr(), ws.numel()), q.device, stream)
     return out, lse
 
 
@@ -346,10 +307,8 @@ def flash_attention_backward(
     lib = load_library()
     if q.dim() != 4 or any(t.shape != q.shape for t in (o, d_o)) or k.dim() != 4 or v.shape != k.shape:
         raise ValueError("q, o, d_o must share one [B,Hq,N,D] shape and k, v one [B,Hkv,N,D] shape")
-    if not all(t.is_cuda for t in (q, k, v, o, d_o, lse)):
-        raise RuntimeError("flash_attention_backward needs device tensors: there is no CPU path")
-    fp8 = q.dtype == torch.float8_e4m3fn
-    if fp8:  # e4m3 Q, K, V with the bf16 O the forward wrote for them (and a bf16 dO)
+    _on_device("flash_attention_backward", q, k, v, o, d_o, lse)
+    if q.dtype == _FP8:  # e4m3 Q, K, V with the bf16 O the forward wrote for them (and a bf16 dO)
         if any(t.dtype != q.dtype for t in (k, v)) or any(t.dtype != torch.bfloat16 for t in (o, d_o)):
             raise ValueError("backward with e4m3 q needs e4m3 k, v and bf16 o, d_o")
     elif q.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q.dtype for t in (k, v, o, d_o)):
@@ -358,24 +317,15 @@ def flash_attention_backward(
     Bk, Hkv, Nk, Dk = k.shape
     if (Bk, Dk) != (B, D) or H % Hkv:
         raise ValueError(f"k/v shape {tuple(k.shape)} does not fit q {tuple(q.shape)} (same B, D; Hq % Hkv == 0)")
-    bs, hs = _strides(q)
-    kbs, khs = _strides(k)
-    if any(_strides(t) != (bs, hs) for t in (o, d_o)) or _strides(v) != (kbs, khs):
+    qs, ks = _strides(q), _kv_strides(k, v)
+    if any(_strides(t) != qs for t in (o, d_o)):
         raise ValueError("q, o, d_o must share batch/head strides, and so must k, v")
     if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * H * N:
         raise ValueError("lse must be contiguous fp32 [B,H,N]")
     dq = torch.empty_strided((B, H, N, D), q.stride(), dtype=torch.float32, device=q.device)
     dk, dv = (torch.empty_strided((B, Hkv, Nk, D), k.stride(), dtype=torch.float32, device=q.device) for _ in range(2))
-    ws = torch.empty(lib.fa_bwd_workspace_bytes_ex(_TORCH2FA[q.dtype], B, H, Hkv, N, Nk, D, bs, hs, kbs, khs), dtype=torch.uint8,
-                     device=q.device)
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
-    if stream is None:
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-    with torch.cuda.device(q.device):
-        st = lib.fa_bwd_ex(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(),
-                           dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), B, H, Hkv, N, Nk, D, float(scale), bs, hs,
-                           kbs, khs, int(bool(is_causal)), _TORCH2FA[q.dtype], stream)
-    if st != 0:
-        raise FaError(st, lib.fa_last_error().decode())
+    ws = _workspace(None, lib.fa_bwd_workspace_bytes_ex(_TORCH2FA[q.dtype], B, H, Hkv, N, Nk, D, *qs, *ks), q.device)
+    _call(lib, "fa_bwd_ex", (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dq.data_ptr(),
+                             dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), B, H, Hkv, N, Nk, D, _scale(scale, D), *qs, *ks,
+                             int(bool(is_causal)), _TORCH2FA[q.dtype]), q.device, stream)
     return dq, dk, dv

@@ -18,7 +18,7 @@ from typing import Tuple
 
 import torch
 
-from .ops import FaError, flash_attention_backward, flash_attention_forward, load_library
+from .ops import _TORCH2FA, FaError, _out_dtype, flash_attention_backward, flash_attention_forward, load_library
 
 _LIB = torch.library.Library("fa_mi355", "DEF")
 _LIB.define("attention_forward(Tensor q, Tensor k, Tensor v, bool is_causal=False, float scale=0.0) -> (Tensor, Tensor)")
@@ -30,9 +30,8 @@ def _impl(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, is_causal: bool = F
 
 
 def _meta(q, k, v, is_causal=False, scale=0.0):
-    out_dtype = torch.bfloat16 if q.dtype == getattr(torch, "float8_e4m3fn", None) else q.dtype
     B, H, N, _ = q.shape
-    return torch.empty_like(q, dtype=out_dtype), q.new_empty((B, H, N), dtype=torch.float32)
+    return torch.empty_like(q, dtype=_out_dtype(q.dtype)), q.new_empty((B, H, N), dtype=torch.float32)
 
 
 _LIB.impl("attention_forward", _impl, "CUDA")
@@ -55,10 +54,9 @@ def _backward(ctx, grad_o, grad_lse):
         return None, None, None, None, None
     B, H, N, D = q.shape
     gqa_ok = k.dim() == 4 and (k.shape[0], k.shape[3]) == (B, D) and H % k.shape[1] == 0 and not (ctx.is_causal and k.shape[2] < N)
-    fa_dt = {torch.float16: 1, torch.bfloat16: 2, getattr(torch, "float8_e4m3fn", None): 3}
-    if not gqa_ok or q.dtype not in fa_dt or not load_library().fa_bwd_supported(fa_dt[q.dtype], D):
+    if not gqa_ok or q.dtype not in _TORCH2FA or not load_library().fa_bwd_supported(_TORCH2FA[q.dtype], D):
         raise FaError(-2, f"no backward kernel for q {tuple(q.shape)} k {tuple(k.shape)} {q.dtype} "
-                          "(fa_bwd_ex: f16 / bf16 / e4m3, Hq % Hkv == 0, causal needs Nk >= Nq, head_dim a multiple of 8 up to 128)")
+                          "(f16 / bf16 / e4m3, Hq % Hkv == 0, causal needs Nk >= Nq, head_dim a multiple of 8 up to 128)", "fa_bwd_ex")
     go = grad_o.to(o.dtype)  # (e4m3 inputs: O and its gradient are bf16)
     if go.stride() != q.stride():
         go = torch.empty_strided(q.shape, q.stride(), dtype=o.dtype, device=q.device).copy_(go)

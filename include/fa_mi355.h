@@ -146,10 +146,12 @@ int fa_fwd(const void *q, const void *k, const void *v, void *o, float *lse,
  *   q, o  [B, Hq, Nq, D] with q_batch_stride / q_head_stride;  k, v  [B, Hkv, Nk, D] with kv strides
  *   query head h attends to key/value head h / (Hq / Hkv)   (Hq % Hkv == 0)
  *   causal is bottom-right aligned: key j is visible to query i iff j <= i + (Nk - Nq); needs Nk >= Nq
- *   lse [B, Hq, Nq]. Matrix-core kernels only (f16 / bf16: D = 32, 64, 96, 128, 256; fp8 inputs: D = 64, 128, 256): the 128-row
- *   kernel, or -- at most 64 blocks of 128 query rows against more than 64 keys, e.g. decode steps, D = 64 -- the
- *   split-KV kernel, as FA_VARIANT_AUTO chooses for fa_fwd.
- * With Hkv = Hq, Nk = Nq and equal strides this is fa_fwd(..., FA_VARIANT_MFMA) (or ..._SPLITKV under that rule).
+ *   lse [B, Hq, Nq]. Matrix-core kernels only (f16 / bf16: D a multiple of 8 up to 128, or 256; fp8 inputs: D = 64, 128, 256).
+ *   FA_VARIANT_AUTO here has a rule of its own, which differs from fa_fwd's: the split-KV kernel for at most 64 blocks of 128 query
+ *   rows against more than 64 keys (e.g. decode steps; D = 64); else the 16x16x32 kernel (FA_VARIANT_MFMA16) for the f16 / bf16 head
+ *   dims up to 128 other than 32, 64, 96 and 128 (zero-padded rows), and for f16 / bf16 on more than 512 blocks of 128 query rows
+ *   from Nk = 1024 on (causal: from 1536 at D = 64, from 2048 otherwise); else the 128-row kernel (FA_VARIANT_MFMA).
+ * With Hkv = Hq, Nk = Nq and equal strides this is fa_fwd with the variant this rule picks.
  */
 int fa_fwd_ex(const void *q, const void *k, const void *v, void *o, float *lse,
               int B, int Hq, int Hkv, int Nq, int Nk, int D, float scale,

@@ -155,3 +155,72 @@ def test_product_never_imports_the_oracle():
                             if re.search(r"import oracle|from oracle|libfa_oracle|attn_oracle\.h", line):
                                 bad.append((fn, line.strip()))
     assert not bad, bad
+
+
+def test_shared_rules_refused_on_every_entry_point(fa):
+    # every argument rule the launch entry points share, on each entry point that applies it: (status, keyword of the message).
+    # Fake aligned pointers, as above: each case breaks exactly one rule of a valid base call, so none of them may launch.
+    lib = fa.load_library()
+    P = ctypes.c_void_p
+    ok = P(0x1000)
+    odd = P(0x1008)  # 8-byte aligned only
+
+    def fwd(q=ok, k=ok, v=ok, o=ok, B=2, H=4, N=128, D=64, scale=0.125, bs=None, hs=None):
+        hs = N * D if hs is None else hs
+        return lib.fa_fwd(q, k, v, o, None, B, H, N, D, scale, H * hs if bs is None else bs, hs, 0, 2, 0, None)
+
+    def ex(entry, variant):
+        def call(q=ok, k=ok, v=ok, o=ok, B=2, Hq=4, Hkv=2, Nq=128, Nk=256, D=64, scale=0.125, qbs=None, qhs=None, kbs=None, khs=None,
+                 causal=0):
+            qhs = Nq * D if qhs is None else qhs
+            khs = Nk * D if khs is None else khs
+            args = (q, k, v, o, None, B, Hq, Hkv, Nq, Nk, D, scale, Hq * qhs if qbs is None else qbs, qhs, Hkv * khs if kbs is None else kbs,
+                    khs, causal, 2) + ((variant,) if variant is not None else ())
+            return entry(*args, None)
+        return call
+
+    def decode(entry, dtype):
+        def call(q=ok, k=ok, v=ok, o=ok, ws=ok, B=2, Hq=8, Hkv=2, Nq=1, Nk=256, D=64, scale=0.125, qbs=None, qhs=None, kbs=None, khs=None,
+                 causal=0, wsb=None):
+            qhs = Nq * D if qhs is None else qhs
+            khs = Nk * D if khs is None else khs
+            if wsb is None:
+                wsb = lib.fa_fwd_decode_workspace_bytes(2, 8, 2, 1, 256, 64)
+            return entry(q, k, v, o, None, B, Hq, Hkv, Nq, Nk, D, scale, Hq * qhs if qbs is None else qbs, qhs,
+                         Hkv * khs if kbs is None else kbs, khs, causal, dtype, ws, wsb, None)
+        return call
+
+    def bwd_ex(q=ok, k=ok, v=ok, o=ok, d_o=ok, dq=ok, ws=ok, B=2, Hq=4, Hkv=2, Nq=128, Nk=256, D=64, scale=0.125, qbs=None, qhs=None,
+               kbs=None, khs=None, causal=0):
+        qhs = Nq * D if qhs is None else qhs
+        khs = Nk * D if khs is None else khs
+        return lib.fa_bwd_ex(q, k, v, o, d_o, ok, dq, ok, ok, ws, B, Hq, Hkv, Nq, Nk, D, scale, Hq * qhs if qbs is None else qbs, qhs,
+                             Hkv * khs if kbs is None else kbs, khs, causal, 2, None)
+
+    def bwd(q=ok, o=ok, dq=ok, ws=ok, B=2, H=4, N=128, D=64, scale=0.125, bs=None, hs=None):
+        hs = N * D if hs is None else hs
+        return lib.fa_bwd(q, ok, ok, o, ok, ok, dq, ok, ok, ws, B, H, N, D, scale, H * hs if bs is None else bs, hs, 0, 2, None)
+
+    fwd_rules = [({"o": None}, -1, "null"), ({"D": 0}, -1, ">= 1"), ({"scale": -1.0}, -1, "scale"), ({"bs": 4 * 8192 + 4}, -1, "stride"),
+                 ({"hs": 8000}, -1, "stride"), ({"v": odd}, -1, "aligned")]
+    ex_rules = [({"k": None}, -1, "null"), ({"Nk": 0}, -1, ">= 1"), ({"Hkv": 3}, -1, "Hkv"), ({"Nk": 64, "khs": 256 * 64, "causal": 1}, -2, "causal"),
+                ({"scale": 0.0}, -1, "scale"), ({"qhs": 128 * 64 + 4}, -1, "stride"), ({"khs": 255 * 64}, -1, "stride"),
+                ({"kbs": 2 * 256 * 64 + 4}, -1, "stride"), ({"o": odd}, -1, "aligned")]
+    decode_rules = [({"ws": None}, -1, "null"), ({"Hkv": 0}, -1, ">= 1"), ({"Hkv": 3}, -1, "Hkv"),
+                    ({"Nq": 2, "qhs": 64, "causal": 1, "Nk": 1, "khs": 256 * 64}, -2, "causal"), ({"scale": float("nan")}, -1, "scale"),
+                    ({"qhs": 32}, -1, "stride"), ({"khs": 100 * 64}, -1, "stride"), ({"kbs": 2 * 256 * 64 + 4}, -1, "stride"),
+                    ({"ws": odd}, -1, "aligned"), ({"k": odd}, -1, "aligned"), ({"wsb": 16}, -1, "workspace")]
+    bwd_rules = [({"ws": None}, -1, "null"), ({"N": 0}, -1, ">= 1"), ({"scale": 0.0}, -1, "scale"), ({"hs": 128 * 64 - 8}, -1, "stride"),
+                 ({"bs": 4 * 8192 + 4}, -1, "stride"), ({"dq": odd}, -1, "aligned")]
+    bwd_ex_rules = [({"d_o": None}, -1, "null"), ({"Nk": 0}, -1, ">= 1"), ({"Hkv": 3}, -1, "Hkv"),
+                    ({"Nk": 64, "khs": 256 * 64, "causal": 1}, -2, "causal"), ({"scale": -0.5}, -1, "scale"), ({"qhs": 100}, -1, "stride"),
+                    ({"khs": 256 * 64 + 4}, -1, "key/value strides"), ({"o": odd}, -1, "aligned")]
+    entries = {"fa_fwd": (fwd, fwd_rules), "fa_fwd_ex": (ex(lib.fa_fwd_ex, None), ex_rules), "fa_fwd_exv": (ex(lib.fa_fwd_exv, 4), ex_rules),
+               "fa_fwd_decode": (decode(lib.fa_fwd_decode, 2), decode_rules),
+               "fa_fwd_decode_kv8": (decode(lib.fa_fwd_decode_kv8, 2), decode_rules + [({"khs": 256 * 64 + 8}, -1, "stride")]),
+               "fa_bwd": (bwd, bwd_rules), "fa_bwd_ex": (bwd_ex, bwd_ex_rules)}
+    for name, (call, rules) in entries.items():
+        for kw, status, word in rules:
+            assert call(**kw) == status, (name, kw)
+            msg = lib.fa_last_error().decode()
+            assert name.startswith(msg.split(":")[0]) and word in msg, (name, kw, msg)  # (fa_fwd_exv reports as fa_fwd_ex, _kv8 as fa_fwd_decode)
