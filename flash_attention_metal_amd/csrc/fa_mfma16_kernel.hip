@@ -199,6 +199,7 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
   // i.e. "the top exponent bit of some packed P' is set" -- an OR over the 16 packed registers instead of 32 additions. bf16 keeps
   // fp32's exponent range (BIAS 7: THR 8 as before); f16 loses probabilities below 2^-24, so its reference sits only 3 above (THR 4).
   constexpr float BIAS = !ONES ? 0.0f : std::is_same<Tag, F16>::value ? 3.0f : 7.0f;
+  constexpr float FIRST_SUM_FLOOR = std::is_same<Tag, F16>::value ? 1.0f : 0x1p-64f;  // see tile(): the first tile starts over below it
   // (the reference of row (16qt + c) itself -- log2 units: a stale row max + BIAS -- lives negated in negm[qt] below)
   float l[2] = {0.0f, 0.0f};            // !ONES: this lane's share of the row sums
   f32x4 lacc[2];                        // ONES: the row sums, complete, in every register of the tuple (accumulator of the ones tile)
@@ -386,9 +387,23 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
       float ls[2] = {0.0f, 0.0f};
       // redo (wave-uniform): first the row maxima of the raw scores -> new reference, then the hot pass. The FIRST tile starts without
       // it (ONES): its reference is the constant BIAS, i.e. an assumed row maximum of 0 -- any finite reference is as good as the true
-      // maximum as long as no P' reaches 2 (the hot pass's own test) and the row sums do not vanish (tested once, behind the first
-      // tile's PV product: scores below -2^6 only) -- which saves every block a whole score pass (16 MFMAs, the maxima, their cross-lane
-      // steps). (A 16-key reference for the first tile, 4 MFMAs instead of 16, was measured: no gain, profiles/r04/ab_mfma16_first_tile.log.)
+      // maximum as long as no P' reaches 2 (the hot pass's own test) and the rounding of P' to the input type keeps its bits (tested
+      // once, behind the first tile's PV product: no row sum below FIRST_SUM_FLOOR) -- which saves every block a whole score pass (16
+      // MFMAs, the maxima, their cross-lane steps). (A 16-key reference for the first tile, 4 MFMAs instead of 16, was measured: no gain,
+      // profiles/r04/ab_mfma16_first_tile.log.)
+      // FIRST_SUM_FLOOR. bf16 has fp32's exponent range: P' keeps its 8 bits down to 2^-126, the floor only catches sums that vanish
+      // (2^-64: scores below -2^6). f16 P' is SUBNORMAL below 2^-14 and zero below 2^-25, and the matrix core takes subnormal f16
+      // operands as they are (measured: the error grows smoothly with the depth of the scores, profiles/r06/parent_score_range.log): a
+      // row whose first 64 scores lie at -11 ... -22 would be summed from probabilities of 0 ... 10 bits, and nothing renews the
+      // reference later (no P' >= 2). Measured boundary of the first tile alone (tests/test_gpu_score_range.py, identical keys: every
+      // P' of a row rounds the same way): sums of 2^-7.5 and more hold the LSE bar, sums of 2^-8 ... 2^-9 (P' below 2^-14) miss it.
+      // A floor just above that, 2^-7, is not enough: a first tile that sums to 2^-6 followed by a thousand keys 8 log2 units lower
+      // (P' of 2^-20: five bits) missed the bar by 2.6x (profiles/r06/floor_2m7_tail_case.log) -- the reference stays for the whole
+      // row. What a floor F buys: a subnormal P' is rounded by at most 2^-25 absolute, so n keys move a row sum >= F by at most
+      // n * 2^-25 / F relative. F = 1: 1.2e-4 at 4096 keys, all roundings in one direction (2^-7: 1.6e-2). (A row that did start
+      // over has its largest P' at 2^-3, a sum of 2^-3 at least: the kept first tile is never the weaker of the two.) Ordinary rows
+      // (scores around 0) sum to about 8 over 64 keys and never start over; the first rows under the causal mask (fewer than 8
+      // visible keys) do, one wave per head.
       bool redo = FIRST && !ONES;
       for (;;) {
         if (__builtin_expect(redo, 0)) {
@@ -448,9 +463,9 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
         __builtin_amdgcn_s_setprio(0);
 #endif
         if constexpr (FIRST && ONES) {
-          // the assumed reference was too HIGH for some row (every score of its first 64 keys below about -2^6: sums under 2^-64):
-          // start the tile over with the true maxima (O and the row sums hold nothing of weight: cleared)
-          if (__builtin_expect(!redo && __builtin_amdgcn_ballot_w64(fminf(lacc[0][0], lacc[1][0]) < 0x1p-64f) != 0, 0)) {
+          // the assumed reference was too HIGH for some row (its first-tile sum is below FIRST_SUM_FLOOR): start the tile over with
+          // the true maxima (O and the row sums hold nothing of weight: cleared)
+          if (__builtin_expect(!redo && __builtin_amdgcn_ballot_w64(fminf(lacc[0][0], lacc[1][0]) < FIRST_SUM_FLOOR) != 0, 0)) {
 #pragma unroll
             for (int qt = 0; qt < 2; ++qt) {
 #pragma unroll

@@ -118,8 +118,13 @@ enum fa_status {
  * without the pre-scaling on config 3). FA_VARIANT_MFMA16 additionally takes its row sums from the matrix core, i.e. it adds the
  * probabilities AFTER their rounding to the input type (the very values the PV product multiplies: O's weights then add up to
  * exactly 1): ln(l) carries that rounding, at most 2^-8 (bf16) / 2^-11 (f16) on top of the bound above and far less on average
- * (measured: 4e-4 at N = 128, below 1e-4 from N = 1024 on, bf16). Every other kernel / dtype (FA_VARIANT_MFMA_EXACT, the split-KV
- * and paired-block kernels, fp8 inputs): |lse - exact| <= 1e-4 for |lse| <= ~10.
+ * (measured: 4e-4 at N = 128, below 1e-4 from N = 1024 on, bf16). With f16 inputs FA_VARIANT_MFMA16 rounds a probability with all 11
+ * bits while it is at least 2^-11 of the largest one its row had seen when the row's reference was last set (2^-14 of the row sum of the
+ * first 64 keys, until a score rises 4 log2 units above them), with one bit less per factor of 2 below that, and drops it below 2^-22
+ * (2^-25): n such keys move lse by at most n * 2^-22 (n * 2^-25), all roundings in one direction. Where the scores sit does not
+ * matter: the first tile is started over from its true row maxima whenever its probabilities against the assumed maximum of 0 add up
+ * to less than 1. Every other kernel / dtype (FA_VARIANT_MFMA_EXACT, the split-KV and paired-block kernels, fp8 inputs):
+ * |lse - exact| <= 1e-4 for |lse| <= ~10.
  *
  * fp8 probabilities. FA_VARIANT_MFMA_FP8PV (e4m3 inputs, D = 64 or 128; FA_VARIANT_AUTO's choice for grids that fill the chip) runs BOTH
  * products on the fp8 matrix pipe: the probabilities are rounded to e4m3 (3 mantissa bits) on their way into the PV product, as the

@@ -17,19 +17,10 @@ Index logic (causal mask, tile skip, head/batch addressing) is checked bit-exact
 import numpy as np
 import pytest
 
-from util import LN2, effective_q, fp8pv_lse_term, fp8pv_term, is_prescaled, lse_tol, make_qkv, o_tol, rowsum_term, run_op, to_dev
+from util import (LN2, MFMA_VARIANTS, TOL_LSE, TOL_O, check, effective_q, fp8pv_lse_term, fp8pv_term, is_prescaled, lse_tol, make_qkv, need,
+                  rowsum_term, run_op, to_dev)
 
 pytestmark = pytest.mark.gpu
-
-TOL_O = {"f32": 2e-5, "f16": 1.5e-3, "bf16": 6e-3}
-TOL_LSE = {"f32": 2e-5, "f16": 1e-4, "bf16": 1e-4}
-# the matrix-core kernels by name; "auto" picks by grid size
-MFMA_VARIANTS = ["mfma", "mfma_splitkv", "mfma_split2", "mfma_exact", "mfma_h64s2", "mfma16", "mfma_fp8pv"]
-
-
-def need(fa, dtype, variant, D):
-    if not fa.supported({"fp8": "fp8_e4m3"}.get(dtype, dtype), variant, D):
-        pytest.skip(f"{variant} has no kernel for {dtype} D={D}")
 
 
 @pytest.fixture(scope="module")
@@ -41,24 +32,6 @@ def fa():
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     fa.load_library()  # raises if the HIP library is missing: no silent fallback
     return fa
-
-
-def check(fa, oracle, q, k, v, dtype, causal, variant, tol_scale=1.0, scale=None):
-    o, lse = run_op(fa, q, k, v, dtype, causal, variant, scale)
-    assert np.isfinite(o).all() and np.isfinite(lse).all()
-    pre = is_prescaled(fa, dtype, variant, *q.shape, causal)
-    if pre:  # strict: the exact operator on the operand the kernel really multiplies
-        o64, lse64 = oracle.attn_fwd_f64(effective_q(oracle, q, dtype, scale), k, v, causal, LN2)
-        err_o, err_l = np.abs(o - o64).max(), np.abs(lse - lse64).max()
-        assert err_o < TOL_O[dtype] * tol_scale, (variant, dtype, causal, q.shape, err_o, "vs oracle on Q~")
-        assert err_l < TOL_LSE[dtype] * tol_scale + rowsum_term(dtype, pre), (variant, dtype, causal, q.shape, err_l, "vs oracle on Q~")
-    # against the true Q: the plain tolerances, plus the documented operand-rounding bound where it applies
-    o64, lse64 = oracle.attn_fwd_f64(q, k, v, causal, scale)
-    err_o = np.abs(o - o64).max()
-    err_l = np.abs(lse - lse64).max()
-    assert err_o < o_tol(dtype, pre, q, k, v, scale, TOL_O[dtype] * tol_scale), (variant, dtype, causal, q.shape, err_o)
-    assert err_l < lse_tol(dtype, pre, q, k, scale, TOL_LSE[dtype] * tol_scale), (variant, dtype, causal, q.shape, err_l)
-    return err_o, err_l
 
 
 # --------------------------------------------------------------------------
@@ -257,6 +230,8 @@ def test_strongly_negative_scores_from_the_first_tile_on(fa, oracle_mod, dtype, 
     # The 16x16x32 kernel forms the FIRST tile's probabilities against an assumed row maximum of 0 and checks afterwards that no row's
     # sum vanished (csrc/fa_mfma16_kernel.hip, tile()): rows whose every score is far below zero -- here around -40 ... -1400 in log2
     # units, in all tiles or in the first tile only -- must come out like any other (every kernel runs the case).
+    # (Here every P' of the first tile is zero. The range in between -- scores at -6 ... -30, where f16 probabilities against the assumed
+    # maximum are subnormal rather than zero, rows of different depths inside one wave, bf16's own edge at 2^-64 --: tests/test_gpu_score_range.py.)
     need(fa, dtype, variant, 64)
     B, H, N, D = 1, 3, 300, 64
     rng = np.random.default_rng(77)

@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests (test side only: imports the oracle)."""
 import numpy as np
+import pytest
 
 TORCH_DTYPE = {"f32": "float32", "f16": "float16", "bf16": "bfloat16", "fp8": "float8_e4m3fn"}
 
@@ -105,3 +106,33 @@ def o_tol(dtype, prescaled, q, k, v, scale=None, base=0.0):
     if not prescaled or dtype not in PRESCALE_EPS:
         return base
     return base + 2.0 * float(np.expm1(prescale_delta(dtype, q, k, scale))) * float(np.abs(v).max())
+
+
+# ---- the bars of the parity tests (tests/test_gpu_parity.py states where they come from) and the check against the oracle ----------
+TOL_O = {"f32": 2e-5, "f16": 1.5e-3, "bf16": 6e-3}
+TOL_LSE = {"f32": 2e-5, "f16": 1e-4, "bf16": 1e-4}
+# the matrix-core kernels by name; "auto" picks by grid size
+MFMA_VARIANTS = ["mfma", "mfma_splitkv", "mfma_split2", "mfma_exact", "mfma_h64s2", "mfma16", "mfma_fp8pv"]
+
+
+def need(fa, dtype, variant, D):
+    if not fa.supported({"fp8": "fp8_e4m3"}.get(dtype, dtype), variant, D):
+        pytest.skip(f"{variant} has no kernel for {dtype} D={D}")
+
+
+def check(fa, oracle, q, k, v, dtype, causal, variant, tol_scale=1.0, scale=None):
+    o, lse = run_op(fa, q, k, v, dtype, causal, variant, scale)
+    assert np.isfinite(o).all() and np.isfinite(lse).all()
+    pre = is_prescaled(fa, dtype, variant, *q.shape, causal)
+    if pre:  # strict: the exact operator on the operand the kernel really multiplies
+        o64, lse64 = oracle.attn_fwd_f64(effective_q(oracle, q, dtype, scale), k, v, causal, LN2)
+        err_o, err_l = np.abs(o - o64).max(), np.abs(lse - lse64).max()
+        assert err_o < TOL_O[dtype] * tol_scale, (variant, dtype, causal, q.shape, err_o, "vs oracle on Q~")
+        assert err_l < TOL_LSE[dtype] * tol_scale + rowsum_term(dtype, pre), (variant, dtype, causal, q.shape, err_l, "vs oracle on Q~")
+    # against the true Q: the plain tolerances, plus the documented operand-rounding bound where it applies
+    o64, lse64 = oracle.attn_fwd_f64(q, k, v, causal, scale)
+    err_o = np.abs(o - o64).max()
+    err_l = np.abs(lse - lse64).max()
+    assert err_o < o_tol(dtype, pre, q, k, v, scale, TOL_O[dtype] * tol_scale), (variant, dtype, causal, q.shape, err_o)
+    assert err_l < lse_tol(dtype, pre, q, k, scale, TOL_LSE[dtype] * tol_scale), (variant, dtype, causal, q.shape, err_l)
+    return err_o, err_l

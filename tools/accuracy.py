@@ -14,6 +14,9 @@ SHAPES = {  # name: (B, H, N, D, dtype, causal) -- heads are cut to --heads (the
     "c2": (1, 8, 1024, 64, "f16", 0), "nc4k": (4, 16, 4096, 64, "bf16", 0), "c3f16": (4, 16, 4096, 64, "f16", 1),
     "c1k": (4, 16, 1024, 64, "bf16", 1), "d128c4k": (1, 32, 4096, 128, "bf16", 1), "d32": (1, 8, 2048, 32, "bf16", 1),
     "d96": (1, 8, 2048, 96, "bf16", 1),
+    # scores far below zero: every 32 rows ramp from 0 down to the 7th entry (log2 units) and back, q = alpha_i*u + noise, k = -20*u + noise
+    # (tests/score_range.py, kind b1: the f16-subnormal window of the 16x16x32 kernel's first tile); amp 1 only
+    "c3f16w": (4, 16, 4096, 64, "f16", 1, -20.0),
 }
 ap = argparse.ArgumentParser(); ap.add_argument("libs", nargs="+"); ap.add_argument("--shapes", default="c3,c4,c5")
 ap.add_argument("--amps", default="1,3"); ap.add_argument("--heads", type=int, default=4); ap.add_argument("--bwd", action="store_true")
@@ -55,13 +58,20 @@ def ref64(q, k, v, causal, scale, d_o=None):
 
 
 for name in a.shapes.split(","):
-    B, H, N, D, dt, causal = SHAPES[name]
+    B, H, N, D, dt, causal, *deepest = SHAPES[name]
     H = min(H, a.heads); B = 1
     tdt = {"bf16": torch.bfloat16, "f16": torch.float16, "fp8": torch.float8_e4m3fn}[dt]; fdt = {"f16": 1, "bf16": 2, "fp8": 3}[dt]
     odt = torch.bfloat16 if dt == "fp8" else tdt
     for amp in [float(x) for x in a.amps.split(",")]:
         g = torch.Generator(device="cuda").manual_seed(0)
         q, k, v = (((torch.rand(B, H, N, D, generator=g, device="cuda") * 2 - 1) * amp).to(tdt) for _ in range(3))
+        if deepest:
+            if amp != 1.0: continue
+            u = torch.randn(D, generator=g, device="cuda"); u /= u.norm()
+            j = torch.arange(N, device="cuda"); j = torch.where((j // 32) % 2 == 0, j % 32, 31 - j % 32)
+            alpha = (-deepest[0] * j / 31.0) * D ** 0.5 / 1.4426950408889634 / 20.0
+            q = (alpha[:, None] * u + 0.05 * torch.randn(B, H, N, D, generator=g, device="cuda")).to(tdt)
+            k = (-20.0 * u + 0.05 * torch.randn(B, H, N, D, generator=g, device="cuda")).to(tdt)
         scale = D ** -0.5
         do_bwd = a.bwd and dt != "fp8" and D in (64, 128) and N <= 4096
         d_o = ((torch.rand(B, H, N, D, generator=g, device="cuda") * 2 - 1)).to(tdt) if do_bwd else None
