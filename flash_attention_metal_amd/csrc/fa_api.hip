@@ -486,7 +486,7 @@ static int bwd_impl(const char *fn, const void *q, const void *k, const void *v,
   TRY(strides_ok(fn, "key/value ", Nk, D, kbs, khs, stride_mult(dtype), Hkv > 1));
   TRY(aligned16(fn, "tensors", {q, k, v, o, d_o, dq, dk, dv}));
   if (!fa::bwd_supported(dtype, D))
-    return fail(FA_ERR_UNSUPPORTED, "%s: no kernel for dtype=%s D=%d (f16 / bf16 / fp8_e4m3, D a multiple of 8 up to 128)", fn, fa_dtype_name(dtype), D);
+    return fail(FA_ERR_UNSUPPORTED, "%s: no kernel for dtype=%s D=%d (f16 / bf16: D a multiple of 8 up to 128, or 256; fp8_e4m3: D a multiple of 16 up to 128)", fn, fa_dtype_name(dtype), D);
   const int rows = std::max(N, Nk);
   TRY(head_fits(fn, (double)rows * D * 2, 4, ""));
   // head dims other than 64 / 128 run on zero-padded rows whose padding is fetched from offset 2^31 + ... (fa_bwd_kernels.hip, PAD)

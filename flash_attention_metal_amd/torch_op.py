@@ -56,7 +56,7 @@ def _backward(ctx, grad_o, grad_lse):
     gqa_ok = k.dim() == 4 and (k.shape[0], k.shape[3]) == (B, D) and H % k.shape[1] == 0 and not (ctx.is_causal and k.shape[2] < N)
     if not gqa_ok or q.dtype not in _TORCH2FA or not load_library().fa_bwd_supported(_TORCH2FA[q.dtype], D):
         raise FaError(-2, f"no backward kernel for q {tuple(q.shape)} k {tuple(k.shape)} {q.dtype} "
-                          "(f16 / bf16 / e4m3, Hq % Hkv == 0, causal needs Nk >= Nq, head_dim a multiple of 8 up to 128)", "fa_bwd_ex")
+                          "(f16 / bf16 / e4m3, Hq % Hkv == 0, causal needs Nk >= Nq, head_dim a multiple of 8 up to 128, or 256)", "fa_bwd_ex")
     go = grad_o.to(o.dtype)  # (e4m3 inputs: O and its gradient are bf16)
     if go.stride() != q.stride():
         go = torch.empty_strided(q.shape, q.stride(), dtype=o.dtype, device=q.device).copy_(go)

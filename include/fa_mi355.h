@@ -110,8 +110,10 @@ enum fa_status {
  * FA_VARIANT_MFMA_SPLIT2, FA_VARIANT_MFMA_H64S2 and FA_VARIANT_MFMA16 with f16 / bf16 inputs and D <= 128 (what FA_VARIANT_AUTO
  * picks for BASELINE configs 3 and 4, and the 128-row route of fa_fwd_ex) -- multiply the query operand by scale*log2(e) and round
  * it to the input type ONCE per block of query rows, so that the matrix core delivers the exponent of every probability directly
- * (replaces the per-score scale-and-subtract of kernels.metal:763-771): the result is the exact operator applied to a Q' with
- * |Q' - Q| <= eps*|Q| element-wise, eps = 2^-9 (bf16) / 2^-12 (f16), half an ulp of the input type. Consequently
+ * (replaces the per-score scale-and-subtract of kernels.metal:763-771): the result is the exact operator applied to a
+ * Q' that differs from Q by one rounding per element: at most half an ulp of the input type, which is eps = 2^-9 (bf16) / 2^-12 (f16)
+ * relative for an element just below a power of two and up to 2 eps = 2^-8 / 2^-11 just above one, so |Q' - Q| <= 2 eps |Q| holds
+ * element-wise; over a row the roundings are independent and |Q' - Q|_2 is typically below eps |Q|_2 (rms 0.6-1.2 eps per element; the bound below uses norms, and the tests hold it as stated). Consequently
  *     |lse - exact| <= 1e-4 + eps * scale * |q_i|_2 * max_j |k_j|_2        (row i),
  * i.e. relative to the score magnitude (measured on BASELINE config 3, U(-1,1) inputs: max 1.0e-3, rms 4e-5 for
  * bf16; 1.3e-4 / 5e-6 for f16), while O keeps the tolerance of the other kernels (max|O - exact| 3.1e-3 vs 2.9e-3
@@ -240,6 +242,21 @@ int fa_fwd_decode_paged_supported(int q_dtype, int kv_dtype, int D, int Hq, int 
  * dtype F16 or BF16 (FP8_E4M3: see fa_bwd_workspace_bytes_ex); D = 64 (the reference's, kernels.metal:905-1265) or 128 natively, any other multiple of 8 up to 128 (32, 96, ...)
  * through the next larger kernel on zero-padded rows (same results per real column; a head must then stay below 2 GiB). D = 256: its own
  * instantiation (one workgroup per CU, f16 / bf16 only).
+ *
+ * Backward accuracy. Sums are fp32; what is rounded to the 16-bit input type (unit roundoff u = 2^-8 bf16 / 2^-11 f16: half an ulp
+ * is up to u relative just above a power of two) is the operand pre-scaled by scale*log2(e) (Q in the dQ kernel, K in the dK/dV
+ * kernel: score (i,j) moves by at most d_ij = u * scale * sum_d |q_id k_jd|), and P and dS = P o (dP - delta) on their way into the
+ * second products; delta is formed from the O the caller passes. Element by element, with the exact P and dS,
+ *     |dQ_id - exact| <= scale * sum_j E_ij |k_jd|,   |dK_jd - exact| <= scale * sum_i E_ij |q_id|,
+ *     |dV_jd - exact| <= sum_i (P_ij (u + expm1(d_ij)) + t) |dO_id|,
+ *     E_ij = |dS_ij| (u + expm1(d_ij)) + P_ij exp(d_ij) (u sum_d |dO_id O_id| + fp32 terms) + t
+ * (plus 2^-24 * N relative for the fp32 sums; over the query heads of a group the bounds add; tests/backward_bound.py spells out
+ * every term, tests/test_gpu_backward_rows.py holds every element of the three gradients to it: measured worst error / bound 0.87).
+ * That is about 2-5e-2 (bf16) / 3-6e-3 (f16) of a row's own largest gradient. t = 2^-25 for f16 and 0 for bf16: f16 values below
+ * 2^-14 are subnormal and rounded absolutely, to a multiple of 2^-24. They are KEPT -- the conversions and the matrix cores honour
+ * subnormal f16 operands, nothing is flushed to zero -- so a d_o of order 2^-8 and less (f16 training without loss scaling), where
+ * every dS is subnormal, still gives dQ / dK within the bound above (test_rows_small_d_o), at the absolute resolution 2^-25 per
+ * (query, key) pair instead of 11 bits; below about 2^-24 / P_ij a dS is rounded to zero, as f16 itself would. e4m3 inputs: u = 2^-8.
  */
 int fa_bwd(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse,
            float *dq, float *dk, float *dv, void *workspace,

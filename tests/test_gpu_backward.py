@@ -9,7 +9,7 @@ in fp64 by tests/test_oracle_backward.py). Tolerance: max|g - g_ref| / max|g_ref
 import numpy as np
 import pytest
 
-from util import make_qkv, to_dev
+from util import make_qkv, rect_reference, to_dev
 
 pytestmark = pytest.mark.gpu
 TOL = {"f16": 4e-3, "bf16": 2e-2}
@@ -97,29 +97,6 @@ def test_backward_grouped_query_heads(fa, oracle_mod, causal, D):
     for a, b_ in ((qd.grad, q2.grad), (kd.grad, k2.grad), (vd.grad, v2.grad)):
         assert a.shape == b_.shape
         assert (a.double() - b_).abs().max().item() / b_.abs().max().item() < 3e-2
-
-
-def rect_reference(q, k, v, do, causal):
-    """fp64 gradients of softmax(q k^T / sqrt(D) [+ bottom-right causal mask]) v for q [B,Hq,Nq,D], k / v [B,Hkv,Nk,D]
-    (plain numpy: the C oracle's backward is square). dS = P o (dP - rowsum(dO o O)), kernels.metal:1160-1169."""
-    B, Hq, Nq, D = q.shape
-    Hkv, Nk = k.shape[1], k.shape[2]
-    G = Hq // Hkv
-    q64, do64 = q.astype(np.float64), do.astype(np.float64)
-    ke, ve = (np.repeat(x.astype(np.float64), G, axis=1) for x in (k, v))
-    s_ = np.einsum("bhid,bhjd->bhij", q64, ke) / np.sqrt(D)
-    if causal:
-        i, j = np.arange(Nq)[:, None], np.arange(Nk)[None, :]
-        s_ = np.where(j <= i + (Nk - Nq), s_, -np.inf)
-    p_ = np.exp(s_ - s_.max(-1, keepdims=True))
-    p_ /= p_.sum(-1, keepdims=True)
-    o = np.einsum("bhij,bhjd->bhid", p_, ve)
-    dv = np.einsum("bhij,bhid->bhjd", p_, do64)
-    dp = np.einsum("bhid,bhjd->bhij", do64, ve)
-    ds = p_ * (dp - (do64 * o).sum(-1, keepdims=True)) / np.sqrt(D)
-    dq = np.einsum("bhij,bhjd->bhid", ds, ke)
-    dk = np.einsum("bhij,bhid->bhjd", ds, q64)
-    return dq, dk.reshape(B, Hkv, G, Nk, D).sum(2), dv.reshape(B, Hkv, G, Nk, D).sum(2)
 
 
 @pytest.mark.parametrize("D", [32, 64, 96, 128, 256])

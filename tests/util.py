@@ -37,7 +37,8 @@ def run_op(fa, q, k, v, dtype, causal, variant="auto", scale=None):
 # input type once per block: they compute the EXACT operator on that Q~ (with scale ln 2). The tests therefore hold them
 # to the strict tolerances against the oracle evaluated on Q~ (effective_q below reproduces the kernel's two fp32
 # multiplications and its RNE rounding bit for bit), and to the documented bound against the oracle on the true Q.
-PRESCALE_EPS = {"f16": 2.0 ** -12, "bf16": 2.0 ** -9}  # half an ulp of the input type, relative
+PRESCALE_EPS = {"f16": 2.0 ** -12, "bf16": 2.0 ** -9}  # half an ulp relative to the TOP of a binade (the rounding is off by up to twice
+# that, 2^-11 / 2^-8 relative, just above a power of two: tests/backward_bound.py uses those; the bars below apply this eps to row norms)
 LN2 = 0.6931471805599453
 
 
@@ -136,3 +137,27 @@ def check(fa, oracle, q, k, v, dtype, causal, variant, tol_scale=1.0, scale=None
     assert err_o < o_tol(dtype, pre, q, k, v, scale, TOL_O[dtype] * tol_scale), (variant, dtype, causal, q.shape, err_o)
     assert err_l < lse_tol(dtype, pre, q, k, scale, TOL_LSE[dtype] * tol_scale), (variant, dtype, causal, q.shape, err_l)
     return err_o, err_l
+
+
+def rect_reference(q, k, v, do, causal, scale=None):
+    """fp64 gradients of softmax(scale * q k^T [+ bottom-right causal mask]) v for q [B,Hq,Nq,D], k / v [B,Hkv,Nk,D]; scale defaults to
+    1/sqrt(D) (plain numpy: the C oracle's backward is square). dS = P o (dP - rowsum(dO o O)), kernels.metal:1160-1169."""
+    B, Hq, Nq, D = q.shape
+    Hkv, Nk = k.shape[1], k.shape[2]
+    G = Hq // Hkv
+    sc = 1.0 / np.sqrt(D) if scale is None else float(scale)
+    q64, do64 = q.astype(np.float64), do.astype(np.float64)
+    ke, ve = (np.repeat(x.astype(np.float64), G, axis=1) for x in (k, v))
+    s_ = (q64 @ ke.swapaxes(-1, -2)) * sc
+    if causal:
+        i, j = np.arange(Nq)[:, None], np.arange(Nk)[None, :]
+        s_ = np.where(j <= i + (Nk - Nq), s_, -np.inf)
+    p_ = np.exp(s_ - s_.max(-1, keepdims=True))
+    p_ /= p_.sum(-1, keepdims=True)
+    o = p_ @ ve
+    dv = p_.swapaxes(-1, -2) @ do64
+    dp = do64 @ ve.swapaxes(-1, -2)
+    ds = p_ * (dp - (do64 * o).sum(-1, keepdims=True)) * sc
+    dq = ds @ ke
+    dk = ds.swapaxes(-1, -2) @ q64
+    return dq, dk.reshape(B, Hkv, G, Nk, D).sum(2), dv.reshape(B, Hkv, G, Nk, D).sum(2)
