@@ -22,8 +22,10 @@ from .ops import (  # noqa: F401
     flash_attention_decode,
     flash_attention_decode_paged,
     flash_attention_forward,
+    flash_attention_varlen,
     forward_kernel_name,
     supported,
+    varlen_supported,
 )
 from .shard import shard_heads  # noqa: F401
 

@@ -16,6 +16,8 @@ SYMBOLS = {
                        c_float, c_longlong, c_longlong, c_int, c_int, c_int, c_void_p]),
     "fa_fwd_ex": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_void_p]),
     "fa_fwd_exv": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_int, c_void_p]),
+    "fa_fwd_varlen": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_void_p]),
+    "fa_fwd_varlen_supported": (c_int, [c_int, c_int]),
     "fa_fwd_decode": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_void_p, c_longlong, c_void_p]),
     "fa_fwd_decode_kv8": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_void_p, c_longlong, c_void_p]),
     "fa_fwd_decode_workspace_bytes": (c_longlong, [c_int] * 6),

@@ -29,6 +29,8 @@ int fail(int code, const char *fmt, ...) {
 //    paged decode 2 GiB per page of one head;
 //  - the grid guards: B * H * ceil(Nq / 128) (fa_fwd, fa_fwd_exv) or B * H * ceil(max(Nq, Nk) / 128) (backward) below 2^31;
 //    B * Hq * Nq and B * Hkv * 256 for the decodes;
+//  - fa_fwd_varlen has row and head strides (no batch): each at least D and a multiple of 8, checked in its own lines; its size guard is
+//    (max_seqlen + 128) * row_stride * 2 < 4 GiB per sequence, for q and for k / v; its grid guard B * Hq * ceil(max_seqlen_q / 128);
 //  - a missing device: FA_ERR_NO_DEVICE from fa_fwd, FA_ERR_LAUNCH from every other entry point.
 #define TRY(check) do { if (const int st_ = (check)) return st_; } while (0)
 
@@ -340,6 +342,48 @@ int fa_fwd_exv(const void *q, const void *k, const void *v, void *o, float *lse,
     return fail(FA_ERR_UNSUPPORTED, "fa_fwd_ex: variant=%s does not support dtype=%s D=%d", fa_variant_name(variant), fa_dtype_name(dtype), D);
   return launched(fn, launch_fwd(q, k, v, o, lse, B, Hq, Hkv, Nq, Nk, D, scale, q_batch_stride, q_head_stride, kv_batch_stride,
                                  kv_head_stride, is_causal, dtype, variant, (hipStream_t)hip_stream));
+}
+
+int fa_fwd_varlen_supported(int dtype, int D) { return fa::mfma_varlen_supported(dtype, D); }
+int fa_fwd_varlen(const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q, const int *cu_seqlens_k,
+                  int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
+                  long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride, int is_causal,
+                  int dtype, void *hip_stream) {
+  g_err[0] = 0;
+  const char *fn = "fa_fwd_varlen";
+  TRY(nonnull(fn, {q, k, v, o, cu_seqlens_q, cu_seqlens_k}));
+  TRY(positive(fn, {B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D}));
+  TRY(grouped(fn, Hq, Hkv));
+  TRY(scale_ok(fn, scale));
+  if (!fa_fwd_varlen_supported(dtype, D))
+    return fail(FA_ERR_UNSUPPORTED, "fa_fwd_varlen: needs f16 / bf16 and D = 64 | 128, got dtype=%s D=%d", fa_dtype_name(dtype), D);
+  if (max_seqlen_q > total_q || max_seqlen_k > total_k)
+    return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen: max_seqlen (%d, %d) exceeds the token count (%d, %d)", max_seqlen_q, max_seqlen_k, total_q, total_k);
+  // a token's head is D contiguous elements; rows and heads may interleave either way ([total, H, D], [H, total, D], views of a packed
+  // QKV projection), so all that is required of a stride is room for one row and 16-byte alignment of every row
+  const int mult = stride_mult(dtype);
+  if (q_row_stride < D || q_head_stride < D || (q_row_stride % mult) || (q_head_stride % mult))
+    return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen: bad strides (row %lld, head %lld): a row holds %d elements, strides are multiples of %d", q_row_stride,
+                q_head_stride, D, mult);
+  if (kv_row_stride < D || kv_head_stride < D || (kv_row_stride % mult) || (kv_head_stride % mult))
+    return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen: bad key/value strides (row %lld, head %lld): a row holds %d elements, strides are multiples of %d",
+                kv_row_stride, kv_head_stride, D, mult);
+  TRY(aligned16(fn, "tensors", {q, k, v, o}));
+  if (((uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen: cu_seqlens_q / cu_seqlens_k must be int32-aligned");
+  // 32-bit byte offsets inside ONE sequence of one head (its base is a 64-bit address: the tensors themselves may exceed 4 GiB); as in
+  // fa_fwd the staging may address up to two 64-key tiles past the end
+  TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
+  TRY(head_fits(fn, (double)(max_seqlen_k + 128) * (double)kv_row_stride * 2, 4, " (one sequence of max_seqlen_k rows)"));
+  TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));
+  fa::VarlenParams p;
+  p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
+  p.B = B; p.H = Hq; p.Hkv = Hkv; p.N = max_seqlen_q; p.Nk = max_seqlen_k; p.D = D; p.scale = scale;
+  p.batch_stride = 0; p.head_stride = q_head_stride; p.kv_batch_stride = 0; p.kv_head_stride = kv_head_stride;
+  p.is_causal = is_causal ? 1 : 0;
+  p.cu_q = cu_seqlens_q; p.cu_k = cu_seqlens_k;
+  p.total_q = total_q; p.total_k = total_k;
+  p.q_rs = q_row_stride; p.kv_rs = kv_row_stride;
+  return launched(fn, fa::launch_mfma_varlen(p, dtype, (hipStream_t)hip_stream));
 }
 
 int fa_fwd_decode_supported(int dtype, int D, int Hq, int Hkv, int Nq) {

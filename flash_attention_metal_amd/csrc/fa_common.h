@@ -46,6 +46,16 @@ struct Params {
   FastDiv fd_h, fd_gq, fd_nq, fd_hg, fd_per;  // by H, H/Hkv, nq, hg, hg*nq
 };
 
+// one fa_fwd_varlen call (the varlen mode of csrc/fa_mfma_kernel.hip): q / o are [total_q, H, D] and k / v [total_k, Hkv, D] under a row
+// (token) stride and the head strides of Params; B counts sequences, N / Nk hold max_seqlen_q / max_seqlen_k (the grid and the issue
+// order depend on nothing else), batch strides are unused. Sequence b owns tokens cu_q[b] .. cu_q[b+1) and keys cu_k[b] .. cu_k[b+1):
+// both tables are device memory read by the kernels only.
+struct VarlenParams : Params {
+  const int *cu_q, *cu_k;     // int32 [B + 1]
+  int total_q, total_k;       // tokens in q / o and in k / v: every table entry is clamped to [0, total]
+  long long q_rs, kv_rs;      // row strides, elements
+};
+
 // one fa_fwd_decode call (csrc/fa_decode_kernel.hip)
 struct DecodeParams {
   const void *q, *k, *v;
@@ -80,6 +90,8 @@ hipError_t launch_naive(const Params &p, int dtype, hipStream_t s);
 hipError_t launch_tiled(const Params &p, int dtype, hipStream_t s);
 hipError_t launch_tiled_v2(const Params &p, int dtype, hipStream_t s);
 hipError_t launch_mfma(const Params &p, int dtype, hipStream_t s);
+hipError_t launch_mfma_varlen(const VarlenParams &p, int dtype, hipStream_t s);
+bool mfma_varlen_supported(int dtype, int D);
 hipError_t launch_mfma_split2(const Params &p, int dtype, hipStream_t s);
 bool mfma_split2_supported(int dtype, int D);
 hipError_t launch_mfma_h64s2(const Params &p, int dtype, hipStream_t s);

@@ -91,8 +91,15 @@ constexpr bool main_kernel_occ4() {
   return (FA_MAIN_OCC4 != 0) && D == 64 && PRESC && prescale_applies<Tag, D>();
 }
 
-template <typename Tag, int D, bool CAUSAL, int SPLIT, bool PRESC, int ROWS = BM>
-__device__ __forceinline__ void fwd_mfma_body(const Params &p) {
+// PT = VarlenParams ("varlen" mode, fa_fwd_varlen): the "batch" index of the block map selects a sequence of a packed
+// [total, heads, D] batch; its lengths come from the cu_seqlens tables in device memory and take the place of N / Nk, its rows are
+// addressed with a run-time pitch. Everything from LDS onwards -- images, swizzles, MFMA order, softmax -- is the dense kernel's, so a
+// sequence comes out bit for bit as the dense kernel computes it alone.
+template <typename Tag, int D, bool CAUSAL, int SPLIT, bool PRESC, int ROWS = BM, typename PT = Params>
+__device__ __forceinline__ void fwd_mfma_body(const PT &p) {
+  constexpr bool VARLEN = std::is_same<PT, VarlenParams>::value;
+  static_assert(!VARLEN || (SPLIT == 1 && ROWS == BM && PRESC && !std::is_same<Tag, FP8>::value && (D == 64 || D == 128)),
+                "varlen mode: the plain 128-row kernel, 16-bit inputs, LDS-DMA staging");
   constexpr int RW = ROWS / WM;   // row groups = waves per split
   constexpr int ST = 64 * RW;     // threads per split (the staging map's width)
   using M = MT<Tag>;
@@ -110,7 +117,9 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
   constexpr int GRB = D * GB;               // global row bytes
   constexpr int GTILE = BN * GRB;           // global bytes of one K (or V) tile
   constexpr int NCH = BN * (GRB / 16) / ST;  // staged 16-byte global chunks per thread per tile
-  constexpr bool MAIN4 = (FA_MAIN_OCC4 != 0) && main_kernel_occ4<Tag, D, PRESC>() && SPLIT == 1 && ROWS == BM;
+  // (varlen without the mask keeps the prefetch and three workgroups: at 128 registers its extra row pitch and sequence base spill 20 B,
+  // some of it reloaded inside the tile loop. The MFMA order is the same in both forms, so the results do not change.)
+  constexpr bool MAIN4 = (FA_MAIN_OCC4 != 0) && main_kernel_occ4<Tag, D, PRESC>() && SPLIT == 1 && ROWS == BM && !(VARLEN && !CAUSAL);
   constexpr bool VPRE = (D == 64) && !IS_FP8 && !MAIN4;  // prefetch V^T fragments under the QK^T MFMAs
   // Pre-scaled operand (f16/bf16): the Q fragments are multiplied by c = scale.log2(e) and rounded back to the input
   // type ONCE per block, and the running reference -m (log2 units) is the C operand of the first MFMA of every score
@@ -146,15 +155,54 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
   int bh, qb;
   map_block<CAUSAL>(blockIdx.x, p, bh, qb);
   long long base, base_kv;
-  head_bases(bh, p, base, base_kv);
+  // varlen only (each use below keeps the dense expression in the other arm of a compile-time choice, so that the dense kernels
+  // compile to the code they had before the mode existed):
+  int LQ = 0, LK = 0;          // queries and keys of this block's sequence
+  unsigned qrb = 0, kvrb = 0;  // row pitch of Q / O and of K / V in global memory, bytes
+  long long lse_base = 0;      // first LSE element of this block's (head, sequence)
+#define FA_NQ (VARLEN ? LQ : p.N)
+#define FA_NK (VARLEN ? LK : p.Nk)
+  if constexpr (VARLEN) {
+    // ---- sequence b = the "batch" index. Both cu pairs are wave-uniform (scalar loads); every entry is clamped to [0, total], a
+    // non-increasing pair is length 0 and a length stops at max_seqlen, so whatever the tables hold the block stays inside tokens
+    // [0, total) of every tensor. The host never sees the lengths: the grid is sized by max_seqlen_q, and a block past its sequence's
+    // last row leaves here, in front of every barrier.
+    const int b = (int)fdiv((unsigned)bh, p.fd_h), hq = bh - b * p.H;
+    const int sq = min(max(p.cu_q[b], 0), p.total_q), eq = min(max(p.cu_q[b + 1], 0), p.total_q);
+    const int sk = min(max(p.cu_k[b], 0), p.total_k), ek = min(max(p.cu_k[b + 1], 0), p.total_k);
+    LQ = min(max(eq - sq, 0), p.N);
+    LK = min(max(ek - sk, 0), p.Nk);
+    if (qb * ROWS >= LQ) return;
+    base = (long long)sq * p.q_rs + (long long)hq * p.head_stride;
+    base_kv = (long long)sk * p.kv_rs + (long long)fdiv((unsigned)hq, p.fd_gq) * p.kv_head_stride;
+    lse_base = (long long)hq * p.total_q + sq;
+    qrb = (unsigned)p.q_rs * 2;
+    kvrb = (unsigned)p.kv_rs * 2;
+    // no key is visible to any row of the block (no keys at all, or causal with Lk < Lq: key j is visible to query i iff
+    // j <= i + Lk - Lq): O = 0, LSE = -inf, as the paged decode defines it
+    if ((CAUSAL ? min(LK, qb * ROWS + ROWS + LK - LQ) : LK) <= 0) {
+      elem *Oz = (elem *)p.o + base;
+      for (int idx = threadIdx.x; idx < ROWS * CPR; idx += NTHREADS) {
+        const int row = qb * ROWS + idx / CPR, ch = idx % CPR;
+        if (row < LQ) *reinterpret_cast<u32x4 *>(Oz + (long long)row * p.q_rs + ch * 8) = u32x4{0u, 0u, 0u, 0u};
+      }
+      const int row = qb * ROWS + (int)threadIdx.x;
+      if (p.lse != nullptr && (int)threadIdx.x < ROWS && row < LQ) p.lse[lse_base + row] = -INFINITY;
+      return;
+    }
+  } else {
+    head_bases(bh, p, base, base_kv);
+  }
   // grouped-query heads: query head h reads key/value head h / (H / Hkv); Nk keys per head.
-  // Causal with Nq != Nk is bottom-right aligned: key j visible to query i iff j <= i + coff.
-  const int coff = p.Nk - p.N;
+  // Causal with Nq != Nk is bottom-right aligned: key j visible to query i iff j <= i + coff (varlen: coff may be negative).
+  const int coff = FA_NK - FA_NQ;
   const int q0 = qb * ROWS;
   const int qw0 = q0 + wave * WM;  // first query row of this wave
   const int qrow = qw0 + r;
 
-  const unsigned head_bytes = (unsigned)p.N * GRB, kv_head_bytes = (unsigned)p.Nk * GRB;
+  // (varlen: the descriptors end with the last row's D elements, so rows at or past the sequence's end read as zero whatever the pitch)
+  const unsigned head_bytes = VARLEN ? (unsigned)(LQ - 1) * qrb + GRB16 : (unsigned)p.N * GRB;
+  const unsigned kv_head_bytes = VARLEN ? (unsigned)(LK - 1) * kvrb + GRB : (unsigned)p.Nk * GRB;
   const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
       (void *)((const char *)p.q + base * GB), 0, head_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(
@@ -176,7 +224,7 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
   } else {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rq, (unsigned)qrow * GRB16 + (2 * ks + h) * 16, 0, 0);
+      const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rq, (VARLEN ? (unsigned)qrow * qrb : (unsigned)qrow * GRB16) + (2 * ks + h) * 16, 0, 0);
       qf[ks] = __builtin_bit_cast(vec8, t);
     }
   }
@@ -221,7 +269,7 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
   for (int i = 0; i < NCH; ++i) {
     const int c = tid + i * ST;
     const int row = c / GCPR, gch = c % GCPR;
-    st_g[i] = row * GRB + gch * 16;
+    st_g[i] = (VARLEN ? (int)(row * kvrb) : row * GRB) + gch * 16;
     const int skx = (D == 32) ? ((row >> 2) & 3) : (D == 64) ? ((row >> 1) & 7) : (row & 15);
     const int svx = (D == 32) ? 0 : (D == 64) ? (((row >> 1) & 1) << 2) : ((row & 3) << 2);
     const int ch = IS_FP8 ? 2 * gch : gch;
@@ -236,7 +284,7 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
     }
   }
 
-  const int kv_end = CAUSAL ? min(p.Nk, q0 + ROWS + coff) : p.Nk;
+  const int kv_end = CAUSAL ? min(FA_NK, q0 + ROWS + coff) : FA_NK;  // (varlen: >= 1 here)
   const int nT = (kv_end + BN - 1) / BN;
 
   // LDS-DMA staging (FA_MFMA_DMA): wave w of a split moves the 1-KiB pieces w, w + RW, ... of each tile; inside a piece the
@@ -250,17 +298,25 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
     const int row = wave * RPP + lane / CPRL, pc = lane % CPRL;
     const int skx = (D == 32) ? ((row >> 2) & 3) : (D == 64) ? ((row >> 1) & 7) : (row & 15);
     const int svx = (D == 32) ? 0 : (D == 64) ? (((row >> 1) & 1) << 2) : ((row & 3) << 2);
-    dma_kvo = (unsigned)(row * GRB + ((pc ^ skx) << 4));
-    dma_vvo = (unsigned)(row * GRB + ((pc ^ svx) << 4));
+    dma_kvo = VARLEN ? row * kvrb + ((pc ^ skx) << 4) : (unsigned)(row * GRB + ((pc ^ skx) << 4));
+    dma_vvo = VARLEN ? row * kvrb + ((pc ^ svx) << 4) : (unsigned)(row * GRB + ((pc ^ svx) << 4));
   }
   auto stage_dma = [&](int t, int buf) {  // tile t -> buffer buf (hipcc does not count these loads: the caller waits vmcnt(0))
 #pragma unroll
     for (int j = 0; j < NPW; ++j) {
-      const unsigned soff = (unsigned)t * GTILE + j * (RW * 1024);
+      const unsigned soff = VARLEN ? ((unsigned)t * BN + j * (RW * RPP)) * kvrb : (unsigned)t * GTILE + j * (RW * 1024);  // (dense: a piece's RPP rows are 1024 bytes)
       const unsigned lk = (unsigned)(__UINTPTR_TYPE__)Kbuf + buf * KTILE + (wave + RW * j) * 1024;
       const unsigned lv = (unsigned)(__UINTPTR_TYPE__)Vbuf + buf * TILE + (wave + RW * j) * 1024;
+      if constexpr (VARLEN) {
+        // the whole offset in voffset, i.e. inside the descriptor's range check: what follows a sequence's last key is another sequence
+        // or the end of the tensor, and both must read as zeros (the dense kernel's heads end where its descriptors end)
+        const unsigned vk = dma_kvo + soff, vv = dma_vvo + soff;
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lk), "v"(vk), "s"(rk) : "memory");
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lv), "v"(vv), "s"(rv) : "memory");
+      } else {
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lk), "v"(dma_kvo), "s"(rk), "s"(soff) : "memory");
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lv), "v"(dma_vvo), "s"(rv), "s"(soff) : "memory");
+      }
     }
   };
   // fp8 inputs: the K tile stays raw e4m3 in LDS (rows of D bytes), so IT can travel by LDS-DMA; V is widened to bf16 on the way
@@ -285,7 +341,7 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
   };
   u32x4 kst[NCH], vst[NCH];
   auto stage_load = [&](int t) {
-    const unsigned g0 = (unsigned)t * GTILE;  // tile t starts at key t*BN
+    const unsigned g0 = VARLEN ? (unsigned)t * BN * kvrb : (unsigned)t * GTILE;  // tile t starts at key t*BN
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       if constexpr (!DMA_K8) kst[i] = __builtin_amdgcn_raw_buffer_load_b128(rk, g0 + st_g[i], 0, 0);
@@ -379,7 +435,7 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
     if (need_mask) {
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
-        int lim = p.Nk - 1 - kv0 - 32 * kb - 4 * h;
+        int lim = FA_NK - 1 - kv0 - 32 * kb - 4 * h;
         if (CAUSAL) lim = min(lim, qrow + coff - kv0 - 32 * kb - 4 * h);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -492,16 +548,16 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
         }
       }
       // ---- mask (only on tiles that cross the diagonal or the end of the sequence)
-      const bool need_mask = (CAUSAL && (kv0 + BN - 1 > qw0 + coff)) || (kv0 + BN > p.Nk);
+      const bool need_mask = (CAUSAL && (kv0 + BN - 1 > qw0 + coff)) || (kv0 + BN > FA_NK);
       if (need_mask) {
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
           // masked iff key > qrow (kernels.metal:748) or key >= N. A 32 x 32 block whose every key is visible to every
           // row of the wave needs no work (wave-uniform test: of the two blocks of a diagonal tile one is of this
           // kind or entirely masked): key offsets inside the block span 0..31, the wave's rows qw0..qw0+31.
-          const int xw = min(p.Nk - 1 - kv0 - 32 * kb, CAUSAL ? qw0 + coff - kv0 - 32 * kb : 0x7fffffff);
+          const int xw = min(FA_NK - 1 - kv0 - 32 * kb, CAUSAL ? qw0 + coff - kv0 - 32 * kb : 0x7fffffff);
           if (xw >= 31) continue;
-          int lim = p.Nk - 1 - kv0 - 32 * kb - 4 * h;
+          int lim = FA_NK - 1 - kv0 - 32 * kb - 4 * h;
           if (CAUSAL) lim = min(lim, qrow + coff - kv0 - 32 * kb - 4 * h);
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
@@ -555,6 +611,10 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
           half_pair(mx, lo, hi);
           mx = fmaxf(lo, hi);
         }
+        // varlen, causal with Lk < Lq: a row that sees no key at all has every score masked. A finite floor keeps its reference
+        // finite (-inf - -inf would be a NaN in alpha and in P): its P and l stay exactly 0 and the epilogue writes O = 0, LSE = -inf.
+        // Any row with a visible key has a finite max already, so nothing changes for it.
+        if constexpr (VARLEN && CAUSAL) mx = fmaxf(mx, -3.4028234663852886e38f);
         // deferred row max (T13): O and l are rescaled only when some row's tile max exceeds the running
         // reference m by more than 2^THR (log2 domain); otherwise p = exp2(c.s - c.m) <= 2^THR with the
         // stale m. m, l and O stay mutually consistent, so LSE = m.scale + ln(l) is exact either way.
@@ -698,9 +758,22 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
       half_pair(l, lo, hi);
       l = lo + hi;
     }
-    const float inv_l = 1.0f / l;
+    // varlen: a row with no visible key (causal with Lk < Lq; an integer test, the object is built without NaN handling)
+    // (coff through an opaque copy: hipcc otherwise keeps the loop's qrow + coff alive for this one test -- a spill at 128 registers)
+    bool no_key = false;
+    if constexpr (VARLEN && CAUSAL) {
+      int coff_e = coff;
+      asm volatile("" : "+s"(coff_e));
+      no_key = qrow + coff_e < 0;
+    }
+    const float inv_l = (VARLEN && CAUSAL) ? (no_key ? 0.0f : 1.0f / l) : 1.0f / l;
+    if constexpr (VARLEN) {
+      if (p.lse != nullptr && h == 0 && qrow < LQ)
+        p.lse[lse_base + qrow] = no_key ? -INFINITY : m * 0.6931471805599453f + logf(l);
+    } else {
     if (p.lse != nullptr && h == 0 && qrow < p.N)
       p.lse[(long long)bh * p.N + qrow] = m * (PRE ? 0.6931471805599453f : p.scale) + logf(l);
+    }
 #pragma unroll
     for (int db = 0; db < DB; ++db) {
 #pragma unroll
@@ -726,11 +799,14 @@ __device__ __forceinline__ void fwd_mfma_body(const Params &p) {
       const int idx = it * 64 + lane;
       const int row = idx / CPR, ch = idx % CPR;
       const u32x4 vv = lds_read_b128(Ot + row * RB + ((ch ^ (row & (CPRL - 1))) << 4));
-      if (qw0 + row < p.N)
-        *reinterpret_cast<u32x4 *>(Og + (long long)(qw0 + row) * D + ch * 8) = vv;
+      if (qw0 + row < FA_NQ)
+        *reinterpret_cast<u32x4 *>(Og + (VARLEN ? (long long)(qw0 + row) * (long long)(qrb / 2) : (long long)(qw0 + row) * D) + ch * 8) = vv;
     }
   }
 }
+
+#undef FA_NQ
+#undef FA_NK
 
 template <typename Tag, int D, bool CAUSAL, bool PRESC>
 __global__ __launch_bounds__(NTHREADS, (main_kernel_occ4<Tag, D, PRESC>() ? 4 : D <= 64 ? 3 : D <= 128 ? 2 : 1)) void fwd_mfma_kernel(Params p) {
@@ -745,6 +821,13 @@ __global__ __launch_bounds__(2 * NTHREADS, 2) void fwd_mfma_split2_kernel(Params
 template <typename Tag, int D, bool CAUSAL>
 __global__ __launch_bounds__(NTHREADS, 2) void fwd_mfma_h64s2_kernel(Params p) {
   fwd_mfma_body<Tag, D, CAUSAL, 2, true, 64>(p);
+}
+
+// fa_fwd_varlen: the plain kernel (pre-scaled operand) in varlen mode, at the plain kernel's occupancy (head_dim 64 without the mask:
+// three workgroups per CU, see MAIN4)
+template <typename Tag, int D, bool CAUSAL>
+__global__ __launch_bounds__(NTHREADS, ((main_kernel_occ4<Tag, D, true>() && CAUSAL) ? 4 : D <= 64 ? 3 : 2)) void fwd_mfma_varlen_kernel(VarlenParams p) {
+  fwd_mfma_body<Tag, D, CAUSAL, 1, true, BM, VarlenParams>(p);
 }
 
 // ---------------------------------------------------------------------------
@@ -786,6 +869,38 @@ static hipError_t launch_one(const Params &p, hipStream_t s) {
     if (!p.exact) return launch_one_<Tag, D, CAUSAL, true>(p, s);
   }
   return launch_one_<Tag, D, CAUSAL, false>(p, s);
+}
+
+// Varlen: one block per (sequence, head, 128 rows up to max_seqlen_q) -- the host does not know the lengths; blocks past the end of
+// their sequence return at once. p.N / p.Nk hold max_seqlen_q / max_seqlen_k: the issue order (map_block) and the causal head groups
+// are those of a dense batch of B sequences of these lengths.
+template <typename Tag, int D, bool CAUSAL>
+static hipError_t launch_varlen_one(const VarlenParams &p, hipStream_t s) {
+  const int nQ = (p.N + BM - 1) / BM;
+  const size_t smem = 4 * BN * (size_t)(D * 2);  // K and V double buffers, as launch_one_
+  auto kern = fwd_mfma_varlen_kernel<Tag, D, CAUSAL>;
+  if (smem > 48 * 1024) {
+    hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem);
+    if (e != hipSuccess) return e;
+  }
+  VarlenParams pp = p;
+  pp.head_group = causal_head_group(p, D, 2);
+  set_block_divisors(pp, nQ, pp.head_group);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(kern, dim3(nQ * p.B * p.H), dim3(NTHREADS), smem, s, pp);
+  return hipGetLastError();
+}
+
+bool mfma_varlen_supported(int dtype, int D) { return (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) && (D == 64 || D == 128); }
+
+hipError_t launch_mfma_varlen(const VarlenParams &p, int dtype, hipStream_t s) {
+  auto go = [&](auto tag) -> hipError_t {
+    using Tag = decltype(tag);
+    if (p.D == 64) return p.is_causal ? launch_varlen_one<Tag, 64, true>(p, s) : launch_varlen_one<Tag, 64, false>(p, s);
+    if (p.D == 128) return p.is_causal ? launch_varlen_one<Tag, 128, true>(p, s) : launch_varlen_one<Tag, 128, false>(p, s);
+    return hipErrorInvalidValue;
+  };
+  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
 }
 
 template <typename Tag, int D, bool CAUSAL>

@@ -290,6 +290,69 @@ def flash_attention_decode_paged(
     return out, lse
 
 
+def varlen_supported(dtype: str, D: int) -> bool:
+    return bool(load_library().fa_fwd_varlen_supported(DTYPES[dtype], D))
+
+
+def flash_attention_varlen(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    cu_seqlens_k: torch.Tensor,
+    max_seqlen_q: int,
+    max_seqlen_k: int,
+    is_causal: bool = False,
+    scale: Optional[float] = None,
+    return_lse: bool = True,
+    out: Optional[torch.Tensor] = None,
+    lse: Optional[torch.Tensor] = None,
+    stream: Optional[int] = None,
+) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The forward over packed variable-length sequences (include/fa_mi355.h fa_fwd_varlen): q [total_q, Hq, D], k / v
+    [total_k, Hkv, D], f16 / bf16, D = 64 | 128. Strides are taken from the tensors: any view with unit element stride works ([H, total, D]
+    storage transposed, slices of one packed QKV projection), k and v must share theirs. cu_seqlens_q / cu_seqlens_k: contiguous int32
+    [B + 1] on q's device, read by the kernel only -- nothing here synchronises or reads device values, so the call can be captured in a
+    graph and replayed after the tables change in place (same B, totals and max_seqlen_*). Sequence b owns query tokens
+    cu_seqlens_q[b] .. cu_seqlens_q[b+1) and attends to keys cu_seqlens_k[b] .. cu_seqlens_k[b+1); causal is bottom-right aligned per
+    sequence; a row with no visible key gets O = 0 and LSE = -inf; tokens at or past cu_seqlens_q[B] and rows beyond max_seqlen_q of a
+    sequence are not written. Returns (out, lse): out like q ([total_q, Hq, D], q's strides unless `out` is given), lse [Hq, total_q]."""
+    lib = load_library()
+    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape:
+        raise ValueError(f"q [total_q,Hq,D] and k, v one [total_k,Hkv,D] shape, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
+    total_q, Hq, D = q.shape
+    total_k, Hkv, Dk = k.shape
+    if Dk != D or Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"incompatible shapes q {tuple(q.shape)} k/v {tuple(k.shape)}")
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k.dtype} {v.dtype} (f16 or bf16)")
+    if q.stride(2) != 1 or k.stride(2) != 1 or v.stride(2) != 1:
+        raise ValueError("q, k, v need a unit element stride (a head of a token is D contiguous elements)")
+    if v.stride() != k.stride():
+        raise ValueError("k and v must share row/head strides")
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if cu.dtype != torch.int32 or cu.dim() != 1 or cu.shape[0] < 2 or not cu.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 [B + 1] tensor")
+    if cu_seqlens_k.shape != cu_seqlens_q.shape:
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must both be [B + 1]")
+    B = cu_seqlens_q.shape[0] - 1
+    if not all(t.is_cuda and t.device == q.device for t in (q, k, v, cu_seqlens_q, cu_seqlens_k)):
+        raise RuntimeError("flash_attention_varlen needs q, k, v and both cu_seqlens on one device: there is no CPU path")
+    if out is None:
+        out = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device)
+    elif (not out.is_cuda or out.device != q.device or out.dtype != q.dtype or out.shape != q.shape or out.stride() != q.stride()):
+        raise ValueError("out must be a device tensor with q's dtype, shape and strides (the kernel writes it under q's strides)")
+    if lse is None:
+        lse = torch.empty((Hq, total_q), dtype=torch.float32, device=q.device) if return_lse else None
+    elif not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.shape != (Hq, total_q):
+        raise ValueError("lse must be contiguous fp32 [Hq, total_q] on q's device")
+    _call(lib, "fa_fwd_varlen",
+          (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
+           B, Hq, Hkv, total_q, total_k, int(max_seqlen_q), int(max_seqlen_k), D, _scale(scale, D), q.stride(0), q.stride(1),
+           k.stride(0), k.stride(1), int(bool(is_causal)), _TORCH2FA[q.dtype]), q.device, stream)
+    return out, lse
+
+
 def flash_attention_backward(
     q: torch.Tensor,
     k: torch.Tensor,

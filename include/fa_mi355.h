@@ -174,6 +174,39 @@ int fa_fwd_exv(const void *q, const void *k, const void *v, void *o, float *lse,
                int is_causal, int dtype, int variant, void *hip_stream);
 
 /*
+ * The forward over PACKED variable-length sequences ("varlen"; the prefill step that goes with fa_fwd_decode_paged; not in the reference):
+ * B sequences lie back to back in q / o [total_q tokens] and k / v [total_k tokens]. Token t, head h, element d of q and o sits at
+ * t * q_row_stride + h * q_head_stride + d, of k and v (one stride set for both) at t * kv_row_stride + h * kv_head_stride + d: both
+ * [total, H, D] (strides H*D, D) and [H, total, D] (strides D, total*D) work, and so do three views of one packed [total, Hq + 2*Hkv, D]
+ * QKV projection (row stride (Hq + 2*Hkv)*D, head stride D). Strides are multiples of 8 elements and at least D, bases 16-byte aligned,
+ * the element stride is 1; lse is [Hq, total_q] fp32 contiguous, or NULL. The tensors may exceed 4 GiB: a sequence's base is a 64-bit
+ * address, and only (max_seqlen + 128) * row_stride * 2 bytes must stay below 4 GiB, for q and for k / v.
+ * cu_seqlens_q / cu_seqlens_k (int32, [B + 1]) are DEVICE memory read by the kernels -- the host never reads them and the launch
+ * geometry depends on the host scalars alone (B * Hq * ceil(max_seqlen_q / 128) workgroups), so one captured graph serves any set of
+ * lengths under the same B, total_* and max_seqlen_*. Sequence b owns query tokens cu_seqlens_q[b] .. cu_seqlens_q[b+1) and keys
+ * cu_seqlens_k[b] .. cu_seqlens_k[b+1). Every table entry is clamped to [0, total], a non-increasing pair gives length 0, and the
+ * lengths Lq_b / Lk_b are clamped to max_seqlen_q / max_seqlen_k: rows of a sequence beyond that clamp and tokens at or past
+ * cu_seqlens_q[B] are not written, and a corrupt table touches nothing outside tokens [0, total) of any tensor.
+ * Per sequence the operator is exactly fa_fwd_ex on that sequence: query head h reads key/value head h / (Hq / Hkv); causal is
+ * bottom-right aligned PER SEQUENCE (key j visible to query i iff j <= i + Lk_b - Lq_b). Unlike fa_fwd_ex, Lk_b < Lq_b and Lk_b = 0 are
+ * legal (the host cannot see the lengths): a row with no visible key gets O = 0 exactly and LSE = -inf, as in fa_fwd_decode_paged.
+ * f16 / bf16, D = 64 | 128, the pre-scaled query operand of FA_VARIANT_MFMA: anything else FA_ERR_UNSUPPORTED. Tolerances are
+ * FA_VARIANT_MFMA's and "LSE accuracy" above applies unchanged; more than that, for every sequence with Lk_b >= Lq_b >= 1 (without the
+ * mask: any Lk_b >= 1, Lq_b >= 1) O and LSE are BIT-IDENTICAL to fa_fwd_exv(..., FA_VARIANT_MFMA) run on that sequence alone, whatever
+ * the strides, the other sequences or max_seqlen_* are. Null pointers (lse may be NULL), sizes < 1, Hq % Hkv != 0, scale <= 0, bad
+ * strides or alignment, max_seqlen_* > total_*, a sequence above the 4 GiB bound or a grid that does not fit an int: FA_ERR_INVALID_ARG
+ * before any launch.
+ */
+int fa_fwd_varlen(const void *q, const void *k, const void *v, void *o, float *lse,
+                  const int *cu_seqlens_q, const int *cu_seqlens_k,
+                  int B, int Hq, int Hkv, int total_q, int total_k,
+                  int max_seqlen_q, int max_seqlen_k, int D, float scale,
+                  long long q_row_stride, long long q_head_stride,
+                  long long kv_row_stride, long long kv_head_stride,
+                  int is_causal, int dtype, void *hip_stream);
+int fa_fwd_varlen_supported(int dtype, int D);
+
+/*
  * Few query rows against a long key sequence (decode steps, short chunks; scope row f3, not in the reference): the same operator as
  * fa_fwd_ex for (Hq / Hkv) * Nq <= 32, f16 / bf16 / e4m3, D = 64 | 128, laid out for the HBM roofline instead of the matrix cores -- the query
  * heads of a key/value head are packed into one row block (K and V are read once per key head), the keys are split over several
