@@ -23,8 +23,11 @@ from .ops import (  # noqa: F401
     flash_attention_decode_paged,
     flash_attention_forward,
     flash_attention_varlen,
+    flash_attention_varlen_backward,
     forward_kernel_name,
     supported,
+    varlen_backward_supported,
+    varlen_backward_workspace_bytes,
     varlen_supported,
 )
 from .shard import shard_heads  # noqa: F401

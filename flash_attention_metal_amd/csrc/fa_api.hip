@@ -31,6 +31,8 @@ int fail(int code, const char *fmt, ...) {
 //    B * Hq * Nq and B * Hkv * 256 for the decodes;
 //  - fa_fwd_varlen has row and head strides (no batch): each at least D and a multiple of 8, checked in its own lines; its size guard is
 //    (max_seqlen + 128) * row_stride * 2 < 4 GiB per sequence, for q and for k / v; its grid guard B * Hq * ceil(max_seqlen_q / 128);
+//  - fa_bwd_varlen: fa_fwd_varlen's rules, with the grid guard for both of its kernels (B * Hq * ceil(max_seqlen_q / 128) and
+//    B * Hkv * ceil(max_seqlen_k / 128));
 //  - a missing device: FA_ERR_NO_DEVICE from fa_fwd, FA_ERR_LAUNCH from every other entry point.
 #define TRY(check) do { if (const int st_ = (check)) return st_; } while (0)
 
@@ -60,6 +62,13 @@ int strides_ok(const char *fn, const char *what, int N, int D, long long bs, lon
   if (hs < (long long)N * D || bs < 0 || (batch_over_head && bs < hs) || (bs % mult) || (hs % mult))
     return fail(FA_ERR_INVALID_ARG, "%s: bad %sstrides (batch %lld, head %lld): a head holds %lld elements, strides are multiples of %d",
                 fn, what, bs, hs, (long long)N * D, mult);
+  return FA_OK;
+}
+// one packed [total, H, D] operand of the varlen entry points under (row, head) element strides: rows and heads may interleave either
+// way, so all that is required of a stride is room for one row and 16-byte alignment of every row
+int varlen_strides_ok(const char *fn, const char *what, int D, long long rs, long long hs, int mult) {
+  if (rs < D || hs < D || (rs % mult) || (hs % mult))
+    return fail(FA_ERR_INVALID_ARG, "%s: bad %sstrides (row %lld, head %lld): a row holds %d elements, strides are multiples of %d", fn, what, rs, hs, D, mult);
   return FA_OK;
 }
 int aligned16(const char *fn, const char *what, std::initializer_list<const void *> ptrs) {
@@ -361,13 +370,8 @@ int fa_fwd_varlen(const void *q, const void *k, const void *v, void *o, float *l
     return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen: max_seqlen (%d, %d) exceeds the token count (%d, %d)", max_seqlen_q, max_seqlen_k, total_q, total_k);
   // a token's head is D contiguous elements; rows and heads may interleave either way ([total, H, D], [H, total, D], views of a packed
   // QKV projection), so all that is required of a stride is room for one row and 16-byte alignment of every row
-  const int mult = stride_mult(dtype);
-  if (q_row_stride < D || q_head_stride < D || (q_row_stride % mult) || (q_head_stride % mult))
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen: bad strides (row %lld, head %lld): a row holds %d elements, strides are multiples of %d", q_row_stride,
-                q_head_stride, D, mult);
-  if (kv_row_stride < D || kv_head_stride < D || (kv_row_stride % mult) || (kv_head_stride % mult))
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen: bad key/value strides (row %lld, head %lld): a row holds %d elements, strides are multiples of %d",
-                kv_row_stride, kv_head_stride, D, mult);
+  TRY(varlen_strides_ok(fn, "", D, q_row_stride, q_head_stride, stride_mult(dtype)));
+  TRY(varlen_strides_ok(fn, "key/value ", D, kv_row_stride, kv_head_stride, stride_mult(dtype)));
   TRY(aligned16(fn, "tensors", {q, k, v, o}));
   if (((uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen: cu_seqlens_q / cu_seqlens_k must be int32-aligned");
   // 32-bit byte offsets inside ONE sequence of one head (its base is a 64-bit address: the tensors themselves may exceed 4 GiB); as in
@@ -568,6 +572,38 @@ int fa_bwd_ex(const void *q, const void *k, const void *v, const void *o, const 
               int is_causal, int dtype, void *hip_stream) {
   return bwd_impl("fa_bwd_ex", q, k, v, o, d_o, lse, dq, dk, dv, workspace, B, Hq, Hkv, Nq, Nk, D, scale, q_batch_stride,
                   q_head_stride, kv_batch_stride, kv_head_stride, is_causal, dtype, hip_stream);
+}
+
+long long fa_bwd_varlen_workspace_bytes(int Hq, int total_q) { return Hq < 1 || total_q < 1 ? 0 : (long long)Hq * total_q * 4; }
+int fa_bwd_varlen_supported(int dtype, int D) { return fa::bwd_varlen_supported(dtype, D); }
+int fa_bwd_varlen(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq, float *dk,
+                  float *dv, void *workspace, const int *cu_seqlens_q, const int *cu_seqlens_k, int B, int Hq, int Hkv, int total_q,
+                  int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale, long long q_row_stride, long long q_head_stride,
+                  long long kv_row_stride, long long kv_head_stride, int is_causal, int dtype, void *hip_stream) {
+  g_err[0] = 0;
+  const char *fn = "fa_bwd_varlen";
+  TRY(nonnull(fn, {q, k, v, o, d_o, lse, dq, dk, dv, workspace, cu_seqlens_q, cu_seqlens_k}));
+  TRY(positive(fn, {B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D}));
+  TRY(grouped(fn, Hq, Hkv));
+  TRY(scale_ok(fn, scale));
+  if (!fa_bwd_varlen_supported(dtype, D))
+    return fail(FA_ERR_UNSUPPORTED, "fa_bwd_varlen: needs f16 / bf16 and D = 64 | 128, got dtype=%s D=%d", fa_dtype_name(dtype), D);
+  if (max_seqlen_q > total_q || max_seqlen_k > total_k)
+    return fail(FA_ERR_INVALID_ARG, "fa_bwd_varlen: max_seqlen (%d, %d) exceeds the token count (%d, %d)", max_seqlen_q, max_seqlen_k, total_q, total_k);
+  TRY(varlen_strides_ok(fn, "", D, q_row_stride, q_head_stride, stride_mult(dtype)));
+  TRY(varlen_strides_ok(fn, "key/value ", D, kv_row_stride, kv_head_stride, stride_mult(dtype)));
+  TRY(aligned16(fn, "tensors", {q, k, v, o, d_o, dq, dk, dv}));
+  if (((uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "fa_bwd_varlen: cu_seqlens_q / cu_seqlens_k must be int32-aligned");
+  if (((uintptr_t)lse | (uintptr_t)workspace) & 3) return fail(FA_ERR_INVALID_ARG, "fa_bwd_varlen: lse / workspace must be fp32-aligned");
+  // as fa_fwd_varlen: 32-bit byte offsets inside ONE sequence of one head of the 16-bit tensors (the gradients are stored through 64-bit
+  // addresses), and the staging may address up to two 64-row tiles past its end
+  TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
+  TRY(head_fits(fn, (double)(max_seqlen_k + 128) * (double)kv_row_stride * 2, 4, " (one sequence of max_seqlen_k rows)"));
+  TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));   // the dQ kernel's
+  TRY(grid_fits(fn, (long long)B * Hkv, max_seqlen_k));  // the dK/dV kernel's
+  return launched(fn, fa::launch_bwd_varlen(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv,
+                                            total_q, total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride,
+                                            kv_row_stride, kv_head_stride, is_causal ? 1 : 0, dtype, (hipStream_t)hip_stream));
 }
 
 }  // extern "C"

@@ -119,6 +119,12 @@ hipError_t launch_widen_e4m3(const void *in, void *out, long long n, hipStream_t
 hipError_t launch_bwd(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse,
                       float *dq, float *dk, float *dv, float *ws, int B, int H, int Hkv, int N, int Nk, int D, float scale,
                       long long bs, long long hs, long long kv_bs, long long kv_hs, int causal, int dtype, hipStream_t s);
+// fa_bwd_varlen (csrc/fa_bwd_varlen_kernels.hip): max_q / max_k size the grids, the cu tables are device memory
+bool bwd_varlen_supported(int dtype, int D);
+hipError_t launch_bwd_varlen(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq,
+                             float *dk, float *dv, float *ws, const int *cu_q, const int *cu_k, int B, int H, int Hkv, int total_q,
+                             int total_k, int max_q, int max_k, int D, float scale, long long q_rs, long long q_hs, long long kv_rs,
+                             long long kv_hs, int causal, int dtype, hipStream_t s);
 
 // ---- host-side launch helper shared by every kernel file that needs more than 48 KiB of dynamic LDS
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device) instead of on every launch.

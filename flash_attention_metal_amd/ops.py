@@ -353,6 +353,88 @@ def flash_attention_varlen(
     return out, lse
 
 
+def varlen_backward_supported(dtype: str, D: int) -> bool:
+    return bool(load_library().fa_bwd_varlen_supported(DTYPES[dtype], D))
+
+
+def varlen_backward_workspace_bytes(Hq: int, total_q: int) -> int:
+    return int(load_library().fa_bwd_varlen_workspace_bytes(Hq, total_q))
+
+
+def flash_attention_varlen_backward(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    o: torch.Tensor,
+    d_o: torch.Tensor,
+    lse: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    cu_seqlens_k: torch.Tensor,
+    max_seqlen_q: int,
+    max_seqlen_k: int,
+    is_causal: bool = False,
+    scale: Optional[float] = None,
+    dq: Optional[torch.Tensor] = None,
+    dk: Optional[torch.Tensor] = None,
+    dv: Optional[torch.Tensor] = None,
+    workspace: Optional[torch.Tensor] = None,
+    stream: Optional[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The backward over packed variable-length sequences (include/fa_mi355.h fa_bwd_varlen), the counterpart of
+    flash_attention_varlen: q, o, d_o [total_q, Hq, D] under one set of strides, k, v [total_k, Hkv, D] under another, f16 / bf16,
+    D = 64 | 128; lse the forward's [Hq, total_q]; the tables as in flash_attention_varlen. Returns (dq, dk, dv) in fp32 under the
+    ELEMENT strides of q / k (allocated so unless given: three views of one fp32 [total, Hq + 2*Hkv, D] buffer serve a packed QKV
+    projection). Only tokens owned by a sequence are written (allocate with zeros if the rest is read); a query row without a visible
+    key gets dQ = 0 and adds nothing to dK / dV. With dq, dk, dv and `workspace` (uint8, at least
+    varlen_backward_workspace_bytes(Hq, total_q) bytes) given the call allocates nothing, and it never synchronises or reads a device
+    value: it can be captured in a graph and replayed after the tables change in place."""
+    lib = load_library()
+    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or o.shape != q.shape or d_o.shape != q.shape:
+        raise ValueError(f"q, o, d_o one [total_q,Hq,D] shape and k, v one [total_k,Hkv,D] shape, got {tuple(q.shape)} {tuple(o.shape)} "
+                         f"{tuple(d_o.shape)} {tuple(k.shape)} {tuple(v.shape)}")
+    total_q, Hq, D = q.shape
+    total_k, Hkv, Dk = k.shape
+    if Dk != D or Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"incompatible shapes q {tuple(q.shape)} k/v {tuple(k.shape)}")
+    if q.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q.dtype for t in (k, v, o, d_o)):
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k.dtype} {v.dtype} {o.dtype} {d_o.dtype} (f16 or bf16)")
+    if q.stride(2) != 1 or k.stride(2) != 1:
+        raise ValueError("q, k, v need a unit element stride (a head of a token is D contiguous elements)")
+    if o.stride() != q.stride() or d_o.stride() != q.stride():
+        raise ValueError("q, o and d_o must share row/head strides")
+    if v.stride() != k.stride():
+        raise ValueError("k and v must share row/head strides")
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if cu.dtype != torch.int32 or cu.dim() != 1 or cu.shape[0] < 2 or not cu.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 [B + 1] tensor")
+    if cu_seqlens_k.shape != cu_seqlens_q.shape:
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must both be [B + 1]")
+    B = cu_seqlens_q.shape[0] - 1
+    if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.shape != (Hq, total_q):
+        raise ValueError("lse must be contiguous fp32 [Hq, total_q]")
+    if not all(t.is_cuda and t.device == q.device for t in (q, k, v, o, d_o, lse, cu_seqlens_q, cu_seqlens_k)):
+        raise RuntimeError("flash_attention_varlen_backward needs every tensor and both cu_seqlens on one device: there is no CPU path")
+    grads = []
+    for name, g, like in (("dq", dq, q), ("dk", dk, k), ("dv", dv, k)):
+        if g is None:
+            g = torch.empty_strided(like.shape, like.stride(), dtype=torch.float32, device=q.device)
+        elif not g.is_cuda or g.device != q.device or g.dtype != torch.float32 or g.shape != like.shape or g.stride() != like.stride():
+            raise ValueError(f"{name} must be an fp32 device tensor with the shape and element strides of {'q' if like is q else 'k'} "
+                             "(the kernels write it under those strides)")
+        grads.append(g)
+    dq, dk, dv = grads
+    need = varlen_backward_workspace_bytes(Hq, total_q)
+    ws = _workspace(workspace, need, q.device)
+    if ws.numel() < need:
+        raise ValueError(f"workspace of {ws.numel()} bytes, varlen_backward_workspace_bytes() asks for {need}")
+    _call(lib, "fa_bwd_varlen",
+          (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+           dv.data_ptr(), ws.data_ptr(), cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), B, Hq, Hkv, total_q, total_k,
+           int(max_seqlen_q), int(max_seqlen_k), D, _scale(scale, D), q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+           int(bool(is_causal)), _TORCH2FA[q.dtype]), q.device, stream)
+    return dq, dk, dv
+
+
 def flash_attention_backward(
     q: torch.Tensor,
     k: torch.Tensor,

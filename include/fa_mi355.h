@@ -318,6 +318,40 @@ int fa_bwd_supported(int dtype, int D);
 /* algorithmic FLOPs of one fa_bwd call: 2.5x the forward (five N x N x D products) */
 double fa_bwd_algorithmic_flops(int B, int H, int N, int D, int is_causal);
 
+/*
+ * The backward over PACKED variable-length sequences: the counterpart of fa_fwd_varlen, per sequence exactly fa_bwd_ex (not in the
+ * reference). Layout, tables and clamping are fa_fwd_varlen's: q, o, d_o (16-bit) and dq (fp32) share the q ELEMENT strides -- token t,
+ * head h, element d at t * q_row_stride + h * q_head_stride + d --, k, v (16-bit) and dk, dv (fp32) the kv element strides, so the
+ * fp32 gradient of three views of one packed [total, Hq + 2*Hkv, D] QKV projection is three views of one fp32 buffer of that shape.
+ * lse is the forward's [Hq, total_q] fp32. Strides are multiples of 8 elements and at least D, bases 16-byte aligned. The tensors may
+ * exceed 4 GiB (gradients are stored through 64-bit addresses); only (max_seqlen + 128) * row_stride * 2 bytes must stay below 4 GiB,
+ * for q and for k / v. `workspace`: caller-owned device memory of fa_bwd_varlen_workspace_bytes(Hq, total_q) bytes (delta, [Hq, total_q]
+ * fp32; 0 for invalid sizes), contents irrelevant before the call. The size cannot be seen from the pointer: the caller answers for it.
+ * cu_seqlens_q / cu_seqlens_k (int32, [B + 1]) are DEVICE memory read by the kernels -- the host never reads them; the grids are
+ * B * Hq * ceil(max_seqlen_q / 128) workgroups for dQ and B * Hkv * ceil(max_seqlen_k / 128) for dK / dV, so one captured graph serves
+ * any set of lengths under the same scalars. Table entries and lengths are clamped exactly as in fa_fwd_varlen, and a corrupt table
+ * touches nothing outside tokens [0, total) of any tensor.
+ * What is written: the dQ row of every query token owned by a sequence and the dK and dV rows of every key token owned by a sequence
+ * (zeros when no query sees the key, e.g. Lq_b = 0). Tokens owned by nobody -- at or past cu_seqlens[B], or beyond the max_seqlen clamp
+ * of their sequence -- are not written, and neither are bytes between heads or rows under wide strides.
+ * A query row without a visible key (Lk_b = 0, or causal with i + Lk_b - Lq_b < 0; the forward gave it O = 0 and LSE = -inf) gets
+ * dQ = 0 exactly and contributes exactly nothing to dK / dV; it is recognised by the forward's integer test, never by its LSE.
+ * Results do not depend on the workspace's prior contents and are bitwise reproducible. For every sequence with Lk_b >= Lq_b >= 1
+ * (without the mask: any Lq_b, Lk_b >= 1) dQ, dK, dV are BIT-IDENTICAL to fa_bwd_ex run on that sequence alone, whatever the strides,
+ * the other sequences or max_seqlen_* are; "Backward accuracy" above applies per sequence.
+ * f16 / bf16, D = 64 | 128: anything else FA_ERR_UNSUPPORTED. Null pointers, sizes < 1, Hq % Hkv != 0, scale <= 0, bad strides or
+ * alignment, max_seqlen_* > total_*, a sequence above the 4 GiB bound or a grid that does not fit an int: FA_ERR_INVALID_ARG before any
+ * launch.
+ */
+int fa_bwd_varlen(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse,
+                  float *dq, float *dk, float *dv, void *workspace,
+                  const int *cu_seqlens_q, const int *cu_seqlens_k,
+                  int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
+                  long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
+                  int is_causal, int dtype, void *hip_stream);
+long long fa_bwd_varlen_workspace_bytes(int Hq, int total_q);
+int fa_bwd_varlen_supported(int dtype, int D);
+
 /* 1 if fa_fwd has a kernel for the combination, else 0 (no GPU needed). */
 int fa_supported(int dtype, int variant, int D);
 
