@@ -130,6 +130,33 @@ def test_decode_known_answers_and_workspace(fa, oracle_mod):
                 assert np.array_equal(col, np.zeros(Hq, np.float32)), (t, iq)
             assert np.abs(lse[0, :, iq].cpu().numpy() - np.log(vis)).max() < 1e-5
         assert np.count_nonzero(o[..., 1:].float().cpu().numpy()) == 0
+    # the same at S = 65 and S = 256 (an uneven partition under the cap, a ragged last tile): t is the first and the last key of the
+    # splits on both sides of every 64-split lane slot of the combine, and the four keys the causal mask cuts through
+    import decode_range as dr
+
+    for nk in (16704, 70001):
+        S = dr.splits_of(fa, B, Hq, Hkv, Nq, nk, D)
+        assert S == dr.S_OF_NK[nk], (nk, S)
+        print(f"known answers at Nk={nk}: S={S}")
+        t0, t1 = dr.split_tiles(nk, S)
+        ts = sorted({int(x) for s_ in (0, 63, 64, 127, 128, 191, 192, S - 1) if s_ < S for x in (t0[s_] * 64, min(t1[s_] * 64, nk) - 1)}
+                    | {nk - 4, nk - 3, nk - 2, nk - 1})
+        kk = torch.randn(B, Hkv, nk, D, dtype=torch.bfloat16, device="cuda")
+        wsn = torch.empty(fa.decode_workspace_bytes(B, Hq, Hkv, Nq, nk, D), dtype=torch.uint8, device="cuda")
+        vv = torch.zeros(B, Hkv, nk, D, dtype=torch.bfloat16, device="cuda")
+        vis = nk - Nq + np.arange(Nq) + 1
+        want = oracle_mod.round_to((1.0 / vis).astype(np.float32), "bf16")
+        for t in ts:
+            vv[:, :, t, 0] = 1.0
+            wsn.fill_(0xFF)
+            o, lse = fa.flash_attention_decode(q, kk, vv, is_causal=True, workspace=wsn)
+            on, ln = o.float().cpu().numpy(), lse.cpu().numpy()
+            vv[:, :, t, 0] = 0.0
+            seen = t < vis
+            col = on[0, :, :, 0]
+            assert np.all(np.abs(col - want)[:, seen] <= 8e-3 * want[seen]), (nk, t, col)
+            assert np.count_nonzero(col[:, ~seen]) == 0 and np.count_nonzero(on[..., 1:]) == 0, (nk, t)
+            assert (np.abs(ln[0] - np.log(vis)) < 1e-5 + 4 * 2.0 ** -23 * np.log(vis)).all(), (nk, t, ln[0] - np.log(vis))
     # deterministic bit for bit, and independent of what the workspace held
     v = torch.randn(B, Hkv, Nk, D, dtype=torch.bfloat16, device="cuda")
     qq = torch.randn(B, Hq, Nq, D, dtype=torch.bfloat16, device="cuda")

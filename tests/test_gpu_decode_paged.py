@@ -132,7 +132,9 @@ def test_paged_full_cache_is_bit_identical_to_dense_decode(fa, oracle_mod, layou
     rng = np.random.default_rng(7)
     for (qdt, kvdt) in (("f16", "f16"), ("bf16", "bf16"), ("fp8", "fp8"), ("bf16", "fp8")):
         for (B, Hq, Hkv, Nq, D, causal, P, mp) in ((3, 16, 4, 2, 128, True, 16, 64), (2, 32, 8, 1, 64, False, 64, 40),
-                                                    (2, 8, 2, 4, 64, True, 256, 5)):
+                                                    (2, 8, 2, 4, 64, True, 256, 5),
+                                                    # 65536 keys on B * Hkv = 2: 256 key splits (tests/decode_range.py S_OF_NK)
+                                                    (1, 8, 2, 1, 64, False, 16, 4096), (1, 8, 2, 4, 128, True, 256, 256)):
             cap = P * mp
             amp = 2.0 if kvdt == "fp8" else 1.0
             q = oracle_mod.round_to(amp * rng.uniform(-1.0, 1.0, (B, Hq, Nq, D)).astype(np.float32), qdt)
