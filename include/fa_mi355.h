@@ -290,6 +290,20 @@ int fa_fwd_decode_paged_supported(int q_dtype, int kv_dtype, int D, int Hq, int 
  * subnormal f16 operands, nothing is flushed to zero -- so a d_o of order 2^-8 and less (f16 training without loss scaling), where
  * every dS is subnormal, still gives dQ / dK within the bound above (test_rows_small_d_o), at the absolute resolution 2^-25 per
  * (query, key) pair instead of 11 bits; below about 2^-24 / P_ij a dS is rounded to zero, as f16 itself would. e4m3 inputs: u = 2^-8.
+ * On the forward's own O and LSE -- what training and torch.ops.fa_mi355 feed it -- the bound above reads "the exact O rounded to the
+ * type, the exact LSE" as two substitutions. With lse_err_i >= |lse_i - exact| and o_err_id >= |O_id - exact| of the forward route that
+ * wrote them: d_ij becomes d_ij + lse_err_i (every P of row i moves by exp(-+lse_err_i)), and u sum_d |dO_id O_id| becomes
+ * sum_d |dO_id| o_err_id (delta moves by sum_d dO_id (O_id - exact)). The forward terms, per route ("LSE accuracy" / "fp8 probabilities"
+ * above): lse_err_i = 1e-4, + eps * scale * |q_i|_2 * max_j |k_j|_2 for the pre-scaled kernels, + 2^-8 (bf16) / 2^-11 (f16) for
+ * FA_VARIANT_MFMA16 (+ n * 2^-22 for n low probabilities of an f16 row), + ln(1 + 2^-4) for FA_VARIANT_MFMA_FP8PV;
+ *     o_err_id = u_out |O_id| + (u_p + u_l + expm1(2 max_j d_ij) + 2^-24 (visible keys + tiles)) * sum_j P_ij |v_jd|
+ * with u_p the rounding of a probability into the PV product (u; 2^-4 for FA_VARIANT_MFMA_FP8PV), u_l = u_p where the row sum adds the
+ * rounded probabilities (FA_VARIANT_MFMA16, _FP8PV) and 0 otherwise, the d_ij term for the pre-scaled kernels only, and
+ * 2 (S + 3) 2^-24 sum_j P_ij |v_jd| more where S key splits are merged. Judged as a function of the six tensors it is handed, whatever
+ * wrote them, the backward is within the bound above with P^_ij = exp(scale s_ij - lse_i) and dS^ = P^ o (dP - sum_d dO o) for P and dS
+ * and without the u sum_d |dO_id O_id| term. tests/chain_bound.py spells out the forward terms, tests/test_chain_bound_model.py checks
+ * them on a model of the kernels' arithmetic, tests/test_gpu_chain.py holds every element of dQ, dK, dV to both bounds on the chains
+ * fa_fwd -> fa_bwd, fa_fwd_exv -> fa_bwd_ex, the torch op under autograd and e4m3 inputs.
  */
 int fa_bwd(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse,
            float *dq, float *dk, float *dv, void *workspace,

@@ -293,21 +293,21 @@ def ratios(case, ref, o, lse, split=0, shift=0.0):
 
 
 # ---- an fp32 model of the kernels' online softmax (CPU tests) ----------------------------------------------------------------
-def model_head(case, b, h, p_dtype, out_dtype, thr=8.0, splits=1, interleave=True, shift=0.0, rng=None):
-    """All rows of one head through an fp32 online softmax as the kernels run it: 64-key tiles; a reference that is renewed only when a
-    score passes it by more than `thr` (and sits `shift` from the maximum it was set from); P rounded to `p_dtype` for the PV product
-    (the row sum adds the fp32 P, or the rounded ones with e4m3); `splits` partial results over interleaved (even / odd) or contiguous
-    tile sets, merged by their references; keys of a tile added in a shuffled order. Returns (O rounded to out_dtype, LSE) in fp32."""
+def model_arrays(q, k, v, vis, c2, in_dtype, p_dtype, out_dtype, thr=8.0, splits=1, interleave=True, shift=0.0, rng=None, prescaled=True,
+                 sum_rounded=None):
+    """One head through an fp32 online softmax as the kernels run it, on plain arrays: q [Nq, D], k / v [Nk, D] (fp32 values of
+    `in_dtype`), vis [Nq, Nk] bool, c2 = c2_of(scale). 64-key tiles; a reference that is renewed only when a score passes it by more than
+    `thr` (and sits `shift` from the maximum it was set from); P rounded to `p_dtype` for the PV product; the row sum adds the fp32 P, or
+    the rounded ones (`sum_rounded`; default: with e4m3 probabilities); `splits` partial results over interleaved (even / odd) or
+    contiguous tile sets, merged by their references; keys of a tile added in a shuffled order; the query operand pre-scaled by c2 and
+    rounded to `in_dtype` once (`prescaled`), or every score scaled in fp32. Returns (O rounded to out_dtype, LSE) in fp32."""
     f32 = np.float32
-    G = case.q.shape[1] // case.k.shape[1]
-    hk = h // G
-    Nq, D = case.q.shape[2], case.q.shape[3]
-    Nk = case.k.shape[2]
-    rows = np.arange(Nq)
-    vis = visible(case, b, rows)
-    c2 = c2_of(case.scale)
-    qs = round_to((case.q[b, h] * c2).astype(f32), {"fp8": "fp8"}.get(case.dtype, case.dtype))  # the pre-scaled operand
-    nt = tiles_of(case)
+    Nq, D = q.shape
+    Nk = k.shape[0]
+    if sum_rounded is None:
+        sum_rounded = p_dtype == "fp8"
+    qs = round_to((q * c2).astype(f32), in_dtype) if prescaled else np.asarray(q, f32)
+    nt = (Nk + TILE - 1) // TILE
     owner = (np.arange(nt) % splits) if interleave else (np.arange(nt) * splits // nt)
     parts = []
     for sp in range(splits):
@@ -318,7 +318,9 @@ def model_head(case, b, h, p_dtype, out_dtype, thr=8.0, splits=1, interleave=Tru
             keys = np.arange(t * TILE, min(Nk, (t + 1) * TILE))
             if rng is not None:
                 keys = rng.permutation(keys)
-            s = (qs @ case.k[b, hk, keys].T).astype(f32)
+            s = (qs @ k[keys].T).astype(f32)
+            if not prescaled:
+                s = (s * c2).astype(f32)
             s = np.where(vis[:, keys], s, f32(-np.inf))
             mx = s.max(1)
             renew = np.isfinite(mx) & (np.isneginf(mref) | (mx > mref - f32(shift) + f32(thr)))
@@ -331,8 +333,8 @@ def model_head(case, b, h, p_dtype, out_dtype, thr=8.0, splits=1, interleave=Tru
             with np.errstate(invalid="ignore"):
                 p = np.where(np.isfinite(s), np.exp2(s - mref[:, None]), 0).astype(f32)
             pr = round_to(p, p_dtype)
-            l = (l + (pr if p_dtype == "fp8" else p).sum(1, dtype=f32)).astype(f32)
-            acc = (acc + (pr @ case.v[b, hk, keys]).astype(f32)).astype(f32)
+            l = (l + (pr if sum_rounded else p).sum(1, dtype=f32)).astype(f32)
+            acc = (acc + (pr @ v[keys]).astype(f32)).astype(f32)
         parts.append((mref, l, acc))
     M = np.max([p[0] for p in parts], axis=0)
     lt = np.zeros(Nq, f32)
@@ -348,6 +350,15 @@ def model_head(case, b, h, p_dtype, out_dtype, thr=8.0, splits=1, interleave=Tru
     with np.errstate(divide="ignore", invalid="ignore"):
         lse = np.where(some, ((M + np.log2(lt).astype(f32)) * LN2_F32), f32(-np.inf)).astype(f32)
     return o, lse
+
+
+def model_head(case, b, h, p_dtype, out_dtype, thr=8.0, splits=1, interleave=True, shift=0.0, rng=None):
+    """All rows of one head of a case through model_arrays (the pre-scaled operand; the row sum adds the fp32 P, or the rounded ones with
+    e4m3). Returns (O rounded to out_dtype, LSE) in fp32."""
+    hk = h // (case.q.shape[1] // case.k.shape[1])
+    vis = visible(case, b, np.arange(case.q.shape[2]))
+    return model_arrays(case.q[b, h], case.k[b, hk], case.v[b, hk], vis, c2_of(case.scale), {"fp8": "fp8"}.get(case.dtype, case.dtype), p_dtype,
+                        out_dtype, thr, splits, interleave, shift, rng)
 
 
 # ---- the catalogue: every case the GPU tests run, and the CPU tests check (one list, no copy) --------------------------------------
