@@ -14,8 +14,12 @@
 //     per 64-key tile; row max / row sum are in-register reductions, the four lanes of a row (g = 0..3) meet only on the
 //     rare exact path and in the epilogue
 //   * pre-scaled query operand Q~ = round(scale.log2e.Q) and the running reference -m as the C operand of the first MFMA
-//     of every score chain (4 registers per query tile instead of 16): P = exp2(S') with no FMA; the row sums decide
-//     whether m is stale (sum-triggered deferred max, threshold 2^8) exactly as in fa_mfma_kernel.hip
+//     of every score chain (4 registers per query tile instead of 16): P = exp2(S') with no FMA. f16: the packed probabilities'
+//     exponent bits decide per tile whether m is stale (threshold 2^4; bf16 at head_dim 128: 2^8), and a stale tile is done again on the
+//     true maxima. bf16 at head_dim 64 and its padded head dims (LAZY):
+//     no per-tile test -- bf16 P' keeps its 8 bits at any scale, so a stale m loses nothing; the row sums the matrix core delivers are
+//     looked at one tile later (one compare), a sum of 2^20 and more takes an exact power of two out of O, the sum and m, and a sum that
+//     left the trusted range (2^64 and more, inf, NaN) makes the workgroup run once more on the exact path (slow mode)
 //   * P^T feeds PV straight from the score registers: the B operand's k index (8g + j) is key 16(j >> 2) + 4g + (j & 3) of a
 //     32-key step, and V^T is read with ds_read_b64_tr_b16 in the same order (V stays row-major in HBM and LDS)
 //   * K/V tiles of 64 keys double-buffered in LDS, global -> LDS by LDS-DMA with the chunk swizzle on the source address;
@@ -45,6 +49,16 @@
 #define FA16_ONES 1  // 1: the row sums come out of the matrix core (a fifth "d tile" of ones in the PV product: +4 MFMAs per 64-key tile) and
                      // the staleness test reads the exponent bits of the packed probabilities (8 v_or3 instead of 32 v_add): the loop is
                      // VALU-issue-bound with the matrix pipe half idle, so VALU is traded for MFMA; 0: row sums by v_add, tested against 2^THR
+#endif
+#ifndef FA16_LAZY
+#define FA16_LAZY 1  // bf16 at head_dim 64 with FA16_ONES: 1 = the reference is renewed lazily from the row sums of the PREVIOUS tile (see tile()); 0 = the per-tile
+                     // test of the packed exponent bits, as f16; 2 = no test at all (TIMING ONLY, the ceiling of 1: wrong for rows that rise)
+#endif
+#ifndef FA16_LAZY_THR
+#define FA16_LAZY_THR 0x1p20f  // LAZY: a row whose sum reached this is renormalised by an exact power of two in front of the next tile
+#endif
+#ifndef FA16_LAZY_POISON
+#define FA16_LAZY_POISON 0x1p64f  // LAZY: a row sum at or above this (inf and NaN included) is not trusted: the block runs again in slow mode
 #endif
 #ifndef FA16_HALVES
 #define FA16_HALVES 0  // 1: the hot pass works on one 32-key half at a time (16 live score registers instead of 32)
@@ -194,6 +208,15 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) oacc[dt][qt][i] = 0.0f;
   constexpr bool ONES = (FA16_ONES != 0);
+  // LAZY (bf16 only): no staleness test in the hot pass at all. bf16 probabilities carry fp32's exponent range, so P' = exp2(S - m) keeps its
+  // 8 bits at ANY scale and O / the row sums are fp32: a stale reference loses nothing, it only has to be corrected before something
+  // overflows -- from the row sums the matrix core has already delivered, one tile later (tile()). f16 P' has 5 exponent bits: not for it.
+  // Head_dim 64 only: head_dim 128 is bound by the matrix pipe, not by the vector-issue port, and measured 0.6 % SLOWER without the test
+  // (config 4 shard, profiles/r11/ab_lazy.log) -- it keeps the per-tile test.
+  constexpr bool LAZY = ONES && std::is_same<Tag, BF16>::value && D == 64 && (FA16_LAZY != 0);
+  constexpr bool LAZY_TEST = LAZY && (FA16_LAZY == 1);
+  lds_char *poison_flag = smem + 4 * SUB * TILE;  // LAZY: one word behind the K / V buffers, the workgroup's OR of the waves' poison flags
+  int slow = 0;    // LAZY, wave-uniform: this is the block's second run -- every tile takes the exact path (true maxima) before its hot pass
   // ONES: probabilities are formed against a reference BIAS log2 units ABOVE the row maximum found when the reference was last set
   // (P' = P / 2^BIAS <= 2^-BIAS then), so that "some score has since risen THR = BIAS + 1 above that maximum" reads "some P' >= 2",
   // i.e. "the top exponent bit of some packed P' is set" -- an OR over the 16 packed registers instead of 32 additions. bf16 keeps
@@ -222,6 +245,9 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
     asm volatile("" : "+v"(negm[qt]));  // opaque: else hipcc re-materialises the splat in front of every MFMA
   }
 
+  if constexpr (LAZY_TEST) {
+    if (threadIdx.x == 0) lds_write_b32(poison_flag, 0u);
+  }
   stage_dma(0, 0);
   if constexpr (SUB == 2) {
     if (1 < nT) stage_dma(1, 1);
@@ -290,18 +316,23 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
       for (int qt = 0; qt < 2; ++qt) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) pf[K0 / 2 + kp][qt][j] = (elem)s[2 * kp + (j >> 2)][qt][j & 3];
-        if constexpr (ONES) {
+        if constexpr (ONES && !LAZY) {
           const u32x4 w = __builtin_bit_cast(u32x4, pf[K0 / 2 + kp][qt]);
           bits |= w[0] | w[1] | w[2] | w[3];
         }
       }
   };
   // the hot pass over NKT key tiles: P = exp2(S') -> pf (and `bits`, or the row sums ls)
-  auto hot_group = [&](auto bufc, auto k0c, auto nktc, const int kv0, vec8 (&pf)[NKP][2], unsigned &bits,
-                       float (&ls)[2]) __attribute__((always_inline)) {
+  // (LAZY, `leave`: slow mode's way into the exact path -- the pass is left behind its score MFMAs, where the mask's branch already
+  // parts the code, and the tile comes back after the true maxima; returns true then)
+  auto hot_group = [&](auto bufc, auto k0c, auto nktc, const int kv0, vec8 (&pf)[NKP][2], unsigned &bits, float (&ls)[2],
+                       const bool leave) __attribute__((always_inline)) -> bool {
     constexpr int NKT = decltype(nktc)::value;
     f32x4 s[NKT][2];
     score_group(bufc, k0c, s, negm[0], negm[1]);
+    if constexpr (LAZY_TEST) {
+      if (__builtin_expect(leave, 0)) return true;
+    }
     if (needs_mask(kv0)) apply_mask(k0c, s, kv0);
 #if FA16_PRIO
     if constexpr (decltype(k0c)::value + NKT == KT) __builtin_amdgcn_s_setprio(0);
@@ -316,6 +347,7 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
           if constexpr (!ONES) ls[qt] = (decltype(k0c)::value == 0 && k2 == 0 && i == 0) ? s[k2][qt][i] : ls[qt] + s[k2][qt][i];
         }
     pack_group(k0c, s, pf, bits);
+    return false;
   };
   // the row maxima of the raw scores of NKT key tiles, into mx[qt] (this lane's keys)
   auto max_group = [&](auto bufc, auto k0c, auto nktc, const int kv0, float (&mx)[2]) __attribute__((always_inline)) {
@@ -357,6 +389,39 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
       for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int i = 0; i < 4; ++i) oacc[dt][qt][i] *= alpha;
+    }
+  };
+  // LAZY: the row sums as they stand (every tile before this one is in them: the ones MFMAs of the previous tile retired before the barrier).
+  // Compared as unsigned bit patterns, so that inf and NaN of either sign read "large" (-fno-honor-nans: a float compare may lose them).
+  // A sum of 2^e.f in [THR, POISON) is renormalised: O and the sum times 2^-e, the reference plus e -- exact, and exactly what a reference
+  // e higher would have given from the start. At or above POISON (a score rose more than ~100 log2 units within one tile, or inf / NaN
+  // input) nothing is repaired: the wave is poisoned (it says so in the workgroup's flag word at once), walks on so that barriers and staging stay uniform, and the block runs again.
+  constexpr unsigned LAZY_THR_BITS = __builtin_bit_cast(unsigned, (float)FA16_LAZY_THR);
+  constexpr unsigned LAZY_POISON_BITS = __builtin_bit_cast(unsigned, (float)FA16_LAZY_POISON);
+  static_assert(LAZY_THR_BITS < LAZY_POISON_BITS && LAZY_POISON_BITS < 0x7f800000u, "2^-BIAS << THR < POISON < inf");
+  auto lazy_renormalise = [&]() __attribute__((always_inline)) {
+    const unsigned b0 = __builtin_bit_cast(unsigned, lacc[0][0]), b1 = __builtin_bit_cast(unsigned, lacc[1][0]);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(max(b0, b1) >= LAZY_THR_BITS) != 0, 0)) {
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        const unsigned a = __builtin_bit_cast(unsigned, lacc[qt][0]) & 0x7fffffffu;
+        const bool bad = a >= LAZY_POISON_BITS;
+        const bool big = !bad && a >= LAZY_THR_BITS;
+        const int e = (int)(a >> 23) - 127;
+        const float sc = big ? __builtin_bit_cast(float, (unsigned)(127 - e) << 23) : 1.0f;
+        const float kf = big ? (float)e : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          lacc[qt][i] *= sc;
+          negm[qt][i] -= kf;
+        }
+        asm volatile("" : "+v"(negm[qt]));
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) oacc[dt][qt][i] *= sc;
+        if (bad) lds_write_b32(poison_flag, 1u);  // (the flag is read behind the tile loop's last barrier)
+      }
     }
   };
   constexpr int G = (FA16_HALVES != 0) ? 2 : 1;  // key-tile groups of the hot pass: 1 = all 16 score MFMAs, then the softmax; 2 = per 32-key half
@@ -404,6 +469,12 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
       // over has its largest P' at 2^-3, a sum of 2^-3 at least: the kept first tile is never the weaker of the two.) Ordinary rows
       // (scores around 0) sum to about 8 over 64 keys and never start over; the first rows under the causal mask (fewer than 8
       // visible keys) do, one wave per head.
+      // LAZY (bf16): the hot pass has no test. What the previous tiles summed to is looked at here, once, in front of the tile (common
+      // case: one v_max_u32, one compare, one branch); the pass below runs scores -> mask -> exp2 -> pack -> PV + ones straight through,
+      // and nothing between the score MFMAs and the PV MFMAs waits for a verdict. The way back is left for the first tile (the floor)
+      // and for slow mode (the second run of a poisoned block), which takes it on EVERY tile, on a scalar flag: true maxima first, so
+      // every P' <= 2^-BIAS. (Backward for the reason given above: as a forward `if (slow)` in front of the pass it cost 32-40 B of scratch.)
+      if constexpr (LAZY_TEST && !FIRST) lazy_renormalise();
       bool redo = FIRST && !ONES;
       for (;;) {
         if (__builtin_expect(redo, 0)) {
@@ -416,10 +487,18 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
         __builtin_amdgcn_s_setprio(1);
 #endif
         unsigned bits = 0;
-        hot_group(bufc, K0A{}, KTG{}, kv0, pf, bits, ls);
-        if constexpr (G == 2) hot_group(bufc, K0B{}, KTG{}, kv0, pf, bits, ls);
+        if constexpr (LAZY_TEST) {
+          if (hot_group(bufc, K0A{}, KTG{}, kv0, pf, bits, ls, slow != 0 && !redo)) {
+            redo = true;
+            continue;
+          }
+        } else {
+          hot_group(bufc, K0A{}, KTG{}, kv0, pf, bits, ls, false);
+        }
+        if constexpr (G == 2) hot_group(bufc, K0B{}, KTG{}, kv0, pf, bits, ls, false);
         bool stale;
-        if constexpr (ONES) stale = __builtin_amdgcn_ballot_w64((bits & 0x40004000u) != 0) != 0;
+        if constexpr (LAZY) stale = false;  // (the test that is not there; written so that the f16 kernels keep their instructions)
+        else if constexpr (ONES) stale = __builtin_amdgcn_ballot_w64((bits & 0x40004000u) != 0) != 0;
         else stale = __builtin_amdgcn_ballot_w64(fmaxf(ls[0], ls[1]) > sum_thr) != 0;
         if (__builtin_expect(stale && !redo, 0)) {  // (after a redo every P' <= 2^-BIAS: a second stale reading is inf / NaN input)
           redo = true;
@@ -495,15 +574,65 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
       if (t0 + 1 < nT) tile(std::integral_constant<int, buf * SUB + 1>{}, std::false_type{}, t0 + 1);
     }
     if (t0 + SUB < nT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the pieces issued at the top of this unit have landed
+    if constexpr (LAZY_TEST) {
+      // the last tile's sums have no tile behind them to be looked at: in front of the block's last barrier, on which the workgroup's OR
+      // of the poison flags rides (a word of LDS, written by poisoned waves only)
+      if (t0 + SUB >= nT && slow == 0) {
+        const unsigned a0 = __builtin_bit_cast(unsigned, lacc[0][0]) & 0x7fffffffu, a1 = __builtin_bit_cast(unsigned, lacc[1][0]) & 0x7fffffffu;
+        if (max(a0, a1) >= LAZY_POISON_BITS) lds_write_b32(poison_flag, 1u);
+      }
+    }
     __syncthreads();
   };
-  unit(std::integral_constant<int, 0>{}, std::true_type{}, 0);
-  for (int t = SUB; t < nT; t += 2 * SUB) {
-    unit(std::integral_constant<int, 1>{}, std::false_type{}, t);
-    if (t + SUB < nT) unit(std::integral_constant<int, 0>{}, std::false_type{}, t + SUB);
+  // LAZY: a poisoned block (the workgroup's flag word, read behind the last barrier; nothing has been stored yet) runs once more, in
+  // slow mode, through the same loops; every other block leaves through the `break`. (The loop ends in front of the epilogue: around
+  // it hipcc hoisted the epilogue's addresses over the tile loop, into scratch; and folded into the tile loop as one more way back to
+  // tile 0 it cost 220 B.)
+  for (;;) {
+    unit(std::integral_constant<int, 0>{}, std::true_type{}, 0);
+    for (int t = SUB; t < nT; t += 2 * SUB) {
+      unit(std::integral_constant<int, 1>{}, std::false_type{}, t);
+      if (t + SUB < nT) unit(std::integral_constant<int, 0>{}, std::false_type{}, t + SUB);
+    }
+    if constexpr (LAZY_TEST) {
+      if (slow == 0) {
+        const unsigned f = *reinterpret_cast<const volatile __attribute__((address_space(3))) unsigned *>(poison_flag);
+        if (__builtin_expect(__builtin_amdgcn_readfirstlane((int)f) != 0, 0)) {
+          // clear the accumulators, take the assumed reference back (the first exact pass replaces it), restage tile 0. Slow mode cannot
+          // poison itself (every P' <= 2^-BIAS) -- inf / NaN inputs give inf / NaN rows -- and the second run is the last.
+          slow = 1;
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              lacc[qt][i] = 0.0f;
+              negm[qt][i] = -BIAS;
+            }
+            asm volatile("" : "+v"(negm[qt]));
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) oacc[dt][qt][i] = 0.0f;
+          }
+          stage_dma(0, 0);
+          if constexpr (SUB == 2) {
+            if (1 < nT) stage_dma(1, 1);
+          }
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          __syncthreads();
+          continue;
+        }
+      }
+    }
+    break;
   }
 
   // ---- epilogue: normalise, LSE, O tile -> LDS -> coalesced 16-byte stores
+  // (LAZY: the lane's indices once more, opaque -- with the second run's loop in front of it hipcc computes the epilogue's addresses in the
+  // prologue and parks them in scratch across the tile loop)
+  int elane = lane;
+  if constexpr (LAZY_TEST) asm volatile("" : "+v"(elane));
+  const int ec = elane & 15, eg = elane >> 4;
   lds_char *Ot = smem + wave * (WM * RB);  // this wave's [32][D] tile (inside the K buffers: free since the last barrier)
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
@@ -513,9 +642,9 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
       lt += xlane(lt, 32);
     }
     const float inv_l = __builtin_amdgcn_rcpf(lt);  // v_rcp_f32 (1 ulp): the IEEE division costs ten instructions per row
-    const int row = 16 * qt + c, qrow = qw0 + row;
+    const int row = 16 * qt + ec, qrow = qw0 + row;
     // LSE = (reference + log2 l) . ln 2, v_log_f32 straight (l is a sum of probabilities around 2^-BIAS .. 2^THR: no denormals)
-    if (p.lse != nullptr && g == 0 && qrow < p.N)
+    if (p.lse != nullptr && eg == 0 && qrow < p.N)
       p.lse[(long long)bh * p.N + qrow] = (__builtin_amdgcn_logf(lt) - negm[qt][0]) * 0.6931471805599453f;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
@@ -525,8 +654,8 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) e[i] = (elem)(oacc[dt][qt][i] * inv_l);
       const u32x2 w = __builtin_bit_cast(u32x2, e);
-      const int ch = (2 * dt + (g >> 1)) ^ (row & (CPR - 1));  // chunk XOR row spreads the rows over the banks
-      lds_write_b64(Ot + row * RB + (ch << 4) + 8 * (g & 1), w);
+      const int ch = (2 * dt + (eg >> 1)) ^ (row & (CPR - 1));  // chunk XOR row spreads the rows over the banks
+      lds_write_b64(Ot + row * RB + (ch << 4) + 8 * (eg & 1), w);
     }
   }
   __syncthreads();
@@ -534,7 +663,7 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
     elem *Og = (elem *)p.o + base;
 #pragma unroll
     for (int it = 0; it < WM * CPR / 64; ++it) {
-      const int idx = it * 64 + lane;
+      const int idx = it * 64 + elane;
       const int row = idx / CPR, ch = idx % CPR;
       const u32x4 vv = lds_read_b128(Ot + row * RB + ((ch ^ (row & (CPR - 1))) << 4));
       if (qw0 + row < p.N && (!PAD || ch * 8 < p.D)) *reinterpret_cast<u32x4 *>(Og + (long long)(qw0 + row) * (PAD ? p.D : D) + ch * 8) = vv;
@@ -552,7 +681,8 @@ bool mfma16_supported(int dtype, int D) { return (dtype == FA_DTYPE_F16 || dtype
 template <typename Tag, int D, bool CAUSAL, int RW, bool PAD = false, int SUB = 1>
 static hipError_t launch16_one(const Params &p, hipStream_t s) {
   const int nQ = (p.N + RW * WM - 1) / (RW * WM);
-  const size_t smem = 4 * SUB * (size_t)(D == 128 ? FA16_BN128 : BN) * D * 2;
+  constexpr bool lazy = std::is_same<Tag, BF16>::value && D == 64 && (FA16_ONES != 0) && (FA16_LAZY == 1);
+  const size_t smem = 4 * SUB * (size_t)(D == 128 ? FA16_BN128 : BN) * D * 2 + (lazy ? 16 : 0);  // K / V double buffers (+ the flag word of the lazy kernels)
   auto kern = fwd_mfma16_kernel<Tag, D, CAUSAL, RW, PAD, SUB>;
   if (smem > 48 * 1024) {
     hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem);
