@@ -24,10 +24,13 @@ from .ops import (  # noqa: F401
     flash_attention_forward,
     flash_attention_varlen,
     flash_attention_varlen_backward,
+    flash_attention_varlen_paged,
     forward_kernel_name,
+    kv_append_paged,
     supported,
     varlen_backward_supported,
     varlen_backward_workspace_bytes,
+    varlen_paged_supported,
     varlen_supported,
 )
 from .shard import shard_heads  # noqa: F401

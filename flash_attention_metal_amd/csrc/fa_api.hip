@@ -33,6 +33,8 @@ int fail(int code, const char *fmt, ...) {
 //    (max_seqlen + 128) * row_stride * 2 < 4 GiB per sequence, for q and for k / v; its grid guard B * Hq * ceil(max_seqlen_q / 128);
 //  - fa_bwd_varlen: fa_fwd_varlen's rules, with the grid guard for both of its kernels (B * Hq * ceil(max_seqlen_q / 128) and
 //    B * Hkv * ceil(max_seqlen_k / 128));
+//  - fa_fwd_varlen_paged: fa_fwd_varlen's rules for q and the grid, page_pool_ok for the pools and tables (the paged decode's rules);
+//    fa_kv_append_paged: varlen_strides_ok for the new rows, page_pool_ok, and a grid of B * ceil(max_seqlen_new / 16) x Hkv;
 //  - a missing device: FA_ERR_NO_DEVICE from fa_fwd, FA_ERR_LAUNCH from every other entry point.
 #define TRY(check) do { if (const int st_ = (check)) return st_; } while (0)
 
@@ -81,6 +83,43 @@ int head_fits(const char *fn, double head_bytes, int gib, const char *why) {
 }
 int grid_fits(const char *fn, long long heads, int rows) {  // heads x blocks of 128 rows fit an int
   return heads <= 0x7fffffffLL / ((rows + 127) / 128) ? FA_OK : fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+}
+// the page pool and its tables, for every entry point that reads or writes one, in three steps (fa_fwd_decode_paged interleaves them with
+// its other checks, in the order it has always reported them; page_pool_ok is the three in a row):
+//  - block_table_stride covers max_pages_per_seq entries;
+int table_stride_ok(const char *fn, long long block_table_stride, int max_pages_per_seq) {
+  return block_table_stride >= max_pages_per_seq
+             ? FA_OK
+             : fail(FA_ERR_INVALID_ARG, "%s: block_table_stride=%lld < max_pages_per_seq=%d", fn, block_table_stride, max_pages_per_seq);
+}
+//  - the three page strides (elements), and 2 GiB per page of one head (32-bit offsets from the page's own 64-bit base);
+int page_strides_ok(const char *fn, int D, int page_size, long long page_stride, long long head_stride, long long row_stride,
+                    long long block_table_stride, int kv_dtype) {
+  const int ksm = stride_mult(kv_dtype);  // keeps every row 16-byte aligned
+  if (row_stride < D || head_stride < D || page_stride < D || (page_stride % ksm) || (head_stride % ksm) || (row_stride % ksm) ||
+      block_table_stride > 0x7fffffffLL)
+    return fail(FA_ERR_INVALID_ARG, "%s: bad page strides", fn);
+  if ((double)page_size * row_stride * (kv_dtype == FA_DTYPE_FP8_E4M3 ? 1 : 2) >= 2147483648.0)
+    return fail(FA_ERR_INVALID_ARG, "%s: one page of one head exceeds 2 GiB", fn);
+  return FA_OK;
+}
+//  - int32 tables, and a capacity of at most 2^30 keys.
+int page_tables_ok(const char *fn, int page_size, int max_pages_per_seq, const void *block_table, const void *seqlens_k) {
+  if (((uintptr_t)block_table | (uintptr_t)seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "%s: block_table / seqlens_k must be int32-aligned", fn);
+  if ((long long)page_size * max_pages_per_seq > (1 << 30)) return fail(FA_ERR_INVALID_ARG, "%s: capacity above 2^30 keys", fn);
+  return FA_OK;
+}
+int page_pool_ok(const char *fn, int D, int page_size, int max_pages_per_seq, long long page_stride, long long head_stride, long long row_stride,
+                 long long block_table_stride, int kv_dtype, const void *block_table, const void *seqlens_k) {
+  TRY(table_stride_ok(fn, block_table_stride, max_pages_per_seq));
+  TRY(page_strides_ok(fn, D, page_size, page_stride, head_stride, row_stride, block_table_stride, kv_dtype));
+  return page_tables_ok(fn, page_size, max_pages_per_seq, block_table, seqlens_k);
+}
+int page_size_ok(int page_size) { return page_size >= 16 && page_size <= 256 && (page_size & (page_size - 1)) == 0; }
+int log2_of(int page_size) {
+  int lp = 0;
+  while ((1 << lp) < page_size) ++lp;
+  return lp;
 }
 int workspace_fits(const char *fn, long long bytes, long long need, const char *sizer) {
   return bytes >= need ? FA_OK : fail(FA_ERR_INVALID_ARG, "%s: workspace of %lld bytes, %s() asks for %lld", fn, bytes, sizer, need);
@@ -474,19 +513,12 @@ int fa_fwd_decode_paged(const void *q, const void *k_pages, const void *v_pages,
     return fail(FA_ERR_UNSUPPORTED, "fa_fwd_decode_paged: needs (q, kv) dtypes f16/f16, bf16/bf16, e4m3/e4m3 or bf16/e4m3, D = 64 | 128, (Hq / Hkv) * Nq "
                 "<= 32 packed query rows and a page size of 16, 32, 64, 128 or 256; got q=%s kv=%s D=%d Hq=%d Hkv=%d Nq=%d page_size=%d",
                 fa_dtype_name(q_dtype), fa_dtype_name(kv_dtype), D, Hq, Hkv, Nq, page_size);
-  if (block_table_stride < max_pages_per_seq)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: block_table_stride=%lld < max_pages_per_seq=%d", block_table_stride, max_pages_per_seq);
+  TRY(table_stride_ok(fn, block_table_stride, max_pages_per_seq));
   TRY(strides_ok(fn, "", Nq, D, q_batch_stride, q_head_stride, stride_mult(q_dtype), Hq > 1 && B > 1));
-  const int kv8 = kv_dtype == FA_DTYPE_FP8_E4M3, ksm = stride_mult(kv_dtype);  // keeps every row 16-byte aligned
-  if (kv_row_stride < D || kv_head_stride < D || kv_page_stride < D || (kv_page_stride % ksm) || (kv_head_stride % ksm) ||
-      (kv_row_stride % ksm) || block_table_stride > 0x7fffffffLL)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: bad page strides");
-  // a page's rows of one head are addressed by 32-bit offsets from the page's own 64-bit base
-  if ((double)page_size * kv_row_stride * (kv8 ? 1 : 2) >= 2147483648.0)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: one page of one head exceeds 2 GiB");
+  const int kv8 = kv_dtype == FA_DTYPE_FP8_E4M3;
+  TRY(page_strides_ok(fn, D, page_size, kv_page_stride, kv_head_stride, kv_row_stride, block_table_stride, kv_dtype));
   TRY(aligned16(fn, "tensors and workspace", {q, k_pages, v_pages, o, workspace}));
-  if (((uintptr_t)block_table | (uintptr_t)seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: block_table / seqlens_k must be int32-aligned");
-  if ((long long)page_size * max_pages_per_seq > (1 << 30)) return fail(FA_ERR_INVALID_ARG, "fa_fwd_decode_paged: capacity above 2^30 keys");
+  TRY(page_tables_ok(fn, page_size, max_pages_per_seq, block_table, seqlens_k));
   const int cap = page_size * max_pages_per_seq;
   TRY(workspace_fits(fn, workspace_bytes, fa::decode_workspace_bytes(B, Hq, Hkv, Nq, cap, D), "fa_fwd_decode_paged_workspace_bytes"));
   fa::DecodePagedParams p;
@@ -496,9 +528,77 @@ int fa_fwd_decode_paged(const void *q, const void *k_pages, const void *v_pages,
   p.block_table = block_table; p.seqlens = seqlens_k;
   p.page_stride = kv_page_stride; p.row_stride = kv_row_stride;
   p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
-  p.lp = 0;
-  while ((1 << p.lp) < page_size) ++p.lp;
+  p.lp = log2_of(page_size);
   return launched(fn, fa::launch_decode_paged(p, D, q_dtype, kv8, (hipStream_t)hip_stream));
+}
+
+int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size) { return fa::mfma_varlen_paged_supported(dtype, D, page_size); }
+int fa_fwd_varlen_paged(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *cu_seqlens_q,
+                        const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                        int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride, long long q_head_stride,
+                        long long kv_page_stride, long long kv_head_stride, long long kv_row_stride, long long block_table_stride,
+                        int is_causal, int dtype, void *hip_stream) {
+  g_err[0] = 0;
+  const char *fn = "fa_fwd_varlen_paged";
+  TRY(nonnull(fn, {q, k_pages, v_pages, o, cu_seqlens_q, block_table, seqlens_k}));
+  TRY(positive(fn, {B, Hq, Hkv, total_q, max_seqlen_q, D, page_size, num_pages, max_pages_per_seq}));
+  TRY(grouped(fn, Hq, Hkv));
+  TRY(scale_ok(fn, scale));
+  if (!fa_fwd_varlen_paged_supported(dtype, D, page_size))
+    return fail(FA_ERR_UNSUPPORTED, "fa_fwd_varlen_paged: needs f16 / bf16 (q and the pool alike), D = 64 | 128 and a page size of 16, 32, 64, 128 or 256; "
+                "got dtype=%s D=%d page_size=%d (an e4m3 pool: fa_fwd_decode_paged)", fa_dtype_name(dtype), D, page_size);
+  if (max_seqlen_q > total_q)
+    return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen_paged: max_seqlen_q=%d exceeds the token count %d", max_seqlen_q, total_q);
+  TRY(varlen_strides_ok(fn, "", D, q_row_stride, q_head_stride, stride_mult(dtype)));
+  TRY(page_pool_ok(fn, D, page_size, max_pages_per_seq, kv_page_stride, kv_head_stride, kv_row_stride, block_table_stride, dtype, block_table, seqlens_k));
+  TRY(aligned16(fn, "tensors", {q, k_pages, v_pages, o}));
+  if ((uintptr_t)cu_seqlens_q & 3) return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen_paged: cu_seqlens_q must be int32-aligned");
+  TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
+  TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));
+  fa::VarlenPagedParams p;
+  p.q = q; p.k = k_pages; p.v = v_pages; p.o = o; p.lse = lse;
+  p.B = B; p.H = Hq; p.Hkv = Hkv; p.N = max_seqlen_q; p.Nk = page_size * max_pages_per_seq; p.D = D; p.scale = scale;
+  p.batch_stride = 0; p.head_stride = q_head_stride; p.kv_batch_stride = 0; p.kv_head_stride = kv_head_stride;
+  p.is_causal = is_causal ? 1 : 0;
+  p.cu_q = cu_seqlens_q; p.cu_k = nullptr;
+  p.total_q = total_q; p.total_k = 0;
+  p.q_rs = q_row_stride; p.kv_rs = kv_row_stride;
+  p.block_table = block_table; p.seqlens = seqlens_k;
+  p.page_stride = kv_page_stride;
+  p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
+  p.lp = log2_of(page_size);
+  return launched(fn, fa::launch_mfma_varlen_paged(p, dtype, (hipStream_t)hip_stream));
+}
+
+int fa_kv_append_paged(const void *k_new, const void *v_new, void *k_pages, void *v_pages, const int *cu_seqlens_new, const int *block_table,
+                       const int *seqlens_k, int B, int Hkv, int total_new, int max_seqlen_new, int D, int page_size, int num_pages,
+                       int max_pages_per_seq, long long new_row_stride, long long new_head_stride, long long kv_page_stride,
+                       long long kv_head_stride, long long kv_row_stride, long long block_table_stride, int dtype, void *hip_stream) {
+  g_err[0] = 0;
+  const char *fn = "fa_kv_append_paged";
+  TRY(nonnull(fn, {k_new, v_new, k_pages, v_pages, cu_seqlens_new, block_table, seqlens_k}));
+  TRY(positive(fn, {B, Hkv, total_new, max_seqlen_new, D, page_size, num_pages, max_pages_per_seq}));
+  const int bytes = fa_dtype_in_bytes(dtype);
+  if ((dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_FP8_E4M3) || ((long long)D * bytes) % 16 || !page_size_ok(page_size))
+    return fail(FA_ERR_UNSUPPORTED, "fa_kv_append_paged: needs f16 / bf16 / fp8_e4m3, rows of whole 16-byte chunks and a page size of 16, 32, 64, 128 "
+                "or 256; got dtype=%s D=%d page_size=%d", fa_dtype_name(dtype), D, page_size);
+  if (max_seqlen_new > total_new)
+    return fail(FA_ERR_INVALID_ARG, "fa_kv_append_paged: max_seqlen_new=%d exceeds the token count %d", max_seqlen_new, total_new);
+  TRY(varlen_strides_ok(fn, "new key/value ", D, new_row_stride, new_head_stride, stride_mult(dtype)));
+  TRY(page_pool_ok(fn, D, page_size, max_pages_per_seq, kv_page_stride, kv_head_stride, kv_row_stride, block_table_stride, dtype, block_table, seqlens_k));
+  TRY(aligned16(fn, "tensors", {k_new, v_new, k_pages, v_pages}));
+  if ((uintptr_t)cu_seqlens_new & 3) return fail(FA_ERR_INVALID_ARG, "fa_kv_append_paged: cu_seqlens_new must be int32-aligned");
+  const long long nblk = (max_seqlen_new + fa::APPEND_ROWS - 1) / fa::APPEND_ROWS;
+  if (Hkv > 65535 || (long long)B * nblk > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  fa::AppendPagedParams p;
+  p.k_new = k_new; p.v_new = v_new; p.k_pages = k_pages; p.v_pages = v_pages;
+  p.cu_new = cu_seqlens_new; p.block_table = block_table; p.seqlens = seqlens_k;
+  p.B = B; p.Hkv = Hkv; p.total_new = total_new; p.max_new = max_seqlen_new; p.D = D;
+  p.new_rs = new_row_stride; p.new_hs = new_head_stride;
+  p.page_stride = kv_page_stride; p.head_stride = kv_head_stride; p.row_stride = kv_row_stride;
+  p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
+  p.lp = log2_of(page_size);
+  return launched(fn, fa::launch_kv_append_paged(p, bytes, (hipStream_t)hip_stream));
 }
 
 long long fa_bwd_workspace_bytes(int B, int H, int N) { return (long long)B * H * N * 4; }

@@ -56,6 +56,16 @@ struct VarlenParams : Params {
   long long q_rs, kv_rs;      // row strides, elements
 };
 
+// one fa_fwd_varlen_paged call (the varlen paged mode of csrc/fa_mfma_kernel.hip): the query side of VarlenParams (cu_k / total_k unused);
+// k / v are the page pools, kv_head_stride their head stride, kv_rs their row stride, Nk the capacity max_pages * page size. Key j of
+// sequence b is slot j % P of page block_table[b * bt_stride + j / P]; both tables are device memory read by the kernels.
+struct VarlenPagedParams : VarlenParams {
+  const int *block_table, *seqlens;
+  long long page_stride;  // elements
+  int bt_stride, num_pages, max_pages;
+  int lp;  // log2 of the page size (16 .. 256)
+};
+
 // one fa_fwd_decode call (csrc/fa_decode_kernel.hip)
 struct DecodeParams {
   const void *q, *k, *v;
@@ -92,6 +102,20 @@ hipError_t launch_tiled_v2(const Params &p, int dtype, hipStream_t s);
 hipError_t launch_mfma(const Params &p, int dtype, hipStream_t s);
 hipError_t launch_mfma_varlen(const VarlenParams &p, int dtype, hipStream_t s);
 bool mfma_varlen_supported(int dtype, int D);
+hipError_t launch_mfma_varlen_paged(const VarlenPagedParams &p, int dtype, hipStream_t s);
+bool mfma_varlen_paged_supported(int dtype, int D, int page_size);
+// fa_kv_append_paged (csrc/fa_decode_kernel.hip): a byte copy of new K / V rows into their slots of the page pools
+struct AppendPagedParams {
+  const void *k_new, *v_new;
+  void *k_pages, *v_pages;
+  const int *cu_new, *block_table, *seqlens;
+  int B, Hkv, total_new, max_new, D;
+  long long new_rs, new_hs, page_stride, head_stride, row_stride;  // elements
+  int bt_stride, num_pages, max_pages;
+  int lp;  // log2 of the page size
+};
+constexpr int APPEND_ROWS = 16;  // new rows per workgroup of the append kernel
+hipError_t launch_kv_append_paged(const AppendPagedParams &p, int elem_bytes, hipStream_t s);
 hipError_t launch_mfma_split2(const Params &p, int dtype, hipStream_t s);
 bool mfma_split2_supported(int dtype, int D);
 hipError_t launch_mfma_h64s2(const Params &p, int dtype, hipStream_t s);

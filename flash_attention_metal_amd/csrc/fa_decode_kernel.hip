@@ -590,4 +590,41 @@ hipError_t launch_decode(const DecodeParams &p0, int D, int dtype, int kv8, hipS
   return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
 }
 
+// fa_kv_append_paged: new K / V rows -> their slots of the page pools, a byte copy (BYTES = element size). One 16-byte chunk per lane and
+// step: a workgroup takes APPEND_ROWS new rows of one (sequence, key head), K and V alike. The sequence lookup and its clamps are the
+// varlen kernels' (entries to [0, total], a non-increasing pair is length 0, n_b <= max_seqlen_new); token i of sequence b goes to key
+// position seqlens[b] - n_b + i -- seqlens is the length AFTER the append -- and is skipped when that position is below 0, at or above
+// the capacity, or on a table entry outside [0, num_pages). Nothing else is written. Plain vector loads and stores.
+template <int BYTES>
+__global__ __launch_bounds__(256) void kv_append_paged_kernel(AppendPagedParams p) {
+  const int nblk = (p.max_new + APPEND_ROWS - 1) / APPEND_ROWS;
+  const int b = (int)blockIdx.x / nblk, rb = (int)blockIdx.x - b * nblk, hk = blockIdx.y;
+  const int s0 = min(max(p.cu_new[b], 0), p.total_new), e0 = min(max(p.cu_new[b + 1], 0), p.total_new);
+  const int n = min(max(e0 - s0, 0), p.max_new);
+  const long long first = (long long)p.seqlens[b] - n;  // key position of the sequence's first new token
+  const long long cap = (long long)p.max_pages << p.lp;
+  const int cpr = p.D * BYTES / 16;  // 16-byte chunks per row
+  const int *tbl = p.block_table + (long long)b * p.bt_stride;
+  for (int idx = threadIdx.x; idx < APPEND_ROWS * cpr; idx += 256) {
+    const int i = rb * APPEND_ROWS + idx / cpr, c = idx % cpr;
+    if (i >= n) continue;
+    const long long pos = first + i;
+    if (pos < 0 || pos >= cap) continue;
+    const int page = tbl[(int)(pos >> p.lp)];
+    if ((unsigned)page >= (unsigned)p.num_pages) continue;
+    const long long src = ((long long)(s0 + i) * p.new_rs + (long long)hk * p.new_hs) * BYTES + 16 * c;
+    const long long dst = ((long long)page * p.page_stride + (long long)hk * p.head_stride + (pos & ((1 << p.lp) - 1)) * p.row_stride) * BYTES + 16 * c;
+    *reinterpret_cast<u32x4 *>((char *)p.k_pages + dst) = *reinterpret_cast<const u32x4 *>((const char *)p.k_new + src);
+    *reinterpret_cast<u32x4 *>((char *)p.v_pages + dst) = *reinterpret_cast<const u32x4 *>((const char *)p.v_new + src);
+  }
+}
+
+hipError_t launch_kv_append_paged(const AppendPagedParams &p, int elem_bytes, hipStream_t s) {
+  const int nblk = (p.max_new + APPEND_ROWS - 1) / APPEND_ROWS;
+  (void)hipGetLastError();
+  if (elem_bytes == 1) hipLaunchKernelGGL(kv_append_paged_kernel<1>, dim3(p.B * nblk, p.Hkv), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(kv_append_paged_kernel<2>, dim3(p.B * nblk, p.Hkv), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
 }  // namespace fa

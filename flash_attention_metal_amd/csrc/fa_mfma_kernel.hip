@@ -95,9 +95,23 @@ constexpr bool main_kernel_occ4() {
 // [total, heads, D] batch; its lengths come from the cu_seqlens tables in device memory and take the place of N / Nk, its rows are
 // addressed with a run-time pitch. Everything from LDS onwards -- images, swizzles, MFMA order, softmax -- is the dense kernel's, so a
 // sequence comes out bit for bit as the dense kernel computes it alone.
+// PT = VarlenPagedParams ("varlen paged" mode, fa_fwd_varlen_paged): the varlen mode's query side, unchanged, over the paged decode's
+// key side (fa_decode_kernel.hip, PAGED). The sequence's length L_b comes from seqlens (clamped to the capacity) and takes LK's place;
+// every 1-KiB LDS-DMA piece (8 / 4 rows) comes from the page the block table names for it, through a descriptor built on that page's
+// 64-bit base whose range covers only the page's valid rows, with the whole in-page offset in voffset. Pages hold >= 16 rows and start
+// at multiples of their size, so a piece lies inside ONE page. Each wave loads the table entries of ITS pieces of the next tile one tile
+// ahead (one vector load, lane j takes the entry of piece j: NPW = 2 / 4 entries, duplicates when a page holds several pieces; the value
+// stays in its register until the NEXT tile's staging makes it wave-uniform). The LDS images are the varlen mode's, and
+// rows at or past L_b read as zeros there as here: a sequence comes out bit for bit as fa_fwd_varlen computes it on the gathered cache.
+// (overloads, so that the body can name the page tables in an expression both modes compile)
+__device__ __forceinline__ int seqlen_paged(const VarlenPagedParams &p, int b) { return p.seqlens[b]; }
+__device__ __forceinline__ int seqlen_paged(const Params &, int) { return 0; }
+__device__ __forceinline__ int paged_capacity(const VarlenPagedParams &p) { return p.max_pages << p.lp; }
+__device__ __forceinline__ int paged_capacity(const Params &) { return 0; }
 template <typename Tag, int D, bool CAUSAL, int SPLIT, bool PRESC, int ROWS = BM, typename PT = Params>
 __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
-  constexpr bool VARLEN = std::is_same<PT, VarlenParams>::value;
+  constexpr bool PAGEDV = std::is_same<PT, VarlenPagedParams>::value;
+  constexpr bool VARLEN = std::is_same<PT, VarlenParams>::value || PAGEDV;
   static_assert(!VARLEN || (SPLIT == 1 && ROWS == BM && PRESC && !std::is_same<Tag, FP8>::value && (D == 64 || D == 128)),
                 "varlen mode: the plain 128-row kernel, 16-bit inputs, LDS-DMA staging");
   constexpr int RW = ROWS / WM;   // row groups = waves per split
@@ -160,6 +174,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   int LQ = 0, LK = 0;          // queries and keys of this block's sequence
   unsigned qrb = 0, kvrb = 0;  // row pitch of Q / O and of K / V in global memory, bytes
   long long lse_base = 0;      // first LSE element of this block's (head, sequence)
+  const int *ptbl = nullptr;   // varlen paged: this sequence's row of the block table
 #define FA_NQ (VARLEN ? LQ : p.N)
 #define FA_NK (VARLEN ? LK : p.Nk)
   if constexpr (VARLEN) {
@@ -169,12 +184,14 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
     // last row leaves here, in front of every barrier.
     const int b = (int)fdiv((unsigned)bh, p.fd_h), hq = bh - b * p.H;
     const int sq = min(max(p.cu_q[b], 0), p.total_q), eq = min(max(p.cu_q[b + 1], 0), p.total_q);
-    const int sk = min(max(p.cu_k[b], 0), p.total_k), ek = min(max(p.cu_k[b + 1], 0), p.total_k);
+    // (varlen paged: no key table; the cache length -- with the chunk already appended -- comes from seqlens, clamped to the capacity)
+    const int sk = PAGEDV ? 0 : min(max(p.cu_k[PAGEDV ? 0 : b], 0), p.total_k), ek = PAGEDV ? 0 : min(max(p.cu_k[PAGEDV ? 0 : b + 1], 0), p.total_k);
     LQ = min(max(eq - sq, 0), p.N);
-    LK = min(max(ek - sk, 0), p.Nk);
+    LK = PAGEDV ? min(max(__builtin_amdgcn_readfirstlane(seqlen_paged(p, b)), 0), paged_capacity(p)) : min(max(ek - sk, 0), p.Nk);
     if (qb * ROWS >= LQ) return;
     base = (long long)sq * p.q_rs + (long long)hq * p.head_stride;
-    base_kv = (long long)sk * p.kv_rs + (long long)fdiv((unsigned)hq, p.fd_gq) * p.kv_head_stride;
+    base_kv = (long long)sk * p.kv_rs + (long long)fdiv((unsigned)hq, p.fd_gq) * p.kv_head_stride;  // (varlen paged: the key head's offset inside a page)
+    if constexpr (PAGEDV) ptbl = p.block_table + (long long)b * p.bt_stride;
     lse_base = (long long)hq * p.total_q + sq;
     qrb = (unsigned)p.q_rs * 2;
     kvrb = (unsigned)p.kv_rs * 2;
@@ -202,13 +219,14 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
 
   // (varlen: the descriptors end with the last row's D elements, so rows at or past the sequence's end read as zero whatever the pitch)
   const unsigned head_bytes = VARLEN ? (unsigned)(LQ - 1) * qrb + GRB16 : (unsigned)p.N * GRB;
-  const unsigned kv_head_bytes = VARLEN ? (unsigned)(LK - 1) * kvrb + GRB : (unsigned)p.Nk * GRB;
+  // (varlen paged: K / V have no descriptor of the whole head, every piece builds its page's; these two stay empty and unused)
+  const unsigned kv_head_bytes = PAGEDV ? 0u : VARLEN ? (unsigned)(LK - 1) * kvrb + GRB : (unsigned)p.Nk * GRB;
   const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
       (void *)((const char *)p.q + base * GB), 0, head_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)((const char *)p.k + base_kv * GB), 0, kv_head_bytes, 0x00020000);
+      (void *)((const char *)p.k + (PAGEDV ? 0 : base_kv) * GB), 0, kv_head_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)((const char *)p.v + base_kv * GB), 0, kv_head_bytes, 0x00020000);
+      (void *)((const char *)p.v + (PAGEDV ? 0 : base_kv) * GB), 0, kv_head_bytes, 0x00020000);
 
   // ---- Q fragments (B operand of K.Q^T): lane (r,h) holds Q[qrow][16ks+8h .. +7].
   // Rows >= N read as zero through the descriptor's range check.
@@ -300,14 +318,46 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
     const int svx = (D == 32) ? 0 : (D == 64) ? (((row >> 1) & 1) << 2) : ((row & 3) << 2);
     dma_kvo = VARLEN ? row * kvrb + ((pc ^ skx) << 4) : (unsigned)(row * GRB + ((pc ^ skx) << 4));
     dma_vvo = VARLEN ? row * kvrb + ((pc ^ svx) << 4) : (unsigned)(row * GRB + ((pc ^ svx) << 4));
+    if constexpr (PAGEDV) {  // the lane's row inside its piece only: the piece's own slot in its page is wave-uniform and added per piece
+      dma_kvo = (lane / CPRL) * kvrb + ((pc ^ skx) << 4);
+      dma_vvo = (lane / CPRL) * kvrb + ((pc ^ svx) << 4);
+    }
   }
+  // ---- varlen paged: lane j of pgv = the table entry of the page that holds this wave's piece j of the next tile to stage, loaded one
+  // tile ahead: ONE global_load_dword per wave and tile, issued behind the tile's LDS-DMA statements. Nothing reads pgv before the next
+  // tile's staging (v_readlane per piece), i.e. behind the vmcnt(0) and the barrier that end this tile: a wait placed at the load would
+  // drain the K / V pieces that have just been issued, in front of the tile's MFMAs. A piece starts at key t * BN + (wave + RW * j) * RPP;
+  // the index never leaves the row's max_pages entries (a tile may reach past the capacity: those pieces have no valid row and read as
+  // zeros whatever the entry says).
+  int pgv = 0;
+  auto fetch_pages = [&](int t) __attribute__((always_inline)) {
+    if constexpr (PAGEDV) {
+      const int kp = t * BN + (wave + RW * (lane & (NPW - 1))) * RPP;
+      pgv = ptbl[min(kp >> p.lp, p.max_pages - 1)];
+    }
+  };
   auto stage_dma = [&](int t, int buf) {  // tile t -> buffer buf (hipcc does not count these loads: the caller waits vmcnt(0))
 #pragma unroll
     for (int j = 0; j < NPW; ++j) {
       const unsigned soff = VARLEN ? ((unsigned)t * BN + j * (RW * RPP)) * kvrb : (unsigned)t * GTILE + j * (RW * 1024);  // (dense: a piece's RPP rows are 1024 bytes)
       const unsigned lk = (unsigned)(__UINTPTR_TYPE__)Kbuf + buf * KTILE + (wave + RW * j) * 1024;
       const unsigned lv = (unsigned)(__UINTPTR_TYPE__)Vbuf + buf * TILE + (wave + RW * j) * 1024;
-      if constexpr (VARLEN) {
+      if constexpr (PAGEDV) {
+        // this piece's page: a descriptor on the page's 64-bit base (+ the key head) that ends with the last valid row's D elements
+        // (rows >= L_b, and every row of a page index outside the pool, read as zeros); the slot's offset goes into voffset
+        const int P = 1 << p.lp, kp = t * BN + (wave + RW * j) * RPP;
+        const int page = __builtin_amdgcn_readlane(pgv, j);
+        const int nv = min(LK - (kp & -P), P);  // valid rows of the page
+        const bool ok = nv > 0 && (unsigned)page < (unsigned)p.num_pages;
+        const long long off = ok ? (long long)page * p.page_stride + base_kv : 0;
+        const unsigned nrec = ok ? (unsigned)(nv - 1) * kvrb + GRB16 : 0u;
+        const __amdgpu_buffer_rsrc_t rkp = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.k + off * 2), 0, nrec, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rvp = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.v + off * 2), 0, nrec, 0x00020000);
+        const unsigned so = (unsigned)(kp & (P - 1)) * kvrb;
+        const unsigned vk = dma_kvo + so, vv = dma_vvo + so;
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lk), "v"(vk), "s"(rkp) : "memory");
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lv), "v"(vv), "s"(rvp) : "memory");
+      } else if constexpr (VARLEN) {
         // the whole offset in voffset, i.e. inside the descriptor's range check: what follows a sequence's last key is another sequence
         // or the end of the tensor, and both must read as zeros (the dense kernel's heads end where its descriptors end)
         const unsigned vk = dma_kvo + soff, vv = dma_vvo + soff;
@@ -318,6 +368,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lv), "v"(dma_vvo), "s"(rv), "s"(soff) : "memory");
       }
     }
+    if constexpr (PAGEDV) fetch_pages(t + 1);
   };
   // fp8 inputs: the K tile stays raw e4m3 in LDS (rows of D bytes), so IT can travel by LDS-DMA; V is widened to bf16 on the way
   // and keeps the register path
@@ -381,6 +432,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   if constexpr (PRE) asm volatile("" : "+v"(negm));  // opaque: else hipcc re-materialises the splat in front of every MFMA
 
   if constexpr (DMA) {
+    if constexpr (PAGEDV) fetch_pages(0);
     stage_dma(sp, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   } else {
@@ -830,6 +882,16 @@ __global__ __launch_bounds__(NTHREADS, ((main_kernel_occ4<Tag, D, true>() && CAU
   fwd_mfma_body<Tag, D, CAUSAL, 1, true, BM, VarlenParams>(p);
 }
 
+// fa_fwd_varlen_paged: the same kernel in varlen paged mode. The page walk lives in SGPRs: the varlen kernels' occupancy is declared.
+template <int D, bool CAUSAL>
+constexpr int varlen_paged_occupancy() {
+  return D <= 64 ? (CAUSAL ? 4 : 3) : 2;
+}
+template <typename Tag, int D, bool CAUSAL>
+__global__ __launch_bounds__(NTHREADS, (varlen_paged_occupancy<D, CAUSAL>())) void fwd_mfma_varlen_paged_kernel(VarlenPagedParams p) {
+  fwd_mfma_body<Tag, D, CAUSAL, 1, true, BM, VarlenPagedParams>(p);
+}
+
 // ---------------------------------------------------------------------------
 bool mfma_supported(int dtype, int D) {
   if (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) return D == 32 || D == 64 || D == 96 || D == 128 || D == 256;
@@ -898,6 +960,38 @@ hipError_t launch_mfma_varlen(const VarlenParams &p, int dtype, hipStream_t s) {
     using Tag = decltype(tag);
     if (p.D == 64) return p.is_causal ? launch_varlen_one<Tag, 64, true>(p, s) : launch_varlen_one<Tag, 64, false>(p, s);
     if (p.D == 128) return p.is_causal ? launch_varlen_one<Tag, 128, true>(p, s) : launch_varlen_one<Tag, 128, false>(p, s);
+    return hipErrorInvalidValue;
+  };
+  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
+}
+
+// Varlen paged: the varlen grid; p.Nk holds the capacity (issue order and head groups as for a dense batch of full caches)
+template <typename Tag, int D, bool CAUSAL>
+static hipError_t launch_varlen_paged_one(const VarlenPagedParams &p, hipStream_t s) {
+  const int nQ = (p.N + BM - 1) / BM;
+  const size_t smem = 4 * BN * (size_t)(D * 2);
+  auto kern = fwd_mfma_varlen_paged_kernel<Tag, D, CAUSAL>;
+  if (smem > 48 * 1024) {
+    hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem);
+    if (e != hipSuccess) return e;
+  }
+  VarlenPagedParams pp = p;
+  pp.head_group = causal_head_group(p, D, 2);
+  set_block_divisors(pp, nQ, pp.head_group);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(kern, dim3(nQ * p.B * p.H), dim3(NTHREADS), smem, s, pp);
+  return hipGetLastError();
+}
+
+bool mfma_varlen_paged_supported(int dtype, int D, int page_size) {
+  return mfma_varlen_supported(dtype, D) && page_size >= 16 && page_size <= 256 && (page_size & (page_size - 1)) == 0;
+}
+
+hipError_t launch_mfma_varlen_paged(const VarlenPagedParams &p, int dtype, hipStream_t s) {
+  auto go = [&](auto tag) -> hipError_t {
+    using Tag = decltype(tag);
+    if (p.D == 64) return p.is_causal ? launch_varlen_paged_one<Tag, 64, true>(p, s) : launch_varlen_paged_one<Tag, 64, false>(p, s);
+    if (p.D == 128) return p.is_causal ? launch_varlen_paged_one<Tag, 128, true>(p, s) : launch_varlen_paged_one<Tag, 128, false>(p, s);
     return hipErrorInvalidValue;
   };
   return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});

@@ -353,6 +353,128 @@ def flash_attention_varlen(
     return out, lse
 
 
+def varlen_paged_supported(dtype: str, D: int, page_size: int) -> bool:
+    return bool(load_library().fa_fwd_varlen_paged_supported(DTYPES[dtype], D, int(page_size)))
+
+
+def _pool(entry: str, k_pages: torch.Tensor, v_pages: torch.Tensor, layout: str):
+    """(num_pages, Hkv, P, D, page stride, head stride, row stride) of a pool pair in layout HND / NHD."""
+    if k_pages.dim() != 4 or k_pages.shape != v_pages.shape:
+        raise ValueError(f"{entry}: k_pages / v_pages one [num_pages,Hkv,P,D] (HND) or [num_pages,P,Hkv,D] (NHD) shape")
+    if layout not in ("HND", "NHD"):
+        raise ValueError(f"layout must be 'HND' or 'NHD', got {layout!r}")
+    if layout == "HND":
+        num_pages, Hkv, P, D = k_pages.shape
+        ps, hs, rs, es = k_pages.stride()
+    else:
+        num_pages, P, Hkv, D = k_pages.shape
+        ps, rs, hs, es = k_pages.stride()
+    if es != 1 or v_pages.stride() != k_pages.stride() or v_pages.dtype != k_pages.dtype:
+        raise ValueError(f"{entry}: k_pages and v_pages need one dtype, a unit element stride and one set of strides")
+    return num_pages, Hkv, P, D, ps, hs, rs
+
+
+def _tables(entry: str, cu: torch.Tensor, cu_name: str, block_table: torch.Tensor, seqlens_k: torch.Tensor) -> int:
+    if cu.dtype != torch.int32 or cu.dim() != 1 or cu.shape[0] < 2 or not cu.is_contiguous():
+        raise ValueError(f"{cu_name} must be a contiguous int32 [B + 1] tensor")
+    B = cu.shape[0] - 1
+    if (block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1
+            or not block_table.is_contiguous() or seqlens_k.dtype != torch.int32 or seqlens_k.shape != (B,) or not seqlens_k.is_contiguous()):
+        raise ValueError("block_table must be a contiguous int32 [B, max_pages_per_seq] tensor and seqlens_k a contiguous int32 [B] one")
+    return B
+
+
+def flash_attention_varlen_paged(
+    q: torch.Tensor,
+    k_pages: torch.Tensor,
+    v_pages: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens_k: torch.Tensor,
+    max_seqlen_q: int,
+    is_causal: bool = False,
+    scale: Optional[float] = None,
+    layout: str = "HND",
+    return_lse: bool = True,
+    out: Optional[torch.Tensor] = None,
+    lse: Optional[torch.Tensor] = None,
+    stream: Optional[int] = None,
+) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Packed queries against a paged KV cache (include/fa_mi355.h fa_fwd_varlen_paged): chunked prefill, prefix caching, verification of
+    many speculated tokens. q [total_q, Hq, D] as in flash_attention_varlen (any view with a unit element stride), cu_seqlens_q int32
+    [B + 1]; k_pages / v_pages, block_table [B, max_pages_per_seq] and seqlens_k [B] as in flash_attention_decode_paged (layout "HND" or
+    "NHD", P in {16, 32, 64, 128, 256}); f16 / bf16 with q and the pools of one type, D = 64 | 128. seqlens_k[b] is the cache length
+    with the chunk already appended (kv_append_paged): causal is bottom-right aligned per sequence, which makes a causal call a
+    chunked-prefill step. The tables are read by the kernel only -- nothing here synchronises or reads device values, so the call can be
+    captured in a graph and replayed after the tables change in place. A row with no visible key gets O = 0 and LSE = -inf; tokens at or
+    past cu_seqlens_q[B] and rows beyond max_seqlen_q of a sequence are not written. An inference path: no torch custom op and no
+    backward. Returns (out, lse): out like q, lse [Hq, total_q]."""
+    lib = load_library()
+    entry = "flash_attention_varlen_paged"
+    if q.dim() != 3:
+        raise ValueError(f"q [total_q,Hq,D], got {tuple(q.shape)}")
+    num_pages, Hkv, P, Dk, ps, hs, rs = _pool(entry, k_pages, v_pages, layout)
+    total_q, Hq, D = q.shape
+    if Dk != D or Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"incompatible q {tuple(q.shape)} and pools {tuple(k_pages.shape)} (same D, Hq % Hkv == 0)")
+    if q.dtype not in (torch.float16, torch.bfloat16) or k_pages.dtype != q.dtype:
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k_pages.dtype} {v_pages.dtype} (f16 or bf16, q and the pools alike)")
+    if q.stride(2) != 1:
+        raise ValueError("q needs a unit element stride (a head of a token is D contiguous elements)")
+    B = _tables(entry, cu_seqlens_q, "cu_seqlens_q", block_table, seqlens_k)
+    if not all(t.is_cuda and t.device == q.device for t in (q, k_pages, v_pages, cu_seqlens_q, block_table, seqlens_k)):
+        raise RuntimeError("flash_attention_varlen_paged needs q, the pools and the tables on one device: there is no CPU path")
+    if out is None:
+        out = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device)
+    elif (not out.is_cuda or out.device != q.device or out.dtype != q.dtype or out.shape != q.shape or out.stride() != q.stride()):
+        raise ValueError("out must be a device tensor with q's dtype, shape and strides (the kernel writes it under q's strides)")
+    if lse is None:
+        lse = torch.empty((Hq, total_q), dtype=torch.float32, device=q.device) if return_lse else None
+    elif not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.shape != (Hq, total_q):
+        raise ValueError("lse must be contiguous fp32 [Hq, total_q] on q's device")
+    _call(lib, "fa_fwd_varlen_paged",
+          (q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), block_table.data_ptr(),
+           seqlens_k.data_ptr(), B, Hq, Hkv, total_q, int(max_seqlen_q), D, P, num_pages, block_table.shape[1], _scale(scale, D),
+           q.stride(0), q.stride(1), ps, hs, rs, block_table.stride(0), int(bool(is_causal)), _TORCH2FA[q.dtype]), q.device, stream)
+    return out, lse
+
+
+def kv_append_paged(
+    k_new: torch.Tensor,
+    v_new: torch.Tensor,
+    k_pages: torch.Tensor,
+    v_pages: torch.Tensor,
+    cu_seqlens_new: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens_k: torch.Tensor,
+    max_seqlen_new: int,
+    layout: str = "HND",
+    stream: Optional[int] = None,
+) -> None:
+    """Write new K / V rows into the page pools, in place (include/fa_mi355.h fa_kv_append_paged): k_new / v_new [total_new, Hkv, D] views
+    with one set of strides, f16 / bf16 / e4m3 like the pools; token i of sequence b (tokens cu_seqlens_new[b] .. cu_seqlens_new[b+1)) goes to
+    key position seqlens_k[b] - n_b + i, i.e. seqlens_k holds the lengths AFTER the append -- the table flash_attention_varlen_paged and
+    flash_attention_decode_paged then read. Positions outside the capacity or on table entries outside the pool are skipped; nothing else
+    is written. Nothing here synchronises or reads device values: graph-capturable. An inference path: no torch custom op, no backward."""
+    lib = load_library()
+    entry = "kv_append_paged"
+    num_pages, Hkv, P, D, ps, hs, rs = _pool(entry, k_pages, v_pages, layout)
+    if k_new.dim() != 3 or k_new.shape != v_new.shape or k_new.shape[1:] != (Hkv, D):
+        raise ValueError(f"k_new / v_new one [total_new,Hkv,D] shape matching the pools, got {tuple(k_new.shape)} {tuple(v_new.shape)} "
+                         f"for pools {tuple(k_pages.shape)}")
+    if k_pages.dtype not in (torch.float16, torch.bfloat16, _FP8) or k_new.dtype != k_pages.dtype or v_new.dtype != k_pages.dtype:
+        raise ValueError(f"unsupported / mixed dtypes {k_new.dtype} {v_new.dtype} {k_pages.dtype} (f16 / bf16 / e4m3, new rows and pools alike)")
+    if k_new.stride(2) != 1 or v_new.stride() != k_new.stride():
+        raise ValueError("k_new and v_new need a unit element stride and one set of row/head strides")
+    B = _tables(entry, cu_seqlens_new, "cu_seqlens_new", block_table, seqlens_k)
+    if not all(t.is_cuda and t.device == k_pages.device for t in (k_new, v_new, k_pages, v_pages, cu_seqlens_new, block_table, seqlens_k)):
+        raise RuntimeError("kv_append_paged needs the new rows, the pools and the tables on one device: there is no CPU path")
+    _call(lib, "fa_kv_append_paged",
+          (k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), cu_seqlens_new.data_ptr(), block_table.data_ptr(),
+           seqlens_k.data_ptr(), B, Hkv, k_new.shape[0], int(max_seqlen_new), D, P, num_pages, block_table.shape[1], k_new.stride(0),
+           k_new.stride(1), ps, hs, rs, block_table.stride(0), _TORCH2FA[k_pages.dtype]), k_pages.device, stream)
+
+
 def varlen_backward_supported(dtype: str, D: int) -> bool:
     return bool(load_library().fa_bwd_varlen_supported(DTYPES[dtype], D))
 

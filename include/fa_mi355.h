@@ -174,7 +174,7 @@ int fa_fwd_exv(const void *q, const void *k, const void *v, void *o, float *lse,
                int is_causal, int dtype, int variant, void *hip_stream);
 
 /*
- * The forward over PACKED variable-length sequences ("varlen"; the prefill step that goes with fa_fwd_decode_paged; not in the reference):
+ * The forward over PACKED variable-length sequences ("varlen"; the prefill of a first prompt, whose K / V are not in a cache yet -- fa_fwd_varlen_paged below reads a paged cache; not in the reference):
  * B sequences lie back to back in q / o [total_q tokens] and k / v [total_k tokens]. Token t, head h, element d of q and o sits at
  * t * q_row_stride + h * q_head_stride + d, of k and v (one stride set for both) at t * kv_row_stride + h * kv_head_stride + d: both
  * [total, H, D] (strides H*D, D) and [H, total, D] (strides D, total*D) work, and so do three views of one packed [total, Hq + 2*Hkv, D]
@@ -260,6 +260,61 @@ int fa_fwd_decode_paged(const void *q, const void *k_pages, const void *v_pages,
 /* = fa_fwd_decode_workspace_bytes(B, Hq, Hkv, Nq, page_size * max_pages_per_seq, D): depends on the capacity only (0 if invalid) */
 long long fa_fwd_decode_paged_workspace_bytes(int B, int Hq, int Hkv, int Nq, int D, int page_size, int max_pages_per_seq);
 int fa_fwd_decode_paged_supported(int q_dtype, int kv_dtype, int D, int Hq, int Hkv, int Nq, int page_size);
+
+/*
+ * PACKED queries against a PAGED KV cache (chunked prefill, prefix caching, speculative verification of many tokens; not in the
+ * reference): the query side of fa_fwd_varlen over the key side of fa_fwd_decode_paged, in the 128-row kernel.
+ * q, o, lse, cu_seqlens_q, total_q, max_seqlen_q and the q strides behave exactly as in fa_fwd_varlen: q and o are packed
+ * [total_q, Hq, D] under row / head element strides (multiples of 8, at least D), lse is [Hq, total_q] fp32 or NULL; table entries are
+ * clamped to [0, total_q], a non-increasing pair gives length 0, Lq_b is clamped to max_seqlen_q, and tokens owned by nobody (at or
+ * past cu_seqlens_q[B], rows of a sequence beyond max_seqlen_q) are not written.
+ * k_pages, v_pages, block_table, seqlens_k, page_size (P), num_pages, max_pages_per_seq, the three kv strides and block_table_stride
+ * behave exactly as in fa_fwd_decode_paged: HND or NHD pools under one set of strides, L_b = seqlens_k[b] clamped to
+ * [0, max_pages_per_seq * P], key j < L_b is slot j % P of page block_table[b][j / P]; a page index outside [0, num_pages) reads as
+ * zeros and touches nothing; slots >= L_b of a last page and table entries past ceil(L_b / P) have no influence (NaN there is harmless).
+ * The pool may exceed 4 GiB, one page of one head stays below 2 GiB, the capacity is at most 2^30 keys.
+ * Per sequence the operator is fa_fwd_ex: query head h reads key head h / (Hq / Hkv); causal is bottom-right aligned per sequence (key
+ * j visible to query i iff j <= i + L_b - Lq_b), where L_b is the cache length WITH the chunk already appended (fa_kv_append_paged
+ * below) -- that makes a causal call a chunked-prefill step. L_b < Lq_b and L_b = 0 are legal: a row with no visible key gets O = 0
+ * exactly and LSE = -inf. The host reads neither table nor the lengths; the grid is B * Hq * ceil(max_seqlen_q / 128) workgroups, so
+ * one captured graph serves every step under the same scalars. No workspace and no key split; asynchronous, allocates nothing.
+ * f16 / bf16 with q and the pool of the same type, D = 64 | 128, P in {16, 32, 64, 128, 256}: anything else FA_ERR_UNSUPPORTED. An
+ * e4m3 pool is out of scope here: the 128-row kernel's varlen mode has no widening stage (fa_fwd_decode_paged takes such pools).
+ * Null pointers (lse may be NULL), sizes < 1, Hq % Hkv != 0, scale <= 0, bad strides or alignment, max_seqlen_q > total_q,
+ * block_table_stride < max_pages_per_seq, a capacity above 2^30, a page of one head at or above 2 GiB,
+ * (max_seqlen_q + 128) * q_row_stride * 2 >= 4 GiB or a grid that does not fit an int: FA_ERR_INVALID_ARG before any launch.
+ * Tolerances are FA_VARIANT_MFMA's and "LSE accuracy" above applies; more than that, for every sequence with L_b >= Lq_b >= 1 (without
+ * the mask: both >= 1) O and LSE are BIT-IDENTICAL to fa_fwd_varlen on the gathered dense cache of that sequence, whatever the page
+ * size, layout, page order, strides or other sequences are. Results are bitwise reproducible.
+ */
+int fa_fwd_varlen_paged(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                        const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                        int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                        int page_size, int num_pages, int max_pages_per_seq, float scale,
+                        long long q_row_stride, long long q_head_stride,
+                        long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                        long long block_table_stride, int is_causal, int dtype, void *hip_stream);
+int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size);
+/*
+ * Write new K / V rows into the page pools ("append"; the step in front of fa_fwd_varlen_paged or fa_fwd_decode_paged): k_new / v_new
+ * are packed [total_new, Hkv, D] views under one (row, head) stride pair; sequence b owns tokens cu_seqlens_new[b] ..
+ * cu_seqlens_new[b+1) (entries clamped to [0, total_new], a non-increasing pair is length 0, n_b clamped to max_seqlen_new). Token i
+ * of sequence b goes to key position seqlens_k[b] - n_b + i of that sequence: seqlens_k is the length AFTER the append, the same table
+ * the attention call then reads. A position below 0, at or above the capacity max_pages_per_seq * P, or on a table entry outside
+ * [0, num_pages) is skipped; nothing else in the pools is written -- no other slot, and no bytes between heads or rows under wide
+ * strides. A pure byte copy: f16 / bf16 / e4m3 (element size fa_dtype_in_bytes(dtype)), D * bytes a multiple of 16, strides multiples
+ * of 8 elements (16 for e4m3) and at least D, bases 16-byte aligned, P in {16, 32, 64, 128, 256}. The tables are DEVICE memory; the grid
+ * (B * ceil(max_seqlen_new / 16) x Hkv workgroups) depends on host scalars only: asynchronous, allocates nothing, graph-capturable.
+ * Bad pointers, sizes, strides or alignment, max_seqlen_new > total_new, block_table_stride < max_pages_per_seq, a capacity above
+ * 2^30, a page of one head at or above 2 GiB, Hkv > 65535 or a grid that does not fit an int: FA_ERR_INVALID_ARG before any launch.
+ */
+int fa_kv_append_paged(const void *k_new, const void *v_new, void *k_pages, void *v_pages,
+                       const int *cu_seqlens_new, const int *block_table, const int *seqlens_k,
+                       int B, int Hkv, int total_new, int max_seqlen_new, int D,
+                       int page_size, int num_pages, int max_pages_per_seq,
+                       long long new_row_stride, long long new_head_stride,
+                       long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                       long long block_table_stride, int dtype, void *hip_stream);
 
 /*
  * Backward of the operator (row f1 of the scope table): the reference binds it as
