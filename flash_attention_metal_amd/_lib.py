@@ -27,6 +27,10 @@ SYMBOLS = {
     "fa_fwd_decode_paged_supported": (c_int, [c_int] * 7),
     "fa_fwd_varlen_paged": (c_int, [c_void_p] * 8 + [c_int] * 9 + [c_float] + [c_longlong] * 6 + [c_int, c_int, c_void_p]),
     "fa_fwd_varlen_paged_supported": (c_int, [c_int] * 3),
+    "fa_fwd_varlen_window": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_int, c_void_p]),
+    "fa_fwd_varlen_paged_window": (c_int, [c_void_p] * 8 + [c_int] * 9 + [c_float] + [c_longlong] * 6 + [c_int, c_int, c_int, c_void_p]),
+    "fa_fwd_decode_paged_window": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_float] + [c_longlong] * 6 + [c_int] * 4 + [c_void_p, c_longlong, c_void_p]),
+    "fa_window_key_range": (c_int, [c_int] * 6 + [c_void_p, c_void_p]),
     "fa_kv_append_paged": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_longlong] * 6 + [c_int, c_void_p]),
     "fa_bwd": (c_int, [c_void_p] * 10 + [c_int, c_int, c_int, c_int, c_float, c_longlong, c_longlong, c_int, c_int, c_void_p]),
     "fa_bwd_ex": (c_int, [c_void_p] * 10 + [c_int] * 6 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_void_p]),

@@ -124,6 +124,14 @@ int log2_of(int page_size) {
 int workspace_fits(const char *fn, long long bytes, long long need, const char *sizer) {
   return bytes >= need ? FA_OK : fail(FA_ERR_INVALID_ARG, "%s: workspace of %lld bytes, %s() asks for %lld", fn, bytes, sizer, need);
 }
+// The *_window entry points route by SIGN only: (wl < 0, wr < 0) is the un-windowed call without the mask and (wl < 0, wr == 0) the
+// causal one -- the existing kernels, bit for bit; every other pair runs the windowed kernels, however large its values.
+enum { WIN_FULL = 0, WIN_CAUSAL = 1, WIN_KERNEL = 2 };
+int window_route(int wl, int wr) { return wl < 0 && wr < 0 ? WIN_FULL : wl < 0 && wr == 0 ? WIN_CAUSAL : WIN_KERNEL; }
+// what the windowed kernels get: a side that is unbounded (negative) or at least `never` wide becomes `never`, the smallest width that
+// cannot bind (wl: the most keys a sequence of the call can hold; wr: the most query rows), so that the kernels' 32-bit coff - wl and
+// row + coff + wr cannot wrap
+int window_clamp(int w, int never) { return w < 0 || w > never ? never : w; }
 int launched(const char *fn, hipError_t e) {
   return e == hipSuccess ? FA_OK : fail(FA_ERR_LAUNCH, "%s: launch failed: %s", fn, hipGetErrorString(e));
 }
@@ -393,40 +401,66 @@ int fa_fwd_exv(const void *q, const void *k, const void *v, void *o, float *lse,
 }
 
 int fa_fwd_varlen_supported(int dtype, int D) { return fa::mfma_varlen_supported(dtype, D); }
-int fa_fwd_varlen(const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q, const int *cu_seqlens_k,
-                  int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
-                  long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride, int is_causal,
-                  int dtype, void *hip_stream) {
+// fa_fwd_varlen (window_left = -1, window_right = is_causal ? 0 : -1) and fa_fwd_varlen_window: one set of rules, one launch path
+static int varlen_impl(const char *fn, const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q,
+                       const int *cu_seqlens_k, int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D,
+                       float scale, long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
+                       int window_left, int window_right, int dtype, void *hip_stream) {
   g_err[0] = 0;
-  const char *fn = "fa_fwd_varlen";
   TRY(nonnull(fn, {q, k, v, o, cu_seqlens_q, cu_seqlens_k}));
   TRY(positive(fn, {B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
   if (!fa_fwd_varlen_supported(dtype, D))
-    return fail(FA_ERR_UNSUPPORTED, "fa_fwd_varlen: needs f16 / bf16 and D = 64 | 128, got dtype=%s D=%d", fa_dtype_name(dtype), D);
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 and D = 64 | 128, got dtype=%s D=%d", fn, fa_dtype_name(dtype), D);
   if (max_seqlen_q > total_q || max_seqlen_k > total_k)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen: max_seqlen (%d, %d) exceeds the token count (%d, %d)", max_seqlen_q, max_seqlen_k, total_q, total_k);
+    return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen (%d, %d) exceeds the token count (%d, %d)", fn, max_seqlen_q, max_seqlen_k, total_q, total_k);
   // a token's head is D contiguous elements; rows and heads may interleave either way ([total, H, D], [H, total, D], views of a packed
   // QKV projection), so all that is required of a stride is room for one row and 16-byte alignment of every row
   TRY(varlen_strides_ok(fn, "", D, q_row_stride, q_head_stride, stride_mult(dtype)));
   TRY(varlen_strides_ok(fn, "key/value ", D, kv_row_stride, kv_head_stride, stride_mult(dtype)));
   TRY(aligned16(fn, "tensors", {q, k, v, o}));
-  if (((uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen: cu_seqlens_q / cu_seqlens_k must be int32-aligned");
+  if (((uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q / cu_seqlens_k must be int32-aligned", fn);
   // 32-bit byte offsets inside ONE sequence of one head (its base is a 64-bit address: the tensors themselves may exceed 4 GiB); as in
   // fa_fwd the staging may address up to two 64-key tiles past the end
   TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
   TRY(head_fits(fn, (double)(max_seqlen_k + 128) * (double)kv_row_stride * 2, 4, " (one sequence of max_seqlen_k rows)"));
   TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));
-  fa::VarlenParams p;
+  const int route = window_route(window_left, window_right);
+  fa::VarlenWindowParams p;
   p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
   p.B = B; p.H = Hq; p.Hkv = Hkv; p.N = max_seqlen_q; p.Nk = max_seqlen_k; p.D = D; p.scale = scale;
   p.batch_stride = 0; p.head_stride = q_head_stride; p.kv_batch_stride = 0; p.kv_head_stride = kv_head_stride;
-  p.is_causal = is_causal ? 1 : 0;
+  p.is_causal = route != WIN_FULL;
   p.cu_q = cu_seqlens_q; p.cu_k = cu_seqlens_k;
   p.total_q = total_q; p.total_k = total_k;
   p.q_rs = q_row_stride; p.kv_rs = kv_row_stride;
-  return launched(fn, fa::launch_mfma_varlen(p, dtype, (hipStream_t)hip_stream));
+  if (route != WIN_KERNEL) return launched(fn, fa::launch_mfma_varlen(p, dtype, (hipStream_t)hip_stream));
+  p.wl = window_clamp(window_left, max_seqlen_k);
+  p.wr = window_clamp(window_right, max_seqlen_q);
+  return launched(fn, fa::launch_mfma_varlen_window(p, dtype, (hipStream_t)hip_stream));
+}
+int fa_fwd_varlen(const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q, const int *cu_seqlens_k,
+                  int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
+                  long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride, int is_causal,
+                  int dtype, void *hip_stream) {
+  return varlen_impl("fa_fwd_varlen", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D,
+                     scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride, -1, is_causal ? 0 : -1, dtype, hip_stream);
+}
+int fa_fwd_varlen_window(const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q, const int *cu_seqlens_k,
+                         int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
+                         long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
+                         int window_left, int window_right, int dtype, void *hip_stream) {
+  return varlen_impl("fa_fwd_varlen_window", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q, total_k, max_seqlen_q,
+                     max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride, window_left, window_right, dtype,
+                     hip_stream);
+}
+int fa_window_key_range(int Lq, int Lk, int window_left, int window_right, int row_first, int row_last, int *key_lo, int *key_hi) {
+  g_err[0] = 0;
+  if (!key_lo || !key_hi) return fail(FA_ERR_INVALID_ARG, "fa_window_key_range: null pointer");
+  if (Lq < 0 || Lk < 0) return fail(FA_ERR_INVALID_ARG, "fa_window_key_range: lengths must be >= 0");
+  fa::window_key_range(Lq, Lk, window_left, window_right, row_first, row_last, *key_lo, *key_hi);
+  return FA_OK;
 }
 
 int fa_fwd_decode_supported(int dtype, int D, int Hq, int Hkv, int Nq) {
@@ -498,21 +532,20 @@ long long fa_fwd_decode_paged_workspace_bytes(int B, int Hq, int Hkv, int Nq, in
   if (page_size < 1 || max_pages_per_seq < 1 || (long long)page_size * max_pages_per_seq > (1 << 30)) return 0;
   return fa_fwd_decode_workspace_bytes(B, Hq, Hkv, Nq, page_size * max_pages_per_seq, D);  // the dense decode's at the capacity
 }
-int fa_fwd_decode_paged(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *block_table,
-                        const int *seqlens_k, int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages, int max_pages_per_seq,
-                        float scale, long long q_batch_stride, long long q_head_stride, long long kv_page_stride, long long kv_head_stride,
-                        long long kv_row_stride, long long block_table_stride, int is_causal, int q_dtype, int kv_dtype, void *workspace,
-                        long long workspace_bytes, void *hip_stream) {
+static int decode_paged_impl(const char *fn, const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                             const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages,
+                             int max_pages_per_seq, float scale, long long q_batch_stride, long long q_head_stride, long long kv_page_stride,
+                             long long kv_head_stride, long long kv_row_stride, long long block_table_stride, int window_left,
+                             int window_right, int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes, void *hip_stream) {
   g_err[0] = 0;
-  const char *fn = "fa_fwd_decode_paged";
   TRY(nonnull(fn, {q, k_pages, v_pages, o, block_table, seqlens_k, workspace}));
   TRY(positive(fn, {B, Hq, Hkv, Nq, D, page_size, num_pages, max_pages_per_seq}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
   if (!fa_fwd_decode_paged_supported(q_dtype, kv_dtype, D, Hq, Hkv, Nq, page_size))
-    return fail(FA_ERR_UNSUPPORTED, "fa_fwd_decode_paged: needs (q, kv) dtypes f16/f16, bf16/bf16, e4m3/e4m3 or bf16/e4m3, D = 64 | 128, (Hq / Hkv) * Nq "
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs (q, kv) dtypes f16/f16, bf16/bf16, e4m3/e4m3 or bf16/e4m3, D = 64 | 128, (Hq / Hkv) * Nq "
                 "<= 32 packed query rows and a page size of 16, 32, 64, 128 or 256; got q=%s kv=%s D=%d Hq=%d Hkv=%d Nq=%d page_size=%d",
-                fa_dtype_name(q_dtype), fa_dtype_name(kv_dtype), D, Hq, Hkv, Nq, page_size);
+                fn, fa_dtype_name(q_dtype), fa_dtype_name(kv_dtype), D, Hq, Hkv, Nq, page_size);
   TRY(table_stride_ok(fn, block_table_stride, max_pages_per_seq));
   TRY(strides_ok(fn, "", Nq, D, q_batch_stride, q_head_stride, stride_mult(q_dtype), Hq > 1 && B > 1));
   const int kv8 = kv_dtype == FA_DTYPE_FP8_E4M3;
@@ -521,45 +554,67 @@ int fa_fwd_decode_paged(const void *q, const void *k_pages, const void *v_pages,
   TRY(page_tables_ok(fn, page_size, max_pages_per_seq, block_table, seqlens_k));
   const int cap = page_size * max_pages_per_seq;
   TRY(workspace_fits(fn, workspace_bytes, fa::decode_workspace_bytes(B, Hq, Hkv, Nq, cap, D), "fa_fwd_decode_paged_workspace_bytes"));
-  fa::DecodePagedParams p;
+  const int route = window_route(window_left, window_right);
+  fa::DecodeWindowParams p;
   // Nk = the capacity, hence the dense decode's split rule there: bit-identical to it on full caches
-  TRY(decode_params(fn, p, q, k_pages, v_pages, o, lse, workspace, B, Hq, Hkv, Nq, cap, D, scale, q_batch_stride, q_head_stride, is_causal, kv8));
+  TRY(decode_params(fn, p, q, k_pages, v_pages, o, lse, workspace, B, Hq, Hkv, Nq, cap, D, scale, q_batch_stride, q_head_stride, route != WIN_FULL, kv8));
   p.kv_bs = 0; p.kv_hs = kv_head_stride;
   p.block_table = block_table; p.seqlens = seqlens_k;
   p.page_stride = kv_page_stride; p.row_stride = kv_row_stride;
   p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
   p.lp = log2_of(page_size);
-  return launched(fn, fa::launch_decode_paged(p, D, q_dtype, kv8, (hipStream_t)hip_stream));
+  if (route != WIN_KERNEL) return launched(fn, fa::launch_decode_paged(p, D, q_dtype, kv8, (hipStream_t)hip_stream));
+  p.wl = window_clamp(window_left, cap);
+  p.wr = window_clamp(window_right, Nq);
+  return launched(fn, fa::launch_decode_paged_window(p, D, q_dtype, kv8, (hipStream_t)hip_stream));
+}
+int fa_fwd_decode_paged(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *block_table,
+                        const int *seqlens_k, int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages, int max_pages_per_seq,
+                        float scale, long long q_batch_stride, long long q_head_stride, long long kv_page_stride, long long kv_head_stride,
+                        long long kv_row_stride, long long block_table_stride, int is_causal, int q_dtype, int kv_dtype, void *workspace,
+                        long long workspace_bytes, void *hip_stream) {
+  return decode_paged_impl("fa_fwd_decode_paged", q, k_pages, v_pages, o, lse, block_table, seqlens_k, B, Hq, Hkv, Nq, D, page_size, num_pages,
+                           max_pages_per_seq, scale, q_batch_stride, q_head_stride, kv_page_stride, kv_head_stride, kv_row_stride,
+                           block_table_stride, -1, is_causal ? 0 : -1, q_dtype, kv_dtype, workspace, workspace_bytes, hip_stream);
+}
+int fa_fwd_decode_paged_window(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *block_table,
+                               const int *seqlens_k, int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages,
+                               int max_pages_per_seq, float scale, long long q_batch_stride, long long q_head_stride, long long kv_page_stride,
+                               long long kv_head_stride, long long kv_row_stride, long long block_table_stride, int window_left,
+                               int window_right, int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes, void *hip_stream) {
+  return decode_paged_impl("fa_fwd_decode_paged_window", q, k_pages, v_pages, o, lse, block_table, seqlens_k, B, Hq, Hkv, Nq, D, page_size,
+                           num_pages, max_pages_per_seq, scale, q_batch_stride, q_head_stride, kv_page_stride, kv_head_stride, kv_row_stride,
+                           block_table_stride, window_left, window_right, q_dtype, kv_dtype, workspace, workspace_bytes, hip_stream);
 }
 
 int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size) { return fa::mfma_varlen_paged_supported(dtype, D, page_size); }
-int fa_fwd_varlen_paged(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *cu_seqlens_q,
-                        const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
-                        int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride, long long q_head_stride,
-                        long long kv_page_stride, long long kv_head_stride, long long kv_row_stride, long long block_table_stride,
-                        int is_causal, int dtype, void *hip_stream) {
+static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                             const int *cu_seqlens_q, const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q,
+                             int max_seqlen_q, int D, int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride,
+                             long long q_head_stride, long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                             long long block_table_stride, int window_left, int window_right, int dtype, void *hip_stream) {
   g_err[0] = 0;
-  const char *fn = "fa_fwd_varlen_paged";
   TRY(nonnull(fn, {q, k_pages, v_pages, o, cu_seqlens_q, block_table, seqlens_k}));
   TRY(positive(fn, {B, Hq, Hkv, total_q, max_seqlen_q, D, page_size, num_pages, max_pages_per_seq}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
   if (!fa_fwd_varlen_paged_supported(dtype, D, page_size))
-    return fail(FA_ERR_UNSUPPORTED, "fa_fwd_varlen_paged: needs f16 / bf16 (q and the pool alike), D = 64 | 128 and a page size of 16, 32, 64, 128 or 256; "
-                "got dtype=%s D=%d page_size=%d (an e4m3 pool: fa_fwd_decode_paged)", fa_dtype_name(dtype), D, page_size);
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 (q and the pool alike), D = 64 | 128 and a page size of 16, 32, 64, 128 or 256; "
+                "got dtype=%s D=%d page_size=%d (an e4m3 pool: fa_fwd_decode_paged)", fn, fa_dtype_name(dtype), D, page_size);
   if (max_seqlen_q > total_q)
-    return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen_paged: max_seqlen_q=%d exceeds the token count %d", max_seqlen_q, total_q);
+    return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen_q=%d exceeds the token count %d", fn, max_seqlen_q, total_q);
   TRY(varlen_strides_ok(fn, "", D, q_row_stride, q_head_stride, stride_mult(dtype)));
   TRY(page_pool_ok(fn, D, page_size, max_pages_per_seq, kv_page_stride, kv_head_stride, kv_row_stride, block_table_stride, dtype, block_table, seqlens_k));
   TRY(aligned16(fn, "tensors", {q, k_pages, v_pages, o}));
-  if ((uintptr_t)cu_seqlens_q & 3) return fail(FA_ERR_INVALID_ARG, "fa_fwd_varlen_paged: cu_seqlens_q must be int32-aligned");
+  if ((uintptr_t)cu_seqlens_q & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q must be int32-aligned", fn);
   TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
   TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));
-  fa::VarlenPagedParams p;
+  const int route = window_route(window_left, window_right);
+  fa::VarlenPagedWindowParams p;
   p.q = q; p.k = k_pages; p.v = v_pages; p.o = o; p.lse = lse;
   p.B = B; p.H = Hq; p.Hkv = Hkv; p.N = max_seqlen_q; p.Nk = page_size * max_pages_per_seq; p.D = D; p.scale = scale;
   p.batch_stride = 0; p.head_stride = q_head_stride; p.kv_batch_stride = 0; p.kv_head_stride = kv_head_stride;
-  p.is_causal = is_causal ? 1 : 0;
+  p.is_causal = route != WIN_FULL;
   p.cu_q = cu_seqlens_q; p.cu_k = nullptr;
   p.total_q = total_q; p.total_k = 0;
   p.q_rs = q_row_stride; p.kv_rs = kv_row_stride;
@@ -567,7 +622,28 @@ int fa_fwd_varlen_paged(const void *q, const void *k_pages, const void *v_pages,
   p.page_stride = kv_page_stride;
   p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
   p.lp = log2_of(page_size);
-  return launched(fn, fa::launch_mfma_varlen_paged(p, dtype, (hipStream_t)hip_stream));
+  if (route != WIN_KERNEL) return launched(fn, fa::launch_mfma_varlen_paged(p, dtype, (hipStream_t)hip_stream));
+  p.wl = window_clamp(window_left, p.Nk);
+  p.wr = window_clamp(window_right, max_seqlen_q);
+  return launched(fn, fa::launch_mfma_varlen_paged_window(p, dtype, (hipStream_t)hip_stream));
+}
+int fa_fwd_varlen_paged(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *cu_seqlens_q,
+                        const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                        int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride, long long q_head_stride,
+                        long long kv_page_stride, long long kv_head_stride, long long kv_row_stride, long long block_table_stride,
+                        int is_causal, int dtype, void *hip_stream) {
+  return varlen_paged_impl("fa_fwd_varlen_paged", q, k_pages, v_pages, o, lse, cu_seqlens_q, block_table, seqlens_k, B, Hq, Hkv, total_q,
+                           max_seqlen_q, D, page_size, num_pages, max_pages_per_seq, scale, q_row_stride, q_head_stride, kv_page_stride,
+                           kv_head_stride, kv_row_stride, block_table_stride, -1, is_causal ? 0 : -1, dtype, hip_stream);
+}
+int fa_fwd_varlen_paged_window(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *cu_seqlens_q,
+                               const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                               int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride,
+                               long long q_head_stride, long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                               long long block_table_stride, int window_left, int window_right, int dtype, void *hip_stream) {
+  return varlen_paged_impl("fa_fwd_varlen_paged_window", q, k_pages, v_pages, o, lse, cu_seqlens_q, block_table, seqlens_k, B, Hq, Hkv, total_q,
+                           max_seqlen_q, D, page_size, num_pages, max_pages_per_seq, scale, q_row_stride, q_head_stride, kv_page_stride,
+                           kv_head_stride, kv_row_stride, block_table_stride, window_left, window_right, dtype, hip_stream);
 }
 
 int fa_kv_append_paged(const void *k_new, const void *v_new, void *k_pages, void *v_pages, const int *cu_seqlens_new, const int *block_table,

@@ -66,6 +66,31 @@ struct VarlenPagedParams : VarlenParams {
   int lp;  // log2 of the page size (16 .. 256)
 };
 
+// The sliding window of the *_window entry points (include/fa_mi355.h, "Sliding window"): key j is visible to query i iff
+// i + coff - wl <= j <= i + coff + wr and 0 <= j < Lk, with coff = Lk - Lq; a negative wl / wr leaves that side unbounded. The half-open
+// key range [lo, hi) that rows row_first .. row_last (clamped to the sequence's rows) see together; empty iff lo >= hi. 64-bit
+// arithmetic: any int is a legal argument. fa_window_key_range is this function; the windowed kernels take their first and last tile
+// from it.
+__host__ __device__ inline void window_key_range(int Lq, int Lk, int wl, int wr, int row_first, int row_last, int &lo, int &hi) {
+  const long long coff = (long long)Lk - Lq;
+  const long long r0 = row_first > 0 ? row_first : 0, r1 = row_last < Lq - 1 ? row_last : (long long)Lq - 1;
+  lo = hi = 0;
+  if (r0 > r1 || Lk <= 0) return;
+  const long long a = wl < 0 ? 0 : r0 + coff - wl, b = wr < 0 ? (long long)Lk : r1 + coff + wr + 1;
+  lo = (int)(a < 0 ? 0 : a > Lk ? Lk : a);
+  hi = (int)(b < 0 ? 0 : b > Lk ? Lk : b);
+}
+
+// the windowed modes of csrc/fa_mfma_kernel.hip (fa_fwd_varlen_window, fa_fwd_varlen_paged_window): the un-windowed call's parameters
+// plus both bounds, which the host has made non-negative (an unbounded or oversized side is the smallest value that can never bind: wl
+// <= max keys, wr <= max_seqlen_q -- so that coff - wl and row + coff + wr stay inside an int)
+struct VarlenWindowParams : VarlenParams {
+  int wl, wr;
+};
+struct VarlenPagedWindowParams : VarlenPagedParams {
+  int wl, wr;
+};
+
 // one fa_fwd_decode call (csrc/fa_decode_kernel.hip)
 struct DecodeParams {
   const void *q, *k, *v;
@@ -89,6 +114,12 @@ struct DecodePagedParams : DecodeParams {
   int lp;  // log2 of the page size (16 .. 256)
 };
 
+// one fa_fwd_decode_paged_window call: the paged decode's parameters plus both bounds, made non-negative by the host (wl <= capacity,
+// wr <= Nq: see VarlenWindowParams)
+struct DecodeWindowParams : DecodePagedParams {
+  int wl, wr;
+};
+
 // dtype tags
 struct F32 {};
 struct F16 {};
@@ -104,6 +135,8 @@ hipError_t launch_mfma_varlen(const VarlenParams &p, int dtype, hipStream_t s);
 bool mfma_varlen_supported(int dtype, int D);
 hipError_t launch_mfma_varlen_paged(const VarlenPagedParams &p, int dtype, hipStream_t s);
 bool mfma_varlen_paged_supported(int dtype, int D, int page_size);
+hipError_t launch_mfma_varlen_window(const VarlenWindowParams &p, int dtype, hipStream_t s);
+hipError_t launch_mfma_varlen_paged_window(const VarlenPagedWindowParams &p, int dtype, hipStream_t s);
 // fa_kv_append_paged (csrc/fa_decode_kernel.hip): a byte copy of new K / V rows into their slots of the page pools
 struct AppendPagedParams {
   const void *k_new, *v_new;
@@ -132,6 +165,7 @@ bool decode_supported(int dtype, int D);
 int decode_splits(int B, int Hkv, int Nk, int D, int kv8);  // kv8: e4m3 inputs (one LDS image per item: twice the items per CU)
 long long decode_workspace_bytes(int B, int Hq, int Hkv, int Nq, int Nk, int D);
 hipError_t launch_decode_paged(const DecodePagedParams &p, int D, int dtype, int kv8, hipStream_t s);
+hipError_t launch_decode_paged_window(const DecodeWindowParams &p, int D, int dtype, int kv8, hipStream_t s);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);

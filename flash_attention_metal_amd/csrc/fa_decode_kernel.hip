@@ -74,7 +74,12 @@ __device__ __forceinline__ u32x4 widen8(unsigned w0, unsigned w1) {
 // whose table entry is wave-uniform. The entries of the next tile to stage are loaded one tile ahead.
 template <typename Tag, int D, int QT, bool CAUSAL, bool KV8, typename PRM = DecodeParams>
 __global__ __launch_bounds__(64) void decode_partial_kernel(PRM p) {
-  constexpr bool PAGED = std::is_same<PRM, DecodePagedParams>::value;
+  constexpr bool PAGED = std::is_base_of<DecodePagedParams, PRM>::value;
+  // WINDOW (PRM = DecodeWindowParams, fa_fwd_decode_paged_window; instantiated with CAUSAL): key j is visible to row iq iff
+  // iq + cl <= j <= iq + cu, cl = coff - wl, cu = coff + wr (non-negative bounds from the host). The item's tiles are a share of
+  // [t_lo, nT), the tiles that hold the keys rows 0 .. Nq - 1 see together, instead of [0, nT).
+  constexpr bool WINDOW = std::is_same<PRM, DecodeWindowParams>::value;
+  static_assert(!WINDOW || CAUSAL, "window mode: the upper bound is the causal one with its own offset");
   using M = MD16<Tag>;
   using vec8 = typename M::vec8;
   using elem = typename M::elem;
@@ -101,8 +106,15 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(PRM p) {
   int Nk = p.Nk;  // keys of this item's sequence
   if constexpr (PAGED) Nk = min(max(__builtin_amdgcn_readfirstlane(p.seqlens[b]), 0), p.max_pages << p.lp);
   const int coff = Nk - p.Nq;
-  const int nT = (Nk + BN - 1) / BN;
-  const int t0 = (int)((long long)s * nT / S), t1 = (int)((long long)(s + 1) * nT / S);
+  int cl = 0, cup = coff, k_lo = 0, k_hi = Nk;
+  if constexpr (WINDOW) {
+    cl = coff - p.wl;
+    cup = coff + p.wr;
+    window_key_range(p.Nq, Nk, p.wl, p.wr, 0, p.Nq - 1, k_lo, k_hi);
+    if (k_lo >= k_hi) k_lo = k_hi = 0;
+  }
+  const int nT = (k_hi + BN - 1) / BN, t_lo = k_lo / BN, nW = nT - t_lo;
+  const int t0 = t_lo + (int)((long long)s * nW / S), t1 = t_lo + (int)((long long)(s + 1) * nW / S);
 
   const long long base_kv = PAGED ? 0 : (long long)b * p.kv_bs + (long long)hkv * p.kv_hs;
   constexpr int EB = KV8 ? 1 : 2;  // bytes per input element
@@ -114,12 +126,14 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(PRM p) {
   const float c2 = p.scale * 1.4426950408889634f;
   vec8 qf[QT][KS];
   int rlim[QT];  // last visible key of the lane's rows (causal; Nk - 1 otherwise and for padding rows)
+  int rlo[QT];   // window mode: their first visible key (0 for padding rows)
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
     const int r = 16 * qt + c;
     const int gi = r / p.Nq, iq = r - gi * p.Nq;
     const bool valid = r < R;
-    rlim[qt] = (CAUSAL && valid) ? iq + coff : Nk - 1;
+    rlim[qt] = (CAUSAL && valid) ? iq + cup : Nk - 1;
+    rlo[qt] = (WINDOW && valid) ? iq + cl : 0;
     const long long qoff = (long long)b * p.q_bs + (long long)(hkv * G + gi) * p.q_hs + (long long)iq * D;
     const elem *qp = (const elem *)p.q + qoff;
 #pragma unroll
@@ -331,14 +345,15 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(PRM p) {
         }
       }
       // ---- mask: key > the row's limit (causal, bottom-right aligned) or key >= Nk
-      if (kv0 + BN > Nk || (CAUSAL && kv0 + BN - 1 > coff)) {
+      if (kv0 + BN > Nk || (CAUSAL && kv0 + BN - 1 > cup) || (WINDOW && kv0 < p.Nq - 1 + cl)) {
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
           const int lim = min(rlim[qt], Nk - 1) - kv0 - 4 * g;
+          const int llo = rlo[qt] - kv0 - 4 * g;  // (window mode)
 #pragma unroll
           for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) sc[kt][qt][i] = (16 * kt + i > lim) ? -INFINITY : sc[kt][qt][i];
+            for (int i = 0; i < 4; ++i) sc[kt][qt][i] = (16 * kt + i > lim || (WINDOW && 16 * kt + i < llo)) ? -INFINITY : sc[kt][qt][i];
         }
       }
       // ---- exact online softmax (a row whose keys are all masked so far keeps m = -inf, l = 0: the guard avoids inf - inf)
@@ -565,6 +580,39 @@ hipError_t launch_decode_paged(const DecodePagedParams &p0, int D, int dtype, in
   if (kv8 || dtype == FA_DTYPE_FP8_E4M3) {
     if (D == 64) return QT == 1 ? launch_decode_paged_q<BF16, 64, 1, true>(p, s) : launch_decode_paged_q<BF16, 64, 2, true>(p, s);
     if (D == 128) return QT == 1 ? launch_decode_paged_q<BF16, 128, 1, true>(p, s) : launch_decode_paged_q<BF16, 128, 2, true>(p, s);
+    return hipErrorInvalidValue;
+  }
+  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
+}
+
+// fa_fwd_decode_paged_window: the paged partial kernel in window mode, then the paged combine kernel as it is (empty splits, rows with
+// no visible key)
+template <typename Tag, int D, int QT, bool KV8 = false>
+static hipError_t launch_decode_window_q(const DecodeWindowParams &p, hipStream_t s) {
+  const size_t smem = ((KV8 || FA_DECODE_REGSTAGE) ? 2 : 4) * (size_t)BN * D * 2;
+  (void)hipGetLastError();
+  auto kern = decode_partial_kernel<Tag, D, QT, true, KV8, DecodeWindowParams>;
+  if (smem > 48 * 1024) { hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem); if (e != hipSuccess) return e; }
+  hipLaunchKernelGGL(kern, dim3(p.B * p.Hkv * p.S), dim3(64), smem, s, p);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((decode_combine_kernel<Tag, D, QT, true>), dim3(p.B * p.Hq * p.Nq), dim3(64), 0, s, (const DecodeParams &)p);
+  return hipGetLastError();
+}
+
+hipError_t launch_decode_paged_window(const DecodeWindowParams &p0, int D, int dtype, int kv8, hipStream_t s) {
+  DecodeWindowParams p = p0;
+  p.q8 = (dtype == FA_DTYPE_FP8_E4M3);
+  const int R = (p.Hq / p.Hkv) * p.Nq, QT = (R + 15) / 16;
+  auto go = [&](auto tag) -> hipError_t {
+    using Tag = decltype(tag);
+    if (D == 64) return QT == 1 ? launch_decode_window_q<Tag, 64, 1>(p, s) : launch_decode_window_q<Tag, 64, 2>(p, s);
+    if (D == 128) return QT == 1 ? launch_decode_window_q<Tag, 128, 1>(p, s) : launch_decode_window_q<Tag, 128, 2>(p, s);
+    return hipErrorInvalidValue;
+  };
+  if (kv8 || dtype == FA_DTYPE_FP8_E4M3) {
+    if (D == 64) return QT == 1 ? launch_decode_window_q<BF16, 64, 1, true>(p, s) : launch_decode_window_q<BF16, 64, 2, true>(p, s);
+    if (D == 128) return QT == 1 ? launch_decode_window_q<BF16, 128, 1, true>(p, s) : launch_decode_window_q<BF16, 128, 2, true>(p, s);
     return hipErrorInvalidValue;
   }
   return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});

@@ -110,8 +110,15 @@ __device__ __forceinline__ int paged_capacity(const VarlenPagedParams &p) { retu
 __device__ __forceinline__ int paged_capacity(const Params &) { return 0; }
 template <typename Tag, int D, bool CAUSAL, int SPLIT, bool PRESC, int ROWS = BM, typename PT = Params>
 __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
-  constexpr bool PAGEDV = std::is_same<PT, VarlenPagedParams>::value;
-  constexpr bool VARLEN = std::is_same<PT, VarlenParams>::value || PAGEDV;
+  constexpr bool PAGEDV = std::is_base_of<VarlenPagedParams, PT>::value;
+  constexpr bool VARLEN = std::is_base_of<VarlenParams, PT>::value;
+  // WINDOW (PT = VarlenWindowParams / VarlenPagedWindowParams; fa_fwd_varlen_window, fa_fwd_varlen_paged_window): the varlen modes under
+  // a sliding window, key j visible to query i iff i + cl <= j <= i + cu with cl = coff - wl, cu = coff + wr (both bounds run-time
+  // scalars, made non-negative by the host). Instantiated with CAUSAL: cu takes coff's place wherever the mask's upper limit is used,
+  // and the lower limit is new -- the tile loop starts at the tile of the block's first row's bound, a wave skips tiles wholly below
+  // ITS first row's bound, and its first ACTIVE tile takes the exact path.
+  constexpr bool WINDOW = std::is_same<PT, VarlenWindowParams>::value || std::is_same<PT, VarlenPagedWindowParams>::value;
+  static_assert(!WINDOW || CAUSAL, "window mode: the upper bound is the causal one with its own offset");
   static_assert(!VARLEN || (SPLIT == 1 && ROWS == BM && PRESC && !std::is_same<Tag, FP8>::value && (D == 64 || D == 128)),
                 "varlen mode: the plain 128-row kernel, 16-bit inputs, LDS-DMA staging");
   constexpr int RW = ROWS / WM;   // row groups = waves per split
@@ -133,7 +140,8 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   constexpr int NCH = BN * (GRB / 16) / ST;  // staged 16-byte global chunks per thread per tile
   // (varlen without the mask keeps the prefetch and three workgroups: at 128 registers its extra row pitch and sequence base spill 20 B,
   // some of it reloaded inside the tile loop. The MFMA order is the same in both forms, so the results do not change.)
-  constexpr bool MAIN4 = (FA_MAIN_OCC4 != 0) && main_kernel_occ4<Tag, D, PRESC>() && SPLIT == 1 && ROWS == BM && !(VARLEN && !CAUSAL);
+  // (window mode: three as well -- two more live scalars and a second compare per masked score)
+  constexpr bool MAIN4 = (FA_MAIN_OCC4 != 0) && main_kernel_occ4<Tag, D, PRESC>() && SPLIT == 1 && ROWS == BM && !(VARLEN && !CAUSAL) && !WINDOW;
   constexpr bool VPRE = (D == 64) && !IS_FP8 && !MAIN4;  // prefetch V^T fragments under the QK^T MFMAs
   // Pre-scaled operand (f16/bf16): the Q fragments are multiplied by c = scale.log2(e) and rounded back to the input
   // type ONCE per block, and the running reference -m (log2 units) is the C operand of the first MFMA of every score
@@ -175,6 +183,8 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   unsigned qrb = 0, kvrb = 0;  // row pitch of Q / O and of K / V in global memory, bytes
   long long lse_base = 0;      // first LSE element of this block's (head, sequence)
   const int *ptbl = nullptr;   // varlen paged: this sequence's row of the block table
+  int cl = 0, cu = 0;          // window mode: key j is visible to row i iff i + cl <= j <= i + cu
+  int t_lo = 0, kv_hi = 0;     // window mode: the block's first tile and the end of its key range
 #define FA_NQ (VARLEN ? LQ : p.N)
 #define FA_NK (VARLEN ? LK : p.Nk)
   if constexpr (VARLEN) {
@@ -197,7 +207,16 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
     kvrb = (unsigned)p.kv_rs * 2;
     // no key is visible to any row of the block (no keys at all, or causal with Lk < Lq: key j is visible to query i iff
     // j <= i + Lk - Lq): O = 0, LSE = -inf, as the paged decode defines it
-    if ((CAUSAL ? min(LK, qb * ROWS + ROWS + LK - LQ) : LK) <= 0) {
+    // (window mode: the block's rows see keys [k_lo, kv_hi) together; none when the range is empty: kv_hi = 0 then)
+    if constexpr (WINDOW) {
+      int k_lo;
+      window_key_range(LQ, LK, p.wl, p.wr, qb * ROWS, qb * ROWS + ROWS - 1, k_lo, kv_hi);
+      cl = LK - LQ - p.wl;
+      cu = LK - LQ + p.wr;
+      t_lo = k_lo / BN;
+      if (k_lo >= kv_hi) kv_hi = 0;
+    }
+    if ((WINDOW ? kv_hi : CAUSAL ? min(LK, qb * ROWS + ROWS + LK - LQ) : LK) <= 0) {
       elem *Oz = (elem *)p.o + base;
       for (int idx = threadIdx.x; idx < ROWS * CPR; idx += NTHREADS) {
         const int row = qb * ROWS + idx / CPR, ch = idx % CPR;
@@ -213,6 +232,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   // grouped-query heads: query head h reads key/value head h / (H / Hkv); Nk keys per head.
   // Causal with Nq != Nk is bottom-right aligned: key j visible to query i iff j <= i + coff (varlen: coff may be negative).
   const int coff = FA_NK - FA_NQ;
+  const int cup = WINDOW ? cu : coff;  // the upper limit's offset
   const int q0 = qb * ROWS;
   const int qw0 = q0 + wave * WM;  // first query row of this wave
   const int qrow = qw0 + r;
@@ -302,7 +322,9 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
     }
   }
 
-  const int kv_end = CAUSAL ? min(FA_NK, q0 + ROWS + coff) : FA_NK;  // (varlen: >= 1 here)
+  const int kv_end = WINDOW ? kv_hi : CAUSAL ? min(FA_NK, q0 + ROWS + coff) : FA_NK;  // (varlen: >= 1 here)
+  const int tb = WINDOW ? t_lo : 0;                             // the block's first tile
+  const int tfw = WINDOW ? max(0, qw0 + cl) / BN : sp;          // this wave's first active tile (the exact path's "first tile")
   const int nT = (kv_end + BN - 1) / BN;
 
   // LDS-DMA staging (FA_MFMA_DMA): wave w of a split moves the 1-KiB pieces w, w + RW, ... of each tile; inside a piece the
@@ -432,8 +454,8 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   if constexpr (PRE) asm volatile("" : "+v"(negm));  // opaque: else hipcc re-materialises the splat in front of every MFMA
 
   if constexpr (DMA) {
-    if constexpr (PAGEDV) fetch_pages(0);
-    stage_dma(sp, 0);
+    if constexpr (PAGEDV) fetch_pages(tb);
+    stage_dma(tb + sp, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   } else {
     if constexpr (DMA_K8) stage_dma_k8(sp, 0);
@@ -488,11 +510,12 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         int lim = FA_NK - 1 - kv0 - 32 * kb - 4 * h;
-        if (CAUSAL) lim = min(lim, qrow + coff - kv0 - 32 * kb - 4 * h);
+        if (CAUSAL) lim = min(lim, qrow + cup - kv0 - 32 * kb - 4 * h);
+        const int llo = qrow + cl - kv0 - 32 * kb - 4 * h;  // (window mode)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int kpart = (i & 3) + 8 * (i >> 2);
-          s[kb][i] = (kpart > lim) ? -INFINITY : s[kb][i];
+          s[kb][i] = (kpart > lim || (WINDOW && kpart < llo)) ? -INFINITY : s[kb][i];
         }
       }
     }
@@ -513,7 +536,8 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
 
     // whole-tile skip per wave (kernels.metal:682 with Br = 32): every key of
     // the tile is past this wave's last query row
-    const bool wave_active = (SPLIT == 1 || t < nT) && (!CAUSAL || (kv0 <= qw0 + WM - 1 + coff));
+    // (window mode: or every key of the tile is below this wave's first row's bound)
+    const bool wave_active = (SPLIT == 1 || t < nT) && (!CAUSAL || (kv0 <= qw0 + WM - 1 + cup)) && (!WINDOW || (kv0 + BN - 1 >= qw0 + cl));
     if (wave_active) {
       const lds_char *Kt = Kbuf + buf * KTILE;  // (fp8 score path only)
       (void)Kt;
@@ -600,21 +624,23 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         }
       }
       // ---- mask (only on tiles that cross the diagonal or the end of the sequence)
-      const bool need_mask = (CAUSAL && (kv0 + BN - 1 > qw0 + coff)) || (kv0 + BN > FA_NK);
+      // (window mode: or holds keys below the wave's last row's bound)
+      const bool need_mask = (CAUSAL && (kv0 + BN - 1 > qw0 + cup)) || (kv0 + BN > FA_NK) || (WINDOW && (kv0 < qw0 + WM - 1 + cl));
       if (need_mask) {
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
           // masked iff key > qrow (kernels.metal:748) or key >= N. A 32 x 32 block whose every key is visible to every
           // row of the wave needs no work (wave-uniform test: of the two blocks of a diagonal tile one is of this
           // kind or entirely masked): key offsets inside the block span 0..31, the wave's rows qw0..qw0+31.
-          const int xw = min(FA_NK - 1 - kv0 - 32 * kb, CAUSAL ? qw0 + coff - kv0 - 32 * kb : 0x7fffffff);
-          if (xw >= 31) continue;
+          const int xw = min(FA_NK - 1 - kv0 - 32 * kb, CAUSAL ? qw0 + cup - kv0 - 32 * kb : 0x7fffffff);
+          if (xw >= 31 && (!WINDOW || kv0 + 32 * kb >= qw0 + WM - 1 + cl)) continue;
           int lim = FA_NK - 1 - kv0 - 32 * kb - 4 * h;
-          if (CAUSAL) lim = min(lim, qrow + coff - kv0 - 32 * kb - 4 * h);
+          if (CAUSAL) lim = min(lim, qrow + cup - kv0 - 32 * kb - 4 * h);
+          const int llo = qrow + cl - kv0 - 32 * kb - 4 * h;  // (window mode: masked iff key < qrow + cl as well)
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const int kpart = (i & 3) + 8 * (i >> 2);
-            s[kb][i] = (kpart > lim) ? -INFINITY : s[kb][i];
+            s[kb][i] = (kpart > lim || (WINDOW && kpart < llo)) ? -INFINITY : s[kb][i];
           }
         }
       }
@@ -634,8 +660,8 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
       // -inf -- the wave takes the exact path: recompute the scores (they were overwritten by P; K is still in LDS),
       // take the row max, rescale O and l, form P again. Saves the 16 v_max3 + swap + compare of every tile
       // (141 -> 118 VALU per 16 MFMAs at head_dim 64); m, l and O stay mutually consistent, LSE = m.scale + ln(l) is exact.
-      bool exact = (t == sp);  // this split's first tile
-      if (t != sp) {
+      bool exact = (t == tfw);  // this split's first tile (window mode: this wave's first active tile)
+      if (t != tfw) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           if constexpr (PRE) {  // the matrix core has already subtracted m
@@ -666,6 +692,8 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         // varlen, causal with Lk < Lq: a row that sees no key at all has every score masked. A finite floor keeps its reference
         // finite (-inf - -inf would be a NaN in alpha and in P): its P and l stay exactly 0 and the epilogue writes O = 0, LSE = -inf.
         // Any row with a visible key has a finite max already, so nothing changes for it.
+        // (window mode: the later rows of a wave can have every score of the wave's first active tile below their bound. The same floor:
+        // their next tile's sums overflow the threshold and take the exact path, which drops the floor for the true maximum.)
         if constexpr (VARLEN && CAUSAL) mx = fmaxf(mx, -3.4028234663852886e38f);
         // deferred row max (T13): O and l are rescaled only when some row's tile max exceeds the running
         // reference m by more than 2^THR (log2 domain); otherwise p = exp2(c.s - c.m) <= 2^THR with the
@@ -767,10 +795,10 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
     }
     __syncthreads();
   };
-  const int steps = (nT + SPLIT - 1) / SPLIT;  // every wave runs the same number of steps (one barrier each)
+  const int steps = (nT - tb + SPLIT - 1) / SPLIT;  // every wave runs the same number of steps (one barrier each)
   for (int j = 0; j < steps; j += 2) {
-    tile(std::integral_constant<int, 0>{}, j * SPLIT + sp);
-    if (j + 1 < steps) tile(std::integral_constant<int, 1>{}, (j + 1) * SPLIT + sp);
+    tile(std::integral_constant<int, 0>{}, tb + j * SPLIT + sp);
+    if (j + 1 < steps) tile(std::integral_constant<int, 1>{}, tb + (j + 1) * SPLIT + sp);
   }
 
   if constexpr (SPLIT == 2) {
@@ -814,7 +842,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
     // (coff through an opaque copy: hipcc otherwise keeps the loop's qrow + coff alive for this one test -- a spill at 128 registers)
     bool no_key = false;
     if constexpr (VARLEN && CAUSAL) {
-      int coff_e = coff;
+      int coff_e = cup;
       asm volatile("" : "+s"(coff_e));
       no_key = qrow + coff_e < 0;
     }
@@ -890,6 +918,16 @@ constexpr int varlen_paged_occupancy() {
 template <typename Tag, int D, bool CAUSAL>
 __global__ __launch_bounds__(NTHREADS, (varlen_paged_occupancy<D, CAUSAL>())) void fwd_mfma_varlen_paged_kernel(VarlenPagedParams p) {
   fwd_mfma_body<Tag, D, CAUSAL, 1, true, BM, VarlenPagedParams>(p);
+}
+
+// fa_fwd_varlen_window / fa_fwd_varlen_paged_window: the two varlen modes in window mode, at the occupancy of the unmasked varlen kernels
+template <typename Tag, int D>
+__global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_window_kernel(VarlenWindowParams p) {
+  fwd_mfma_body<Tag, D, true, 1, true, BM, VarlenWindowParams>(p);
+}
+template <typename Tag, int D>
+__global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_window_paged_kernel(VarlenPagedWindowParams p) {
+  fwd_mfma_body<Tag, D, true, 1, true, BM, VarlenPagedWindowParams>(p);
 }
 
 // ---------------------------------------------------------------------------
@@ -992,6 +1030,44 @@ hipError_t launch_mfma_varlen_paged(const VarlenPagedParams &p, int dtype, hipSt
     using Tag = decltype(tag);
     if (p.D == 64) return p.is_causal ? launch_varlen_paged_one<Tag, 64, true>(p, s) : launch_varlen_paged_one<Tag, 64, false>(p, s);
     if (p.D == 128) return p.is_causal ? launch_varlen_paged_one<Tag, 128, true>(p, s) : launch_varlen_paged_one<Tag, 128, false>(p, s);
+    return hipErrorInvalidValue;
+  };
+  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
+}
+
+// Window mode: the grids, LDS and issue order of the two varlen launchers (the causal order: heaviest-first is harmless where the blocks
+// weigh the same)
+template <typename PT, typename K>
+static hipError_t launch_window_one(K kern, const PT &p, int D, hipStream_t s) {
+  const int nQ = (p.N + BM - 1) / BM;
+  const size_t smem = 4 * BN * (size_t)(D * 2);
+  if (smem > 48 * 1024) {
+    hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem);
+    if (e != hipSuccess) return e;
+  }
+  PT pp = p;
+  pp.head_group = causal_head_group(p, D, 2);
+  set_block_divisors(pp, nQ, pp.head_group);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(kern, dim3(nQ * p.B * p.H), dim3(NTHREADS), smem, s, pp);
+  return hipGetLastError();
+}
+
+hipError_t launch_mfma_varlen_window(const VarlenWindowParams &p, int dtype, hipStream_t s) {
+  auto go = [&](auto tag) -> hipError_t {
+    using Tag = decltype(tag);
+    if (p.D == 64) return launch_window_one(fwd_mfma_window_kernel<Tag, 64>, p, 64, s);
+    if (p.D == 128) return launch_window_one(fwd_mfma_window_kernel<Tag, 128>, p, 128, s);
+    return hipErrorInvalidValue;
+  };
+  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
+}
+
+hipError_t launch_mfma_varlen_paged_window(const VarlenPagedWindowParams &p, int dtype, hipStream_t s) {
+  auto go = [&](auto tag) -> hipError_t {
+    using Tag = decltype(tag);
+    if (p.D == 64) return launch_window_one(fwd_mfma_window_paged_kernel<Tag, 64>, p, 64, s);
+    if (p.D == 128) return launch_window_one(fwd_mfma_window_paged_kernel<Tag, 128>, p, 128, s);
     return hipErrorInvalidValue;
   };
   return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});

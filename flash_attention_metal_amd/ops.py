@@ -230,6 +230,23 @@ def flash_attention_decode(
     return out, lse
 
 
+def _window(window, is_causal: bool) -> Tuple[int, int]:
+    """(window_left, window_right) of a *_window entry point (include/fa_mi355.h, "Sliding window"): negative = unbounded on that side.
+    is_causal=True turns an unbounded right side into 0 and refuses any other right side that is not 0."""
+    try:
+        left, right = (int(x) for x in window)
+    except (TypeError, ValueError):
+        raise ValueError(f"window must be a (left, right) pair of ints, got {window!r}") from None
+    if max(left, right) > 2 ** 31 - 1:
+        raise ValueError(f"window sides are ints up to 2**31 - 1, got {window!r}")
+    left, right = max(left, -1), max(right, -1)
+    if is_causal:
+        if right > 0:
+            raise ValueError(f"is_causal=True needs window right side 0 (or negative: then it is 0), got {right}")
+        right = 0
+    return left, right
+
+
 def decode_paged_workspace_bytes(B: int, Hq: int, Hkv: int, Nq: int, D: int, page_size: int, max_pages_per_seq: int) -> int:
     return int(load_library().fa_fwd_decode_paged_workspace_bytes(B, Hq, Hkv, Nq, D, page_size, max_pages_per_seq))
 
@@ -248,13 +265,16 @@ def flash_attention_decode_paged(
     lse: Optional[torch.Tensor] = None,
     workspace: Optional[torch.Tensor] = None,
     stream: Optional[int] = None,
+    window: Optional[Tuple[int, int]] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """A decode step against a paged KV cache (include/fa_mi355.h fa_fwd_decode_paged): q [B,Hq,Nq,D]; k_pages / v_pages one pool
     each, [num_pages, Hkv, P, D] (layout "HND") or [num_pages, P, Hkv, D] ("NHD"), P in {16, 32, 64, 128, 256}; block_table int32
     [B, max_pages_per_seq] and seqlens_k int32 [B], both contiguous on q's device and read by the kernels only -- nothing here
     synchronises or reads device values, so the call can be captured in a graph and replayed after the tables change in place.
     dtypes as flash_attention_decode (f16, bf16, e4m3, or bf16 queries on an e4m3 pool). A row with no visible key gets O = 0 and
-    LSE = -inf. `workspace`: a uint8 device tensor of at least decode_paged_workspace_bytes(...) bytes (allocated here if None)."""
+    LSE = -inf. `workspace`: a uint8 device tensor of at least decode_paged_workspace_bytes(...) bytes (allocated here if None).
+    window=(left, right): a sliding window (fa_fwd_decode_paged_window: key j visible to query i iff i + L_b - Nq - left <= j <=
+    i + L_b - Nq + right; negative = unbounded; with is_causal=True right must be 0 or negative). None: the call above, untouched."""
     lib = load_library()
     if q.dim() != 4 or k_pages.dim() != 4 or k_pages.shape != v_pages.shape:
         raise ValueError("q [B,Hq,Nq,D], k_pages / v_pages one [num_pages,Hkv,P,D] (HND) or [num_pages,P,Hkv,D] (NHD) shape")
@@ -283,9 +303,10 @@ def flash_attention_decode_paged(
     max_pages = block_table.shape[1]
     out, lse = _out(out, q, qs), _lse(lse, return_lse, q)
     ws = _workspace(workspace, decode_paged_workspace_bytes(B, Hq, Hkv, Nq, D, P, max(max_pages, 1)), q.device)
-    _call(lib, "fa_fwd_decode_paged",
+    mask = (int(bool(is_causal)),) if window is None else _window(window, is_causal)
+    _call(lib, "fa_fwd_decode_paged" if window is None else "fa_fwd_decode_paged_window",
           (q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(), _ptr(lse), block_table.data_ptr(), seqlens_k.data_ptr(),
-           B, Hq, Hkv, Nq, D, P, num_pages, max_pages, _scale(scale, D), *qs, ps, hs, rs, block_table.stride(0), int(bool(is_causal)),
+           B, Hq, Hkv, Nq, D, P, num_pages, max_pages, _scale(scale, D), *qs, ps, hs, rs, block_table.stride(0), *mask,
            _TORCH2FA[q.dtype], _TORCH2FA[k_pages.dtype], ws.data_ptr(), ws.numel()), q.device, stream)
     return out, lse
 
@@ -308,6 +329,7 @@ def flash_attention_varlen(
     out: Optional[torch.Tensor] = None,
     lse: Optional[torch.Tensor] = None,
     stream: Optional[int] = None,
+    window: Optional[Tuple[int, int]] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """The forward over packed variable-length sequences (include/fa_mi355.h fa_fwd_varlen): q [total_q, Hq, D], k / v
     [total_k, Hkv, D], f16 / bf16, D = 64 | 128. Strides are taken from the tensors: any view with unit element stride works ([H, total, D]
@@ -316,7 +338,10 @@ def flash_attention_varlen(
     graph and replayed after the tables change in place (same B, totals and max_seqlen_*). Sequence b owns query tokens
     cu_seqlens_q[b] .. cu_seqlens_q[b+1) and attends to keys cu_seqlens_k[b] .. cu_seqlens_k[b+1); causal is bottom-right aligned per
     sequence; a row with no visible key gets O = 0 and LSE = -inf; tokens at or past cu_seqlens_q[B] and rows beyond max_seqlen_q of a
-    sequence are not written. Returns (out, lse): out like q ([total_q, Hq, D], q's strides unless `out` is given), lse [Hq, total_q]."""
+    sequence are not written. window=(left, right): a sliding window (fa_fwd_varlen_window: key j visible to query i iff
+    i + Lk_b - Lq_b - left <= j <= i + Lk_b - Lq_b + right; negative = unbounded; with is_causal=True right must be 0 or negative);
+    None: the call above, untouched. Returns (out, lse): out like q ([total_q, Hq, D], q's strides unless `out` is given), lse
+    [Hq, total_q]."""
     lib = load_library()
     if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape:
         raise ValueError(f"q [total_q,Hq,D] and k, v one [total_k,Hkv,D] shape, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
@@ -346,10 +371,11 @@ def flash_attention_varlen(
         lse = torch.empty((Hq, total_q), dtype=torch.float32, device=q.device) if return_lse else None
     elif not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.shape != (Hq, total_q):
         raise ValueError("lse must be contiguous fp32 [Hq, total_q] on q's device")
-    _call(lib, "fa_fwd_varlen",
+    mask = (int(bool(is_causal)),) if window is None else _window(window, is_causal)
+    _call(lib, "fa_fwd_varlen" if window is None else "fa_fwd_varlen_window",
           (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
            B, Hq, Hkv, total_q, total_k, int(max_seqlen_q), int(max_seqlen_k), D, _scale(scale, D), q.stride(0), q.stride(1),
-           k.stride(0), k.stride(1), int(bool(is_causal)), _TORCH2FA[q.dtype]), q.device, stream)
+           k.stride(0), k.stride(1), *mask, _TORCH2FA[q.dtype]), q.device, stream)
     return out, lse
 
 
@@ -399,6 +425,7 @@ def flash_attention_varlen_paged(
     out: Optional[torch.Tensor] = None,
     lse: Optional[torch.Tensor] = None,
     stream: Optional[int] = None,
+    window: Optional[Tuple[int, int]] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Packed queries against a paged KV cache (include/fa_mi355.h fa_fwd_varlen_paged): chunked prefill, prefix caching, verification of
     many speculated tokens. q [total_q, Hq, D] as in flash_attention_varlen (any view with a unit element stride), cu_seqlens_q int32
@@ -408,7 +435,8 @@ def flash_attention_varlen_paged(
     chunked-prefill step. The tables are read by the kernel only -- nothing here synchronises or reads device values, so the call can be
     captured in a graph and replayed after the tables change in place. A row with no visible key gets O = 0 and LSE = -inf; tokens at or
     past cu_seqlens_q[B] and rows beyond max_seqlen_q of a sequence are not written. An inference path: no torch custom op and no
-    backward. Returns (out, lse): out like q, lse [Hq, total_q]."""
+    backward. window=(left, right): a sliding window as in flash_attention_varlen, with seqlens_k[b] in Lk_b's place
+    (fa_fwd_varlen_paged_window); None: the call above, untouched. Returns (out, lse): out like q, lse [Hq, total_q]."""
     lib = load_library()
     entry = "flash_attention_varlen_paged"
     if q.dim() != 3:
@@ -432,10 +460,11 @@ def flash_attention_varlen_paged(
         lse = torch.empty((Hq, total_q), dtype=torch.float32, device=q.device) if return_lse else None
     elif not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.shape != (Hq, total_q):
         raise ValueError("lse must be contiguous fp32 [Hq, total_q] on q's device")
-    _call(lib, "fa_fwd_varlen_paged",
+    mask = (int(bool(is_causal)),) if window is None else _window(window, is_causal)
+    _call(lib, "fa_fwd_varlen_paged" if window is None else "fa_fwd_varlen_paged_window",
           (q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), block_table.data_ptr(),
            seqlens_k.data_ptr(), B, Hq, Hkv, total_q, int(max_seqlen_q), D, P, num_pages, block_table.shape[1], _scale(scale, D),
-           q.stride(0), q.stride(1), ps, hs, rs, block_table.stride(0), int(bool(is_causal)), _TORCH2FA[q.dtype]), q.device, stream)
+           q.stride(0), q.stride(1), ps, hs, rs, block_table.stride(0), *mask, _TORCH2FA[q.dtype]), q.device, stream)
     return out, lse
 
 

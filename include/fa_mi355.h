@@ -296,6 +296,54 @@ int fa_fwd_varlen_paged(const void *q, const void *k_pages, const void *v_pages,
                         long long block_table_stride, int is_causal, int dtype, void *hip_stream);
 int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size);
 /*
+ * Sliding window: fa_fwd_varlen_window, fa_fwd_varlen_paged_window and fa_fwd_decode_paged_window are fa_fwd_varlen,
+ * fa_fwd_varlen_paged and fa_fwd_decode_paged with `is_causal` replaced by two ints, window_left (wl) and window_right (wr). With
+ * coff = Lk_b - Lq_b (paged: L_b - Lq_b; decode: L_b - Nq), key j is visible to query i of its sequence iff
+ *     i + coff - wl <= j <= i + coff + wr   and   0 <= j < Lk_b.
+ * A negative value leaves that side unbounded: (-1, -1) is the full operator, (-1, 0) bottom-right causal, (W - 1, 0) a causal window
+ * of W keys, (W, W) a symmetric band. Every non-negative int up to INT_MAX is legal: the host replaces an unbounded side, and any
+ * width that can never bind (wl above the most keys a sequence of the call can hold -- max_seqlen_k or the capacity --, wr above
+ * max_seqlen_q / Nq), by that smallest never-binding width, so the kernels' 32-bit index arithmetic cannot wrap (CLAMPED ON THE HOST;
+ * fa_window_key_range itself computes in 64 bits). A row with no visible key (i + coff + wr < 0, or Lk_b = 0) gets O = 0 exactly and
+ * LSE = -inf. Everything else -- layouts, strides, tables and their clamping, what is written, every argument rule and its status code,
+ * the support tables (fa_fwd_varlen_supported, fa_fwd_varlen_paged_supported, fa_fwd_decode_paged_supported), the decode workspace
+ * (fa_fwd_decode_paged_workspace_bytes), tolerances and "LSE accuracy" -- is the un-windowed entry point's.
+ * ROUTING IS BY SIGN ONLY: (wl < 0, wr < 0) and (wl < 0, wr == 0) launch the kernels of the un-windowed call without / with the mask
+ * and are bit-identical to it; every other pair launches the windowed kernels, however large its values. Through those, (INT_MAX, 0)
+ * is bit-identical to the causal call and (INT_MAX, INT_MAX) to the full one on every sequence with Lk_b >= Lq_b >= 1.
+ * The 128-row kernels walk the 64-key tiles [lo / 64, ceil(hi / 64)) of each 128-row block, [lo, hi) being fa_window_key_range of the
+ * block's rows. The decode divides tiles [t_lo, nT) over its S key splits, t_lo = max(0, L_b - Nq - wl) / 64 and nT =
+ * ceil(min(L_b, L_b + wr) / 64): split s takes tiles t_lo + floor(s n / S) .. t_lo + floor((s + 1) n / S), n = nT - t_lo (the
+ * un-windowed rule at t_lo = 0). Keys outside [lo, hi) of every block of a sequence are never read.
+ */
+int fa_fwd_varlen_window(const void *q, const void *k, const void *v, void *o, float *lse,
+                         const int *cu_seqlens_q, const int *cu_seqlens_k,
+                         int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k,
+                         int D, float scale, long long q_row_stride, long long q_head_stride,
+                         long long kv_row_stride, long long kv_head_stride,
+                         int window_left, int window_right, int dtype, void *hip_stream);
+int fa_fwd_varlen_paged_window(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                               const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                               int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                               int page_size, int num_pages, int max_pages_per_seq, float scale,
+                               long long q_row_stride, long long q_head_stride,
+                               long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                               long long block_table_stride, int window_left, int window_right, int dtype, void *hip_stream);
+int fa_fwd_decode_paged_window(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                               const int *block_table, const int *seqlens_k,
+                               int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages, int max_pages_per_seq,
+                               float scale, long long q_batch_stride, long long q_head_stride,
+                               long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                               long long block_table_stride, int window_left, int window_right, int q_dtype, int kv_dtype,
+                               void *workspace, long long workspace_bytes, void *hip_stream);
+/*
+ * The half-open key range [*key_lo, *key_hi) that rows row_first .. row_last (clamped to 0 .. Lq - 1) of a sequence of Lq queries and Lk
+ * keys see together under (window_left, window_right); empty iff *key_lo >= *key_hi. Host only, no device needed; any int is a legal
+ * window or row (64-bit arithmetic). FA_OK, or FA_ERR_INVALID_ARG for a null pointer or a negative length. The kernels take their
+ * first and last tile from the same inline function (csrc/fa_common.h, window_key_range).
+ */
+int fa_window_key_range(int Lq, int Lk, int window_left, int window_right, int row_first, int row_last, int *key_lo, int *key_hi);
+/*
  * Write new K / V rows into the page pools ("append"; the step in front of fa_fwd_varlen_paged or fa_fwd_decode_paged): k_new / v_new
  * are packed [total_new, Hkv, D] views under one (row, head) stride pair; sequence b owns tokens cu_seqlens_new[b] ..
  * cu_seqlens_new[b+1) (entries clamped to [0, total_new], a non-increasing pair is length 0, n_b clamped to max_seqlen_new). Token i
