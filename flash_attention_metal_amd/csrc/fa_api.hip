@@ -115,7 +115,6 @@ int page_pool_ok(const char *fn, int D, int page_size, int max_pages_per_seq, lo
   TRY(page_strides_ok(fn, D, page_size, page_stride, head_stride, row_stride, block_table_stride, kv_dtype));
   return page_tables_ok(fn, page_size, max_pages_per_seq, block_table, seqlens_k);
 }
-int page_size_ok(int page_size) { return page_size >= 16 && page_size <= 256 && (page_size & (page_size - 1)) == 0; }
 int log2_of(int page_size) {
   int lp = 0;
   while ((1 << lp) < page_size) ++lp;
@@ -525,8 +524,7 @@ int fa_fwd_decode_kv8(const void *q, const void *k, const void *v, void *o, floa
 int fa_fwd_decode_paged_supported(int q_dtype, int kv_dtype, int D, int Hq, int Hkv, int Nq, int page_size) {
   const bool pair = (q_dtype == kv_dtype && (q_dtype == FA_DTYPE_F16 || q_dtype == FA_DTYPE_BF16 || q_dtype == FA_DTYPE_FP8_E4M3)) ||
                     (q_dtype == FA_DTYPE_BF16 && kv_dtype == FA_DTYPE_FP8_E4M3);
-  const bool pow2 = page_size >= 16 && page_size <= 256 && (page_size & (page_size - 1)) == 0;
-  return pair && pow2 && fa_fwd_decode_supported(q_dtype, D, Hq, Hkv, Nq);
+  return pair && fa::page_size_ok(page_size) && fa_fwd_decode_supported(q_dtype, D, Hq, Hkv, Nq);
 }
 long long fa_fwd_decode_paged_workspace_bytes(int B, int Hq, int Hkv, int Nq, int D, int page_size, int max_pages_per_seq) {
   if (page_size < 1 || max_pages_per_seq < 1 || (long long)page_size * max_pages_per_seq > (1 << 30)) return 0;
@@ -655,7 +653,7 @@ int fa_kv_append_paged(const void *k_new, const void *v_new, void *k_pages, void
   TRY(nonnull(fn, {k_new, v_new, k_pages, v_pages, cu_seqlens_new, block_table, seqlens_k}));
   TRY(positive(fn, {B, Hkv, total_new, max_seqlen_new, D, page_size, num_pages, max_pages_per_seq}));
   const int bytes = fa_dtype_in_bytes(dtype);
-  if ((dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_FP8_E4M3) || ((long long)D * bytes) % 16 || !page_size_ok(page_size))
+  if ((dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_FP8_E4M3) || ((long long)D * bytes) % 16 || !fa::page_size_ok(page_size))
     return fail(FA_ERR_UNSUPPORTED, "fa_kv_append_paged: needs f16 / bf16 / fp8_e4m3, rows of whole 16-byte chunks and a page size of 16, 32, 64, 128 "
                 "or 256; got dtype=%s D=%d page_size=%d", fa_dtype_name(dtype), D, page_size);
   if (max_seqlen_new > total_new)

@@ -60,6 +60,30 @@ constexpr int bwd_occ(int D) { return D == 64 ? 3 : D == 128 ? 2 : 1; }  // (hea
 constexpr int bwd_sub_dq(int D) { return FA_BWD_SUB; }
 constexpr int bwd_sub_kv(int D) { return FA_BWD_SUB; }
 
+// Dynamic LDS of the two bodies: K and V (dQ) / Q and dO (dK, dV) double buffers of staged tiles; the dK/dV body keeps the -lse.log2e
+// and -delta rows of both buffers behind them
+constexpr size_t bwd_dq_lds_bytes(int D) { return (size_t)4 * bwd_sub_dq(D) * BN * D * 2; }
+constexpr size_t bwd_dkdv_lds_bytes(int D) { return (size_t)4 * bwd_sub_kv(D) * BN * D * 2 + 2 * 2 * bwd_sub_kv(D) * BN * 4; }
+
+// One backward call: dQ first -- it leaves delta in the workspace for the dK/dV kernel -- then dK/dV on the same stream, one error
+// check at the end. p.N / p.Nk size the grids (varlen: max_seqlen_q / max_seqlen_k, blocks past the end of their sequence return at once).
+template <typename KQ, typename KK, typename PT>
+inline hipError_t launch_bwd_pair(KQ kq, KK kk, const PT &p, int D, hipStream_t s) {
+  const int nBq = (p.N + BM - 1) / BM, nBk = (p.Nk + BM - 1) / BM;
+  const size_t smem_dq = bwd_dq_lds_bytes(D), smem_kv = bwd_dkdv_lds_bytes(D);
+  hipError_t e = hipSuccess;
+  if (smem_kv > 48 * 1024) e = set_dyn_lds_once((const void *)kk, (int)smem_kv);
+  if (e != hipSuccess) return e;
+  if (smem_dq > 48 * 1024) {
+    e = set_dyn_lds_once((const void *)kq, (int)smem_dq);
+    if (e != hipSuccess) return e;
+  }
+  (void)hipGetLastError();  // do not report an older sticky error as this launch's
+  hipLaunchKernelGGL(kq, dim3(nBq * p.B * p.H), dim3(NTHREADS), smem_dq, s, p);
+  hipLaunchKernelGGL(kk, dim3(nBk * p.B * p.Hkv), dim3(NTHREADS), smem_kv, s, p);
+  return hipGetLastError();
+}
+
 // per-head-dim constants of the kernels below (the reference kernel is head_dim 64 only, kernels.metal:905-1265;
 // 128 is the same algorithm with twice the k-steps / output blocks and two workgroups per CU)
 #define FA_BWD_CONSTS(D, SUBS)                                                                   \

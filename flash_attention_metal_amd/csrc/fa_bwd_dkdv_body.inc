@@ -21,6 +21,7 @@
   lds_char *QU = smem;                // [2] Q tile (BT rows): read by rows for S, transposed for dK
   lds_char *OU = smem + 2 * STILE;    // [2] dO tile: read by rows for dP, transposed for dV
   lds_char *ROWS = smem + 4 * STILE;  // [2][2][BT] floats: -lse*log2e, -delta of the tile's query rows (the chains' initial accumulators)
+  static_assert(4 * STILE + 2 * 2 * BT * 4 == bwd_dkdv_lds_bytes(D), "the launcher's LDS size is the Q / dO buffers and the row constants");
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);

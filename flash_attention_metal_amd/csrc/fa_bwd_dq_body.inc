@@ -20,6 +20,7 @@
   lds_char *smem = (lds_char *)smem_generic;
   lds_char *KU = smem;               // [2] K tile of BT rows (read by rows for S, transposed for dQ)
   lds_char *VR = smem + 2 * STILE;   // [2] V tile (read by rows)
+  static_assert(4 * STILE == bwd_dq_lds_bytes(D), "the launcher's LDS size is the K / V buffers");
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);

@@ -97,31 +97,15 @@ hipError_t launch_widen_e4m3(const void *in, void *out, long long n, hipStream_t
 
 template <typename Tag, int D, bool CAUSAL, bool PAD>
 static hipError_t launch_bwd_one(const BwdParams &p, hipStream_t s) {
-  constexpr int BTILE = BN * D * 2;
-  const int nBq = (p.N + BM - 1) / BM, nBk = (p.Nk + BM - 1) / BM;
-  const size_t smem_dq = 4 * bwd_sub_dq(D) * BTILE, smem_kv = 4 * bwd_sub_kv(D) * BTILE + 2 * 2 * bwd_sub_kv(D) * BN * 4;
-  auto kq = bwd_dq_kernel<Tag, D, CAUSAL, PAD>;
-  auto kk = bwd_dkdv_kernel<Tag, D, CAUSAL, PAD>;
-  hipError_t e = hipSuccess;
-  if (smem_kv > 48 * 1024) e = set_dyn_lds_once((const void *)kk, (int)smem_kv);
-  if (e != hipSuccess) return e;
-  if (smem_dq > 48 * 1024) {
-    e = set_dyn_lds_once((const void *)kq, (int)smem_dq);
-    if (e != hipSuccess) return e;
-  }
-  (void)hipGetLastError();  // do not report an older sticky error as this launch's
-  hipLaunchKernelGGL(kq, dim3(nBq * p.B * p.H), dim3(NTHREADS), smem_dq, s, p);
-  hipLaunchKernelGGL(kk, dim3(nBk * p.B * p.Hkv), dim3(NTHREADS), smem_kv, s, p);
-  return hipGetLastError();
+  return launch_bwd_pair(bwd_dq_kernel<Tag, D, CAUSAL, PAD>, bwd_dkdv_kernel<Tag, D, CAUSAL, PAD>, p, D, s);
 }
 
+// head dims without a kernel of their own: the next larger instantiation on zero-padded rows (PAD)
 template <typename Tag>
 static hipError_t launch_bwd_dt(const BwdParams &p, hipStream_t s) {
-  if (p.D == 64) return p.is_causal ? launch_bwd_one<Tag, 64, true, false>(p, s) : launch_bwd_one<Tag, 64, false, false>(p, s);
-  if (p.D == 128) return p.is_causal ? launch_bwd_one<Tag, 128, true, false>(p, s) : launch_bwd_one<Tag, 128, false, false>(p, s);
-  if (p.D == 256) return p.is_causal ? launch_bwd_one<Tag, 256, true, false>(p, s) : launch_bwd_one<Tag, 256, false, false>(p, s);
-  if (p.D < 64) return p.is_causal ? launch_bwd_one<Tag, 64, true, true>(p, s) : launch_bwd_one<Tag, 64, false, true>(p, s);
-  return p.is_causal ? launch_bwd_one<Tag, 128, true, true>(p, s) : launch_bwd_one<Tag, 128, false, true>(p, s);
+  if (p.D == 64 || p.D == 128 || p.D == 256)
+    return with_dim_causal<64, 128, 256>(p.D, p.is_causal, [&](auto d, auto c) { return launch_bwd_one<Tag, d(), c(), false>(p, s); });
+  return with_dim_causal<64, 128>(p.D < 64 ? 64 : 128, p.is_causal, [&](auto d, auto c) { return launch_bwd_one<Tag, d(), c(), true>(p, s); });
 }
 
 hipError_t launch_bwd(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse,

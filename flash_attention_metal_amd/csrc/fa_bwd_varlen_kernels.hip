@@ -34,28 +34,6 @@ __global__ __launch_bounds__(NTHREADS, bwd_varlen_occ(D)) void bwd_dkdv_varlen_k
 
 bool bwd_varlen_supported(int dtype, int D) { return (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) && (D == 64 || D == 128); }
 
-// dQ first: it leaves delta in the workspace for the dK/dV kernel (same stream). p.N / p.Nk hold max_seqlen_q / max_seqlen_k: blocks
-// past the end of their sequence return at once.
-template <typename Tag, int D, bool CAUSAL>
-static hipError_t launch_bwd_varlen_one(const BwdVarlenParams &p, hipStream_t s) {
-  constexpr int BTILE = BN * D * 2;
-  const int nBq = (p.N + BM - 1) / BM, nBk = (p.Nk + BM - 1) / BM;
-  const size_t smem_dq = 4 * bwd_sub_dq(D) * BTILE, smem_kv = 4 * bwd_sub_kv(D) * BTILE + 2 * 2 * bwd_sub_kv(D) * BN * 4;  // as launch_bwd_one
-  auto kq = bwd_dq_varlen_kernel<Tag, D, CAUSAL>;
-  auto kk = bwd_dkdv_varlen_kernel<Tag, D, CAUSAL>;
-  hipError_t e = hipSuccess;
-  if (smem_kv > 48 * 1024) e = set_dyn_lds_once((const void *)kk, (int)smem_kv);
-  if (e != hipSuccess) return e;
-  if (smem_dq > 48 * 1024) {
-    e = set_dyn_lds_once((const void *)kq, (int)smem_dq);
-    if (e != hipSuccess) return e;
-  }
-  (void)hipGetLastError();  // do not report an older sticky error as this launch's
-  hipLaunchKernelGGL(kq, dim3(nBq * p.B * p.H), dim3(NTHREADS), smem_dq, s, p);
-  hipLaunchKernelGGL(kk, dim3(nBk * p.B * p.Hkv), dim3(NTHREADS), smem_kv, s, p);
-  return hipGetLastError();
-}
-
 hipError_t launch_bwd_varlen(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq,
                              float *dk, float *dv, float *ws, const int *cu_q, const int *cu_k, int B, int H, int Hkv, int total_q,
                              int total_k, int max_q, int max_k, int D, float scale, long long q_rs, long long q_hs, long long kv_rs,
@@ -67,13 +45,11 @@ hipError_t launch_bwd_varlen(const void *q, const void *k, const void *v, const 
   p.batch_stride = 0; p.head_stride = q_hs; p.is_causal = causal;
   p.Hkv = Hkv; p.Nk = max_k; p.kv_batch_stride = 0; p.kv_head_stride = kv_hs;
   p.cu_q = cu_q; p.cu_k = cu_k; p.total_q = total_q; p.total_k = total_k; p.q_rs = q_rs; p.kv_rs = kv_rs;
-  auto go = [&](auto tag) -> hipError_t {
-    using Tag = decltype(tag);
-    if (D == 64) return causal ? launch_bwd_varlen_one<Tag, 64, true>(p, s) : launch_bwd_varlen_one<Tag, 64, false>(p, s);
-    if (D == 128) return causal ? launch_bwd_varlen_one<Tag, 128, true>(p, s) : launch_bwd_varlen_one<Tag, 128, false>(p, s);
-    return hipErrorInvalidValue;
-  };
-  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
+  return with_tag(dtype, [&](auto tag) {
+    return with_dim_causal<64, 128>(D, causal, [&](auto d, auto c) {
+      return launch_bwd_pair(bwd_dq_varlen_kernel<decltype(tag), d(), c()>, bwd_dkdv_varlen_kernel<decltype(tag), d(), c()>, p, d(), s);
+    });
+  });
 }
 
 }  // namespace fa

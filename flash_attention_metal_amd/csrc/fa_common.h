@@ -135,6 +135,8 @@ hipError_t launch_mfma_varlen(const VarlenParams &p, int dtype, hipStream_t s);
 bool mfma_varlen_supported(int dtype, int D);
 hipError_t launch_mfma_varlen_paged(const VarlenPagedParams &p, int dtype, hipStream_t s);
 bool mfma_varlen_paged_supported(int dtype, int D, int page_size);
+// page sizes of the paged entry points: 16, 32, 64, 128 or 256 rows
+inline bool page_size_ok(int page_size) { return page_size >= 16 && page_size <= 256 && (page_size & (page_size - 1)) == 0; }
 hipError_t launch_mfma_varlen_window(const VarlenWindowParams &p, int dtype, hipStream_t s);
 hipError_t launch_mfma_varlen_paged_window(const VarlenPagedWindowParams &p, int dtype, hipStream_t s);
 // fa_kv_append_paged (csrc/fa_decode_kernel.hip): a byte copy of new K / V rows into their slots of the page pools

@@ -64,6 +64,10 @@ __device__ __forceinline__ u32x4 widen8(unsigned w0, unsigned w1) {
   return u32x4{r[0], r[1], r[2], r[3]};
 }
 
+// Dynamic LDS of an item: K and V double buffers of 64-key tiles; one image each where the tiles are staged through registers
+template <int D, bool KV8>
+constexpr size_t decode_lds_bytes() { return ((KV8 || FA_DECODE_REGSTAGE) ? 2 : 4) * (size_t)BN * D * 2; }
+
 // PRM = DecodePagedParams (PAGED: fa_fwd_decode_paged; the DecodeParams instantiations are fa_fwd_decode's kernels, unchanged): the
 // item's sequence has its own length L_b
 // (read once from device memory, clamped to the capacity p.Nk) in place of Nk, and every K / V piece comes from the page the block
@@ -96,6 +100,7 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(PRM p) {
   lds_char *smem = (lds_char *)smem_generic;
   constexpr bool RS = KV8 || (FA_DECODE_REGSTAGE != 0);  // tiles staged through registers into one LDS image
   lds_char *Kbuf = smem, *Vbuf = smem + (RS ? 1 : 2) * TILE;
+  static_assert((RS ? 2 : 4) * TILE == decode_lds_bytes<D, KV8>(), "the launcher's LDS size is the K / V buffers");
 
   const int lane = threadIdx.x;
   const int c = lane & 15, g = lane >> 4;
@@ -535,108 +540,49 @@ long long decode_workspace_bytes(int B, int Hq, int Hkv, int Nq, int Nk, int D) 
   return (long long)B * Hkv * std::max(decode_splits(B, Hkv, Nk, D, 0), decode_splits(B, Hkv, Nk, D, 1)) * (16 * QT) * (D + 2) * 4;
 }
 
-template <typename Tag, int D, int QT, bool KV8 = false>
-static hipError_t launch_decode_q(const DecodeParams &p, hipStream_t s) {
-  const size_t smem = ((KV8 || FA_DECODE_REGSTAGE) ? 2 : 4) * (size_t)BN * D * 2;
+// One call: the partial kernel over the B . Hkv . S items, then the combine kernel over the output rows, on the same stream. PRM picks
+// the mode: DecodeParams (dense: the plain combine kernel), DecodePagedParams, DecodeWindowParams (paged combine kernel: empty splits,
+// rows with no visible key; window mode has the causal partial kernel only).
+template <typename PRM, typename KP, typename KC>
+static hipError_t launch_decode_pair(KP partial, KC combine, size_t smem, const PRM &p, hipStream_t s) {
   (void)hipGetLastError();
-  if (p.is_causal) {
-    auto kern = decode_partial_kernel<Tag, D, QT, true, KV8>;
-    if (smem > 48 * 1024) { hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem); if (e != hipSuccess) return e; }
-    hipLaunchKernelGGL(kern, dim3(p.B * p.Hkv * p.S), dim3(64), smem, s, p);
-  } else {
-    auto kern = decode_partial_kernel<Tag, D, QT, false, KV8>;
-    if (smem > 48 * 1024) { hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem); if (e != hipSuccess) return e; }
-    hipLaunchKernelGGL(kern, dim3(p.B * p.Hkv * p.S), dim3(64), smem, s, p);
-  }
+  if (smem > 48 * 1024) { hipError_t e = set_dyn_lds_once((const void *)partial, (int)smem); if (e != hipSuccess) return e; }
+  hipLaunchKernelGGL(partial, dim3(p.B * p.Hkv * p.S), dim3(64), smem, s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((decode_combine_kernel<Tag, D, QT>), dim3(p.B * p.Hq * p.Nq), dim3(64), 0, s, p);
+  hipLaunchKernelGGL(combine, dim3(p.B * p.Hq * p.Nq), dim3(64), 0, s, (const DecodeParams &)p);
   return hipGetLastError();
 }
 
-template <typename Tag, int D, int QT, bool KV8 = false>
-static hipError_t launch_decode_paged_q(const DecodePagedParams &p, hipStream_t s) {
-  const size_t smem = ((KV8 || FA_DECODE_REGSTAGE) ? 2 : 4) * (size_t)BN * D * 2;
-  (void)hipGetLastError();
-  auto kern = p.is_causal ? decode_partial_kernel<Tag, D, QT, true, KV8, DecodePagedParams> : decode_partial_kernel<Tag, D, QT, false, KV8, DecodePagedParams>;
-  if (smem > 48 * 1024) { hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem); if (e != hipSuccess) return e; }
-  hipLaunchKernelGGL(kern, dim3(p.B * p.Hkv * p.S), dim3(64), smem, s, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((decode_combine_kernel<Tag, D, QT, true>), dim3(p.B * p.Hq * p.Nq), dim3(64), 0, s, (const DecodeParams &)p);
-  return hipGetLastError();
-}
-
-hipError_t launch_decode_paged(const DecodePagedParams &p0, int D, int dtype, int kv8, hipStream_t s) {
-  DecodePagedParams p = p0;
-  p.q8 = (dtype == FA_DTYPE_FP8_E4M3);
-  const int R = (p.Hq / p.Hkv) * p.Nq, QT = (R + 15) / 16;
-  auto go = [&](auto tag) -> hipError_t {
-    using Tag = decltype(tag);
-    if (D == 64) return QT == 1 ? launch_decode_paged_q<Tag, 64, 1>(p, s) : launch_decode_paged_q<Tag, 64, 2>(p, s);
-    if (D == 128) return QT == 1 ? launch_decode_paged_q<Tag, 128, 1>(p, s) : launch_decode_paged_q<Tag, 128, 2>(p, s);
-    return hipErrorInvalidValue;
-  };
-  if (kv8 || dtype == FA_DTYPE_FP8_E4M3) {
-    if (D == 64) return QT == 1 ? launch_decode_paged_q<BF16, 64, 1, true>(p, s) : launch_decode_paged_q<BF16, 64, 2, true>(p, s);
-    if (D == 128) return QT == 1 ? launch_decode_paged_q<BF16, 128, 1, true>(p, s) : launch_decode_paged_q<BF16, 128, 2, true>(p, s);
-    return hipErrorInvalidValue;
+template <typename Tag, int D, int QT, bool KV8, typename PRM>
+static hipError_t launch_decode_q(const PRM &p, hipStream_t s) {
+  constexpr bool PAGED = std::is_base_of<DecodePagedParams, PRM>::value, WINDOW = std::is_same<PRM, DecodeWindowParams>::value;
+  auto combine = decode_combine_kernel<Tag, D, QT, PAGED>;
+  if constexpr (!WINDOW) {
+    if (!p.is_causal) return launch_decode_pair(decode_partial_kernel<Tag, D, QT, false, KV8, PRM>, combine, decode_lds_bytes<D, KV8>(), p, s);
   }
-  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
-}
-
-// fa_fwd_decode_paged_window: the paged partial kernel in window mode, then the paged combine kernel as it is (empty splits, rows with
-// no visible key)
-template <typename Tag, int D, int QT, bool KV8 = false>
-static hipError_t launch_decode_window_q(const DecodeWindowParams &p, hipStream_t s) {
-  const size_t smem = ((KV8 || FA_DECODE_REGSTAGE) ? 2 : 4) * (size_t)BN * D * 2;
-  (void)hipGetLastError();
-  auto kern = decode_partial_kernel<Tag, D, QT, true, KV8, DecodeWindowParams>;
-  if (smem > 48 * 1024) { hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem); if (e != hipSuccess) return e; }
-  hipLaunchKernelGGL(kern, dim3(p.B * p.Hkv * p.S), dim3(64), smem, s, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((decode_combine_kernel<Tag, D, QT, true>), dim3(p.B * p.Hq * p.Nq), dim3(64), 0, s, (const DecodeParams &)p);
-  return hipGetLastError();
-}
-
-hipError_t launch_decode_paged_window(const DecodeWindowParams &p0, int D, int dtype, int kv8, hipStream_t s) {
-  DecodeWindowParams p = p0;
-  p.q8 = (dtype == FA_DTYPE_FP8_E4M3);
-  const int R = (p.Hq / p.Hkv) * p.Nq, QT = (R + 15) / 16;
-  auto go = [&](auto tag) -> hipError_t {
-    using Tag = decltype(tag);
-    if (D == 64) return QT == 1 ? launch_decode_window_q<Tag, 64, 1>(p, s) : launch_decode_window_q<Tag, 64, 2>(p, s);
-    if (D == 128) return QT == 1 ? launch_decode_window_q<Tag, 128, 1>(p, s) : launch_decode_window_q<Tag, 128, 2>(p, s);
-    return hipErrorInvalidValue;
-  };
-  if (kv8 || dtype == FA_DTYPE_FP8_E4M3) {
-    if (D == 64) return QT == 1 ? launch_decode_window_q<BF16, 64, 1, true>(p, s) : launch_decode_window_q<BF16, 64, 2, true>(p, s);
-    if (D == 128) return QT == 1 ? launch_decode_window_q<BF16, 128, 1, true>(p, s) : launch_decode_window_q<BF16, 128, 2, true>(p, s);
-    return hipErrorInvalidValue;
-  }
-  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
+  return launch_decode_pair(decode_partial_kernel<Tag, D, QT, true, KV8, PRM>, combine, decode_lds_bytes<D, KV8>(), p, s);
 }
 
 // dtype: of the queries (and of K / V unless kv8); kv8: K and V are e4m3 (dtype FP8: so are the queries; BF16: an e4m3 cache under
-// bf16 queries -- the arithmetic is bf16 either way)
-hipError_t launch_decode(const DecodeParams &p0, int D, int dtype, int kv8, hipStream_t s) {
-  DecodeParams p = p0;
+// bf16 queries -- the arithmetic, and the output, are bf16 either way)
+template <typename PRM>
+static hipError_t dispatch_decode(const PRM &p0, int D, int dtype, int kv8, hipStream_t s) {
+  PRM p = p0;
   p.q8 = (dtype == FA_DTYPE_FP8_E4M3);
   const int R = (p.Hq / p.Hkv) * p.Nq, QT = (R + 15) / 16;
-  auto go = [&](auto tag) -> hipError_t {
-    using Tag = decltype(tag);
-    if (D == 64) return QT == 1 ? launch_decode_q<Tag, 64, 1>(p, s) : launch_decode_q<Tag, 64, 2>(p, s);
-    if (D == 128) return QT == 1 ? launch_decode_q<Tag, 128, 1>(p, s) : launch_decode_q<Tag, 128, 2>(p, s);
-    return hipErrorInvalidValue;
+  auto go = [&](auto tag, auto k8) {
+    return with_dim<64, 128>(D, [&](auto d) {
+      return QT == 1 ? launch_decode_q<decltype(tag), d(), 1, k8()>(p, s) : launch_decode_q<decltype(tag), d(), 2, k8()>(p, s);
+    });
   };
-  if (kv8 || dtype == FA_DTYPE_FP8_E4M3) {  // e4m3 K, V (and Q, or bf16 Q); bf16 arithmetic and output
-    if (D == 64) return QT == 1 ? launch_decode_q<BF16, 64, 1, true>(p, s) : launch_decode_q<BF16, 64, 2, true>(p, s);
-    if (D == 128) return QT == 1 ? launch_decode_q<BF16, 128, 1, true>(p, s) : launch_decode_q<BF16, 128, 2, true>(p, s);
-    return hipErrorInvalidValue;
-  }
-  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
+  if (kv8 || dtype == FA_DTYPE_FP8_E4M3) return go(BF16{}, std::true_type{});
+  return with_tag(dtype, [&](auto tag) { return go(tag, std::false_type{}); });
 }
+
+hipError_t launch_decode(const DecodeParams &p, int D, int dtype, int kv8, hipStream_t s) { return dispatch_decode(p, D, dtype, kv8, s); }
+hipError_t launch_decode_paged(const DecodePagedParams &p, int D, int dtype, int kv8, hipStream_t s) { return dispatch_decode(p, D, dtype, kv8, s); }
+hipError_t launch_decode_paged_window(const DecodeWindowParams &p, int D, int dtype, int kv8, hipStream_t s) { return dispatch_decode(p, D, dtype, kv8, s); }
 
 // fa_kv_append_paged: new K / V rows -> their slots of the page pools, a byte copy (BYTES = element size). One 16-byte chunk per lane and
 // step: a workgroup takes APPEND_ROWS new rows of one (sequence, key head), K and V alike. The sequence lookup and its clamps are the

@@ -57,6 +57,9 @@ __device__ __forceinline__ f32x16 mfma_f8(i32x8 a, i32x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
 }
 
+// Dynamic LDS of a workgroup of the body below: the e4m3 K and V double buffers, reused by the epilogue's bf16 O tiles
+constexpr size_t fp8_lds_bytes(int D) { return std::max((size_t)4 * BN * D, (size_t)BM * 2 * D); }
+
 template <int D, bool CAUSAL>
 __device__ __forceinline__ void fwd_fp8_body(const Params &p) {
   static_assert(D == 64 || D == 128, "head dims of the all-fp8 kernel");
@@ -73,6 +76,7 @@ __device__ __forceinline__ void fwd_fp8_body(const Params &p) {
   lds_char *smem = (lds_char *)smem_generic;
   lds_char *Kbuf = smem;             // [2][BN][RB], chunks swizzled
   lds_char *Vbuf = smem + 2 * TILE;  // [2][BN][RB], chunks swizzled
+  static_assert(4 * TILE <= fp8_lds_bytes(D) && RW * WM * ORB <= fp8_lds_bytes(D), "the launcher's LDS size covers the K / V buffers and the epilogue's O tiles");
 
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -360,21 +364,12 @@ bool fp8pv_supported(int dtype, int D) { return dtype == FA_DTYPE_FP8_E4M3 && (D
 
 template <int D, bool CAUSAL>
 static hipError_t launch8_one(const Params &p, hipStream_t s) {
-  const int nQ = (p.N + BM - 1) / BM;
-  const size_t smem = std::max((size_t)4 * BN * D, (size_t)BM * 2 * D);  // K / V double buffers; the epilogue's bf16 O tiles
-  auto kern = fwd_fp8_kernel<D, CAUSAL>;
-  Params pp = p;
-  pp.head_group = causal_head_group(p, D, 1);
-  set_block_divisors(pp, nQ, pp.head_group);
-  (void)hipGetLastError();  // do not report an older sticky error as this launch's
-  hipLaunchKernelGGL(kern, dim3(nQ * p.B * p.H), dim3(NTHREADS), smem, s, pp);
-  return hipGetLastError();
+  return launch_blocks(fwd_fp8_kernel<D, CAUSAL>, p, BM, NTHREADS, fp8_lds_bytes(D), causal_head_group(p, D, 1), s);
 }
 
 hipError_t launch_fp8pv(const Params &p, int dtype, hipStream_t s) {
   if (!fp8pv_supported(dtype, p.D)) return hipErrorInvalidValue;
-  if (p.D == 128) return p.is_causal ? launch8_one<128, true>(p, s) : launch8_one<128, false>(p, s);
-  return p.is_causal ? launch8_one<64, true>(p, s) : launch8_one<64, false>(p, s);
+  return with_dim_causal<64, 128>(p.D, p.is_causal, [&](auto d, auto c) { return launch8_one<d(), c()>(p, s); });
 }
 
 }  // namespace fa

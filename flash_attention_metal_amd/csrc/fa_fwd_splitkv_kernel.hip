@@ -21,6 +21,12 @@
 
 namespace fa {
 
+// Dynamic LDS of a workgroup of S waves: a private K tile and V tile per wave, reused as the merge buffer of (16 D/32 + 2) floats per lane
+constexpr size_t splitkv_lds_bytes(int D, int S) {
+  const size_t tiles = (size_t)2 * BN * D * 2, merge = (size_t)(16 * (D / 32) + 2) * 64 * 4;
+  return S * (tiles > merge ? tiles : merge);
+}
+
 template <typename Tag, int D, bool CAUSAL>
 // (head_dim 128 never runs more than four waves -- splitkv_waves: LDS -- so its register cap is 512, not 256: compiled for
 //  eight it spilled 820 B per lane and ran 3-4x slower than the kernels it was chosen over, profiles/r03/ab_d128_small_grids.log)
@@ -48,6 +54,7 @@ __global__ __launch_bounds__((D == 64 ? 512 : 256), 1) void fwd_splitkv_kernel(P
   const int r = lane & 31, h = lane >> 5;
   lds_char *Kt = smem + wave * (2 * TILE);    // this wave's private K tile, V tile behind it
   lds_char *Vt = Kt + TILE;
+  static_assert(2 * TILE <= splitkv_lds_bytes(D, 1) && (NACC + 2) * 64 * 4 <= splitkv_lds_bytes(D, 1), "a wave's share of the launcher's LDS size covers its tiles and its merge rows");
 
   const int nQ = p.nq;
   const int bh = (int)fdiv(blockIdx.x, p.fd_nq), qrem = (int)blockIdx.x - bh * nQ;
@@ -303,34 +310,17 @@ int splitkv_waves(int D, int Nk) {
 template <typename Tag, int D, bool CAUSAL>
 static hipError_t launch_splitkv_one(const Params &p, hipStream_t s) {
   const int S = splitkv_waves(D, p.Nk);
-  const int nQ = (p.N + WM - 1) / WM;
-  size_t smem = (size_t)S * 2 * BN * D * 2;                                // S private K+V tiles ...
-  const size_t merge = (size_t)S * (16 * (D / 32) + 2) * 64 * 4;           // ... reused as the merge buffer
-  if (merge > smem) smem = merge;
-  auto kern = fwd_splitkv_kernel<Tag, D, CAUSAL>;
-  if (smem > 48 * 1024) {
-    hipError_t e = set_dyn_lds_once((const void *)kern, 160 * 1024);
-    if (e != hipSuccess) return e;
-  }
-  // one workgroup per 32-row block: four times the grid fa_fwd's "grid too large" guard (128-row blocks) lets through
-  const long long grid = (long long)nQ * p.B * p.H;
-  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  Params pp = p;
-  set_block_divisors(pp, nQ, 0);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * S), smem, s, pp);
-  return hipGetLastError();
-}
-
-template <typename Tag>
-static hipError_t launch_splitkv_dt(const Params &p, hipStream_t s) {
-  if (p.D == 64) return p.is_causal ? launch_splitkv_one<Tag, 64, true>(p, s) : launch_splitkv_one<Tag, 64, false>(p, s);
-  return hipErrorInvalidValue;
+  // One workgroup per 32-row block: four times the grid fa_fwd's "grid too large" guard (128-row blocks) lets through -- launch_blocks
+  // checks it. The LDS size depends on the run-time S but its attribute is set once per instantiation: always the whole 160 KiB, or a
+  // call with S = 8 after one with S = 4 would not launch.
+  return launch_blocks(fwd_splitkv_kernel<Tag, D, CAUSAL>, p, WM, 64 * S, splitkv_lds_bytes(D, S), 0, s, 160 * 1024);
 }
 
 hipError_t launch_splitkv(const Params &p, int dtype, hipStream_t s) {
-  if (dtype == FA_DTYPE_FP8_E4M3) return launch_splitkv_dt<FP8>(p, s);
-  return dtype == FA_DTYPE_F16 ? launch_splitkv_dt<F16>(p, s) : launch_splitkv_dt<BF16>(p, s);
+  auto go = [&](auto tag) {
+    return with_dim_causal<64>(p.D, p.is_causal, [&](auto d, auto c) { return launch_splitkv_one<decltype(tag), d(), c()>(p, s); });
+  };
+  return dtype == FA_DTYPE_FP8_E4M3 ? go(FP8{}) : with_tag(dtype, go);
 }
 
 }  // namespace fa

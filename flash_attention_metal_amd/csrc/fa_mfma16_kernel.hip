@@ -100,6 +100,14 @@ __device__ __forceinline__ float xlane(float x, int mask) { return __shfl_xor(x,
 // in global memory, the LDS images and register fragments have the kernel's pitch, and every 16-byte chunk at or past column p.D is
 // fetched from an offset outside the buffer descriptor's range, which reads as zeros for register loads and LDS-DMA alike. The padding
 // adds 0 to every score and its O columns are never stored.
+// Dynamic LDS of a workgroup of the body below: the K and V double buffers of SUB tiles each (the epilogue's O tiles sit inside them)
+// and, for the lazy kernels, the flag word behind them
+template <typename Tag, int D, int SUB>
+constexpr size_t mfma16_lds_bytes() {
+  constexpr bool lazy = std::is_same<Tag, BF16>::value && D == 64 && (FA16_ONES != 0) && (FA16_LAZY == 1);
+  return 4 * SUB * (size_t)(D == 128 ? FA16_BN128 : BN) * D * 2 + (lazy ? 16 : 0);
+}
+
 template <typename Tag, int D, bool CAUSAL, int RW, bool PAD, int SUB>
 __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
   using M = MT16<Tag>;
@@ -215,6 +223,8 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
   // (config 4 shard, profiles/r11/ab_lazy.log) -- it keeps the per-tile test.
   constexpr bool LAZY = ONES && std::is_same<Tag, BF16>::value && D == 64 && (FA16_LAZY != 0);
   constexpr bool LAZY_TEST = LAZY && (FA16_LAZY == 1);
+  static_assert(4 * SUB * TILE + (LAZY_TEST ? 4 : 0) <= mfma16_lds_bytes<Tag, D, SUB>() && RW * WM * RB <= 4 * SUB * TILE,
+                "the launcher's LDS size covers the K / V buffers, the flag word and the epilogue's O tiles");
   lds_char *poison_flag = smem + 4 * SUB * TILE;  // LAZY: one word behind the K / V buffers, the workgroup's OR of the waves' poison flags
   int slow = 0;    // LAZY, wave-uniform: this is the block's second run -- every tile takes the exact path (true maxima) before its hot pass
   // ONES: probabilities are formed against a reference BIAS log2 units ABOVE the row maximum found when the reference was last set
@@ -680,23 +690,11 @@ bool mfma16_supported(int dtype, int D) { return (dtype == FA_DTYPE_F16 || dtype
 
 template <typename Tag, int D, bool CAUSAL, int RW, bool PAD = false, int SUB = 1>
 static hipError_t launch16_one(const Params &p, hipStream_t s) {
-  const int nQ = (p.N + RW * WM - 1) / (RW * WM);
-  constexpr bool lazy = std::is_same<Tag, BF16>::value && D == 64 && (FA16_ONES != 0) && (FA16_LAZY == 1);
-  const size_t smem = 4 * SUB * (size_t)(D == 128 ? FA16_BN128 : BN) * D * 2 + (lazy ? 16 : 0);  // K / V double buffers (+ the flag word of the lazy kernels)
-  auto kern = fwd_mfma16_kernel<Tag, D, CAUSAL, RW, PAD, SUB>;
-  if (smem > 48 * 1024) {
-    hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  Params pp = p;
-  pp.head_group = causal_head_group(p, D, 2);
+  int head_group = causal_head_group(p, D, 2);
 #ifdef FA16_FORCE_HEAD_GROUP  // scheduling experiments only (tools/ab.py arms): never defined in the shipped library
-  pp.head_group = FA16_FORCE_HEAD_GROUP;
+  head_group = FA16_FORCE_HEAD_GROUP;
 #endif
-  set_block_divisors(pp, nQ, pp.head_group);
-  (void)hipGetLastError();  // do not report an older sticky error as this launch's
-  hipLaunchKernelGGL(kern, dim3(nQ * p.B * p.H), dim3(64 * RW), smem, s, pp);
-  return hipGetLastError();
+  return launch_blocks(fwd_mfma16_kernel<Tag, D, CAUSAL, RW, PAD, SUB>, p, RW * WM, 64 * RW, mfma16_lds_bytes<Tag, D, SUB>(), head_group, s);
 }
 
 // Waves per workgroup: 4 (128 query rows) or 8 (256 rows, the same 32 rows per wave: eight waves share every K / V tile, so the
@@ -723,7 +721,7 @@ int mfma16_waves(int D, int BH, int N, int Nk, int is_causal) {
 
 hipError_t launch_mfma16(const Params &p, int dtype, hipStream_t s) {
   const bool w8 = mfma16_waves(p.D, p.B * p.H, p.N, p.Nk, p.is_causal) == 8 && (p.D == 64 || !p.is_causal);
-  auto go = [&](auto tag) -> hipError_t {
+  return with_tag(dtype, [&](auto tag) -> hipError_t {
     using Tag = decltype(tag);
     if (p.D != 64 && p.D != 128) {  // zero-padded rows of the next larger instantiation (four waves)
       if (p.D < 64) return p.is_causal ? launch16_one<Tag, 64, true, 4, true>(p, s) : launch16_one<Tag, 64, false, 4, true>(p, s);
@@ -738,8 +736,7 @@ hipError_t launch_mfma16(const Params &p, int dtype, hipStream_t s) {
       return p.is_causal ? launch16_one<Tag, 128, true, 4>(p, s) : launch16_one<Tag, 128, false, 4>(p, s);
     }
     return hipErrorInvalidValue;
-  };
-  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
+  });
 }
 
 }  // namespace fa

@@ -314,4 +314,43 @@ inline void set_block_divisors(Params &p, int nq, int head_group) {
   p.fd_per = make_fastdiv((unsigned)hg * (unsigned)nq);
 }
 
+// One launch of a forward matrix-core kernel: one workgroup of `threads` threads per `rows` query rows of every (batch, head), `lds`
+// bytes of dynamic LDS (as the kernel family's *_lds_bytes function states them), causal issue order in groups of `head_group` heads.
+// lds_attr: the size set_dyn_lds_once declares, once per (kernel, device) -- the launch's own unless one instantiation is launched
+// with several sizes (0 = lds). The grid check is reachable by the 32-row split-KV grid only (fa_fwd has bounded the 128-row grid).
+template <typename K, typename PT>
+inline hipError_t launch_blocks(K kern, const PT &p, int rows, int threads, size_t lds, int head_group, hipStream_t s, size_t lds_attr = 0) {
+  const int nQ = (p.N + rows - 1) / rows;
+  if (lds > 48 * 1024) {
+    hipError_t e = set_dyn_lds_once((const void *)kern, (int)(lds_attr ? lds_attr : lds));
+    if (e != hipSuccess) return e;
+  }
+  const long long grid = (long long)nQ * p.B * p.H;
+  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  PT pp = p;
+  pp.head_group = head_group;
+  set_block_divisors(pp, nQ, head_group);
+  (void)hipGetLastError();  // do not report an older sticky error as this launch's
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, s, pp);
+  return hipGetLastError();
+}
+
+// The dispatch on run-time (dtype, head_dim, causal): f(F16{}) or f(BF16{}); f(integral_constant<int, D>{}) for the D among Ds...
+// (no other: hipErrorInvalidValue); the same with true_type / false_type for the mask. Call sites that must not instantiate a
+// combination (e4m3, a head dim without a kernel, a causal-only form) spell theirs out.
+template <typename F>
+inline hipError_t with_tag(int dtype, F &&f) {
+  return dtype == FA_DTYPE_F16 ? f(F16{}) : f(BF16{});
+}
+template <int... Ds, typename F>
+inline hipError_t with_dim(int D, F &&f) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)(... || (D == Ds && ((e = f(std::integral_constant<int, Ds>{})), true)));
+  return e;
+}
+template <int... Ds, typename F>
+inline hipError_t with_dim_causal(int D, bool causal, F &&f) {
+  return with_dim<Ds...>(D, [&](auto d) { return causal ? f(d, std::true_type{}) : f(d, std::false_type{}); });
+}
+
 }  // namespace fa

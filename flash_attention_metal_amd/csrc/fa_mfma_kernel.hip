@@ -35,16 +35,8 @@
 #ifndef FA_DEFER_THR
 #define FA_DEFER_THR 8.0f  // log2 units: P values are bounded by 2^8 between rescales (0 = rescale whenever a max moved)
 #endif
-#ifndef FA_SUMTRIG
-#define FA_SUMTRIG 1  // 1: the row sums decide whether the reference max is stale (no per-tile max); 0: per-tile max vs threshold
-#endif
 #ifndef FA_PRESCALE
 #define FA_PRESCALE 1  // 1 (f16/bf16): Q~ = round(scale.log2e.Q) once per block and -m (log2 units) as the C operand of each score chain: P = exp2(S') with no FMA
-#endif
-#ifndef FA_VPRE_HALF
-#define FA_VPRE_HALF 0  // 1: only the first 32 keys' V^T fragments are prefetched under the QK^T MFMAs, the second half under the first half's PV MFMAs (-16 live
-                        // registers: needed while K/V were staged through registers; with LDS-DMA staging the full prefetch fits -- 162-164 VGPR, no scratch --
-                        // and is 0.5-0.9 % faster, profiles/r03/ab_knobs_final_build.log)
 #endif
 #ifndef FA_MAIN_OCC4
 #define FA_MAIN_OCC4 1  // 1: the plain 128-row kernel at head_dim 64 (16-bit inputs, pre-scaled operand) gives up the V^T prefetch below and
@@ -61,9 +53,6 @@
 #endif                             // LDS-DMA staging freed the registers: +1..2 %, profiles/r03/ab_dma_knobs.log)
 #ifndef FA_LAV
 #define FA_LAV (D == 128 ? 4 : 2)  // ... and V^T fragments
-#endif
-#ifndef FA_PRIO
-#define FA_PRIO 2  // wave priority: 2 = raised around the MFMA clusters (+0.4..0.9 % A/B), 1 = around the softmax (-1..-6 %), 0 = off
 #endif
 
 namespace fa {
@@ -108,6 +97,16 @@ __device__ __forceinline__ int seqlen_paged(const VarlenPagedParams &p, int b) {
 __device__ __forceinline__ int seqlen_paged(const Params &, int) { return 0; }
 __device__ __forceinline__ int paged_capacity(const VarlenPagedParams &p) { return p.max_pages << p.lp; }
 __device__ __forceinline__ int paged_capacity(const Params &) { return 0; }
+// Dynamic LDS of a workgroup of the body below, the figure every launcher passes: per split the K and V double buffers (K rows of D
+// bytes for e4m3 inputs, head_dim 96 rows in 256-byte slots); the epilogue's O tiles sit inside them, and the split merge buffer --
+// (16 D/32 + 2) floats per lane of the publishing waves -- behind the O tiles.
+template <typename Tag, int D, int SPLIT = 1, int ROWS = BM>
+constexpr size_t mfma_lds_bytes() {
+  constexpr size_t RB = (D == 96) ? 256 : D * 2, KRB = std::is_same<Tag, FP8>::value ? D : RB;
+  constexpr size_t otiles = (size_t)ROWS * RB, merge_end = otiles + (size_t)(ROWS / WM) * (16 * (D / 32) + 2) * 64 * 4;
+  return std::max(SPLIT * (2 * BN * KRB + 2 * BN * RB), SPLIT == 2 ? merge_end : otiles);
+}
+
 template <typename Tag, int D, bool CAUSAL, int SPLIT, bool PRESC, int ROWS = BM, typename PT = Params>
 __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   constexpr bool PAGEDV = std::is_base_of<VarlenPagedParams, PT>::value;
@@ -162,6 +161,9 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   const int wave_all = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int sp = (SPLIT == 1) ? 0 : (wave_all / RW);  // which KV split this wave works on
   constexpr int GROUP_LDS = 2 * KTILE + 2 * TILE;     // K and V double buffers of one split
+  constexpr size_t LDS = mfma_lds_bytes<Tag, D, SPLIT, ROWS>();
+  static_assert(SPLIT * GROUP_LDS <= LDS && RW * WM * RB <= LDS, "the launchers' LDS size covers the K / V buffers and the epilogue's O tiles");
+  static_assert(SPLIT == 1 || RW * WM * RB + RW * (16 * DB + 2) * 64 * 4 <= LDS, "... and the split merge buffer");
   lds_char *smem = (lds_char *)smem_generic + sp * GROUP_LDS;
   lds_char *Kbuf = smem;              // [2][BN][KRB], rows swizzled
   lds_char *Vbuf = smem + 2 * KTILE;  // [2][BN][RB], rows swizzled
@@ -441,11 +443,9 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) oacc[db][i] = 0.0f;
   float m = -INFINITY;     // reference max of this row's scores (may lag the true max by < 2^THR); units: raw scores, PRE: log2 units
-  float mthr = -INFINITY;  // m + threshold: a tile max above it forces a rescale
   float l = 0.0f;          // this lane half's share of the running sum
   const float c2 = p.scale * 1.4426950408889634f;  // scale * log2(e)
   const float cm = PRE ? 1.0f : c2;                // m's units -> log2 units
-  const float thr_raw = FA_DEFER_THR / cm;         // the threshold in m's units
   // PRE: -m in all 16 registers of a tuple = the C operand of each score chain's first MFMA (0 until the first tile has
   // set m: the first tile's scores come out raw and go through the exact path)
   f32x16 negm;
@@ -546,9 +546,8 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
       // fragments of the PV product are streamed in between the MFMAs, two transposed
       // reads per MFMA: they do not depend on the softmax, so PV finds its operands in
       // registers instead of waiting on LDS per MFMA. sched_barrier pins that order.
-#if FA_PRIO == 2
+      // Wave priority is raised around the two MFMA clusters (+0.4..0.9 % A/B; around the softmax instead: -1..-6 %).
       __builtin_amdgcn_s_setprio(1);
-#endif
       f32x16 s[2];
       s16x4 vlo[VPRE ? 2 : 1][2][DB], vhi[VPRE ? 2 : 1][2][DB];
       if constexpr (VPRE) {
@@ -566,25 +565,16 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
             s[kb] = M::mfma(kf[kb][ks], qf[ks], (PRE && ks == 0) ? negm : s[kb]);
-            if constexpr (FA_VPRE_HALF) {  // the 2 * DB V blocks of keys 0..31, one per two QK MFMAs
-              const int mm = kb * KS + ks;
-              if ((mm & 1) == 0) {
-                const int m = mm >> 1;
-                const int vst = (m / DB) % 2, vdb = m % DB;
-                const lds_char *vb = vptr[vdb] + buf * TILE + (16 * vst) * RB;
-                vlo[0][vst][vdb] = lds_read_tr16(vb);
-                vhi[0][vst][vdb] = lds_read_tr16(vb + 8 * RB);
-              }
-            } else {
-              constexpr int PER = (2 * 2 * DB) / (2 * KS);  // V block reads per QK MFMA (1 at D=64)
+            // the V blocks of all 64 keys (prefetching only keys 0..31 here and the rest under the PV MFMAs saved 16 registers
+            // and was 0.5-0.9 % slower once LDS-DMA staging had freed them, profiles/r03/ab_knobs_final_build.log)
+            constexpr int PER = (2 * 2 * DB) / (2 * KS);  // V block reads per QK MFMA (1 at D=64)
 #pragma unroll
-              for (int u = 0; u < PER; ++u) {
-                const int m = (kb * KS + ks) * PER + u;
-                const int vkb = m / (2 * DB), vst = (m / DB) % 2, vdb = m % DB;
-                const lds_char *vb = vptr[vdb] + buf * TILE + (32 * vkb + 16 * vst) * RB;
-                vlo[vkb][vst][vdb] = lds_read_tr16(vb);
-                vhi[vkb][vst][vdb] = lds_read_tr16(vb + 8 * RB);
-              }
+            for (int u = 0; u < PER; ++u) {
+              const int m = (kb * KS + ks) * PER + u;
+              const int vkb = m / (2 * DB), vst = (m / DB) % 2, vdb = m % DB;
+              const lds_char *vb = vptr[vdb] + buf * TILE + (32 * vkb + 16 * vst) * RB;
+              vlo[vkb][vst][vdb] = lds_read_tr16(vb);
+              vhi[vkb][vst][vdb] = lds_read_tr16(vb + 8 * RB);
             }
             __builtin_amdgcn_sched_barrier(0);
           }
@@ -644,16 +634,11 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
           }
         }
       }
-#if FA_PRIO == 1
-      __builtin_amdgcn_s_setprio(1);
-#elif FA_PRIO == 2
       __builtin_amdgcn_s_setprio(0);
-#endif
       // ---- online softmax, lane-local + one half swap
       const float mc_old = m * c2;  // (unused with PRE)
       (void)mc_old;
       float ls0 = 0.0f, ls1 = 0.0f;
-#if FA_SUMTRIG
       // Deferred row max (T13) WITHOUT a per-tile max: P = exp2(c.s - c.m) is formed with the running reference m, and
       // the row sums that are needed anyway tell whether m is stale: a lane whose 32 probabilities add up to more than
       // 2^THR (or to +inf) has a score more than 2^THR above m at worst. Only then -- and on the first tile, where m is
@@ -678,9 +663,6 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         if (exact) recompute_scores(bufc, s, kv0, need_mask);
       }
       if (exact) {
-#else
-      {
-#endif
         float mx = fmaxf(s[0][0], s[1][0]);
 #pragma unroll
         for (int i = 1; i < 16; ++i) mx = fmaxf(fmaxf(mx, s[0][i]), s[1][i]);  // -> v_max3_f32
@@ -695,26 +677,20 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         // (window mode: the later rows of a wave can have every score of the wave's first active tile below their bound. The same floor:
         // their next tile's sums overflow the threshold and take the exact path, which drops the floor for the true maximum.)
         if constexpr (VARLEN && CAUSAL) mx = fmaxf(mx, -3.4028234663852886e38f);
-        // deferred row max (T13): O and l are rescaled only when some row's tile max exceeds the running
-        // reference m by more than 2^THR (log2 domain); otherwise p = exp2(c.s - c.m) <= 2^THR with the
-        // stale m. m, l and O stay mutually consistent, so LSE = m.scale + ln(l) is exact either way.
-        // On random data a 32-row wave sees SOME row's max move in most tiles, so the exact form
-        // (rescale whenever a max moved) paid the 32-multiply O pass nearly every tile.
-        if (FA_SUMTRIG || __builtin_amdgcn_ballot_w64(mx > mthr) != 0) {  // wave-uniform; first tile: mthr = -inf
-          const float m_new = fmaxf(m, mx);
-          const float alpha = __builtin_amdgcn_exp2f((m - m_new) * cm);
-          l *= alpha;
+        // the reference moves to the true maximum and O and l are rescaled to it: the 32-multiply O pass that a per-tile maximum
+        // with "rescale whenever a max moved" paid in nearly every tile on random data (profiles/r02/ab_sumtrig.log)
+        const float m_new = fmaxf(m, mx);
+        const float alpha = __builtin_amdgcn_exp2f((m - m_new) * cm);
+        l *= alpha;
 #pragma unroll
-          for (int db = 0; db < DB; ++db)
+        for (int db = 0; db < DB; ++db)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) oacc[db][i] *= alpha;
-          m = m_new;
-          mthr = m_new + thr_raw;
-          if constexpr (PRE) {
+          for (int i = 0; i < 16; ++i) oacc[db][i] *= alpha;
+        m = m_new;
+        if constexpr (PRE) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) negm[i] = -m_new;
-            asm volatile("" : "+v"(negm));
-          }
+          for (int i = 0; i < 16; ++i) negm[i] = -m_new;
+          asm volatile("" : "+v"(negm));
         }
         const float mc = m * cm;
         ls0 = 0.0f;
@@ -728,11 +704,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         }
       }
       l += ls0 + ls1;
-#if FA_PRIO == 1
-      __builtin_amdgcn_s_setprio(0);
-#elif FA_PRIO == 2
       __builtin_amdgcn_s_setprio(1);
-#endif
       // ---- O^T += V^T.P^T : per 16-key step, P fragment = 8 accumulator registers
       if constexpr (VPRE) {
 #pragma unroll
@@ -746,14 +718,6 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
             for (int db = 0; db < DB; ++db) {
               const s16x8 v8 = __builtin_shufflevector(vlo[kb][st][db], vhi[kb][st][db], 0, 1, 2, 3, 4, 5, 6, 7);
               oacc[db] = M::mfma(__builtin_bit_cast(vec8, v8), pf, oacc[db]);
-              if constexpr (FA_VPRE_HALF) {
-                if (kb == 0) {  // keys 32..63: the same block of the second half, read behind the MFMA that frees its registers' twin
-                  const lds_char *vb = vptr[db] + buf * TILE + (32 + 16 * st) * RB;
-                  vlo[1][st][db] = lds_read_tr16(vb);
-                  vhi[1][st][db] = lds_read_tr16(vb + 8 * RB);
-                  __builtin_amdgcn_sched_barrier(0);
-                }
-              }
             }
           }
         }
@@ -936,29 +900,18 @@ bool mfma_supported(int dtype, int D) {
   return dtype == FA_DTYPE_FP8_E4M3 && (D == 64 || D == 128 || D == 256);  // an fp8 row must fill whole 16-byte chunks per thread
 }
 
+// Every launcher below: launch_blocks (fa_mfma_common.h) with the kernel, its block height and threads, mfma_lds_bytes and a head group.
 template <typename Tag, int D, bool CAUSAL, bool PRESC>
 static hipError_t launch_one_(const Params &p, hipStream_t s) {
-  const int nQ = (p.N + BM - 1) / BM;
-  const size_t vrow = (D == 96) ? 256 : D * 2;  // fp8: K tiles stay e4m3 (rows of D bytes), V tiles are widened to bf16
-  const size_t smem = 2 * BN * (std::is_same<Tag, FP8>::value ? (size_t)D : vrow) + 2 * BN * vrow;
-  auto kern = fwd_mfma_kernel<Tag, D, CAUSAL, PRESC>;
-  if (smem > 48 * 1024) {
-    hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  Params pp = p;
-  pp.head_group = causal_head_group(p, D, std::is_same<Tag, FP8>::value ? 1 : 2);
+  int head_group = causal_head_group(p, D, std::is_same<Tag, FP8>::value ? 1 : 2);
 #ifdef FA_DEBUG_KNOBS  // scheduling experiments only: never compiled into the shipped library
   static const int env_head_group = [] { const char *e = getenv("FA_HEAD_GROUP"); return e ? atoi(e) : -1; }();
-  if (env_head_group >= 0) pp.head_group = env_head_group;
+  if (env_head_group >= 0) head_group = env_head_group;
 #ifdef FA_FORCE_HEAD_GROUP  // compile-time form for tools/ab.py (several builds side by side in one process share the environment)
-  pp.head_group = FA_FORCE_HEAD_GROUP;
+  head_group = FA_FORCE_HEAD_GROUP;
 #endif
 #endif
-  set_block_divisors(pp, nQ, pp.head_group);
-  (void)hipGetLastError();  // do not report an older sticky error as this launch's
-  hipLaunchKernelGGL(kern, dim3(nQ * p.B * p.H), dim3(NTHREADS), smem, s, pp);
-  return hipGetLastError();
+  return launch_blocks(fwd_mfma_kernel<Tag, D, CAUSAL, PRESC>, p, BM, NTHREADS, mfma_lds_bytes<Tag, D>(), head_group, s);
 }
 
 // p.exact (variant mfma_exact) selects the instantiation without the pre-scaled operand; where the pre-scaling does not
@@ -971,155 +924,52 @@ static hipError_t launch_one(const Params &p, hipStream_t s) {
   return launch_one_<Tag, D, CAUSAL, false>(p, s);
 }
 
-// Varlen: one block per (sequence, head, 128 rows up to max_seqlen_q) -- the host does not know the lengths; blocks past the end of
-// their sequence return at once. p.N / p.Nk hold max_seqlen_q / max_seqlen_k: the issue order (map_block) and the causal head groups
-// are those of a dense batch of B sequences of these lengths.
-template <typename Tag, int D, bool CAUSAL>
-static hipError_t launch_varlen_one(const VarlenParams &p, hipStream_t s) {
-  const int nQ = (p.N + BM - 1) / BM;
-  const size_t smem = 4 * BN * (size_t)(D * 2);  // K and V double buffers, as launch_one_
-  auto kern = fwd_mfma_varlen_kernel<Tag, D, CAUSAL>;
-  if (smem > 48 * 1024) {
-    hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  VarlenParams pp = p;
-  pp.head_group = causal_head_group(p, D, 2);
-  set_block_divisors(pp, nQ, pp.head_group);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(kern, dim3(nQ * p.B * p.H), dim3(NTHREADS), smem, s, pp);
-  return hipGetLastError();
+// The varlen modes: one block per (sequence, head, 128 rows up to max_seqlen_q) -- the host does not know the lengths; blocks past the
+// end of their sequence return at once. p.N / p.Nk hold max_seqlen_q / max_seqlen_k (varlen paged: the capacity): the issue order
+// (map_block) and the causal head groups are those of a dense batch of B sequences of these lengths. Window mode takes the causal
+// order: heaviest-first is harmless where the blocks weigh the same.
+template <typename Tag, int D, typename PT, typename K>
+static hipError_t launch_varlen_one(K kern, const PT &p, hipStream_t s) {
+  return launch_blocks(kern, p, BM, NTHREADS, mfma_lds_bytes<Tag, D>(), causal_head_group(p, D, 2), s);
 }
 
 bool mfma_varlen_supported(int dtype, int D) { return (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) && (D == 64 || D == 128); }
 
 hipError_t launch_mfma_varlen(const VarlenParams &p, int dtype, hipStream_t s) {
-  auto go = [&](auto tag) -> hipError_t {
-    using Tag = decltype(tag);
-    if (p.D == 64) return p.is_causal ? launch_varlen_one<Tag, 64, true>(p, s) : launch_varlen_one<Tag, 64, false>(p, s);
-    if (p.D == 128) return p.is_causal ? launch_varlen_one<Tag, 128, true>(p, s) : launch_varlen_one<Tag, 128, false>(p, s);
-    return hipErrorInvalidValue;
-  };
-  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
+  return with_tag(dtype, [&](auto tag) {
+    return with_dim_causal<64, 128>(p.D, p.is_causal, [&](auto d, auto c) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_varlen_kernel<decltype(tag), d(), c()>, p, s); });
+  });
 }
 
-// Varlen paged: the varlen grid; p.Nk holds the capacity (issue order and head groups as for a dense batch of full caches)
-template <typename Tag, int D, bool CAUSAL>
-static hipError_t launch_varlen_paged_one(const VarlenPagedParams &p, hipStream_t s) {
-  const int nQ = (p.N + BM - 1) / BM;
-  const size_t smem = 4 * BN * (size_t)(D * 2);
-  auto kern = fwd_mfma_varlen_paged_kernel<Tag, D, CAUSAL>;
-  if (smem > 48 * 1024) {
-    hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  VarlenPagedParams pp = p;
-  pp.head_group = causal_head_group(p, D, 2);
-  set_block_divisors(pp, nQ, pp.head_group);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(kern, dim3(nQ * p.B * p.H), dim3(NTHREADS), smem, s, pp);
-  return hipGetLastError();
-}
-
-bool mfma_varlen_paged_supported(int dtype, int D, int page_size) {
-  return mfma_varlen_supported(dtype, D) && page_size >= 16 && page_size <= 256 && (page_size & (page_size - 1)) == 0;
-}
+bool mfma_varlen_paged_supported(int dtype, int D, int page_size) { return mfma_varlen_supported(dtype, D) && page_size_ok(page_size); }
 
 hipError_t launch_mfma_varlen_paged(const VarlenPagedParams &p, int dtype, hipStream_t s) {
-  auto go = [&](auto tag) -> hipError_t {
-    using Tag = decltype(tag);
-    if (p.D == 64) return p.is_causal ? launch_varlen_paged_one<Tag, 64, true>(p, s) : launch_varlen_paged_one<Tag, 64, false>(p, s);
-    if (p.D == 128) return p.is_causal ? launch_varlen_paged_one<Tag, 128, true>(p, s) : launch_varlen_paged_one<Tag, 128, false>(p, s);
-    return hipErrorInvalidValue;
-  };
-  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
-}
-
-// Window mode: the grids, LDS and issue order of the two varlen launchers (the causal order: heaviest-first is harmless where the blocks
-// weigh the same)
-template <typename PT, typename K>
-static hipError_t launch_window_one(K kern, const PT &p, int D, hipStream_t s) {
-  const int nQ = (p.N + BM - 1) / BM;
-  const size_t smem = 4 * BN * (size_t)(D * 2);
-  if (smem > 48 * 1024) {
-    hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  PT pp = p;
-  pp.head_group = causal_head_group(p, D, 2);
-  set_block_divisors(pp, nQ, pp.head_group);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(kern, dim3(nQ * p.B * p.H), dim3(NTHREADS), smem, s, pp);
-  return hipGetLastError();
+  return with_tag(dtype, [&](auto tag) {
+    return with_dim_causal<64, 128>(p.D, p.is_causal, [&](auto d, auto c) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_varlen_paged_kernel<decltype(tag), d(), c()>, p, s); });
+  });
 }
 
 hipError_t launch_mfma_varlen_window(const VarlenWindowParams &p, int dtype, hipStream_t s) {
-  auto go = [&](auto tag) -> hipError_t {
-    using Tag = decltype(tag);
-    if (p.D == 64) return launch_window_one(fwd_mfma_window_kernel<Tag, 64>, p, 64, s);
-    if (p.D == 128) return launch_window_one(fwd_mfma_window_kernel<Tag, 128>, p, 128, s);
-    return hipErrorInvalidValue;
-  };
-  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
+  return with_tag(dtype, [&](auto tag) {
+    return with_dim<64, 128>(p.D, [&](auto d) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_window_kernel<decltype(tag), d()>, p, s); });
+  });
 }
 
 hipError_t launch_mfma_varlen_paged_window(const VarlenPagedWindowParams &p, int dtype, hipStream_t s) {
-  auto go = [&](auto tag) -> hipError_t {
-    using Tag = decltype(tag);
-    if (p.D == 64) return launch_window_one(fwd_mfma_window_paged_kernel<Tag, 64>, p, 64, s);
-    if (p.D == 128) return launch_window_one(fwd_mfma_window_paged_kernel<Tag, 128>, p, 128, s);
-    return hipErrorInvalidValue;
-  };
-  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
-}
-
-template <typename Tag, int D, bool CAUSAL>
-static hipError_t launch_split2_one(const Params &p, hipStream_t s) {
-  const int nQ = (p.N + BM - 1) / BM;
-  const size_t vrow = D * 2;
-  const size_t group = 2 * BN * (std::is_same<Tag, FP8>::value ? (size_t)D : vrow) + 2 * BN * vrow;  // as launch_one
-  const size_t merge_end = (size_t)(BM / WM) * WM * vrow + (size_t)(BM / WM) * (16 * (D / 32) + 2) * 64 * 4;
-  const size_t smem = std::max(2 * group, merge_end);
-  auto kern = fwd_mfma_split2_kernel<Tag, D, CAUSAL>;
-  if (smem > 48 * 1024) {
-    hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  Params pp = p;
-  pp.head_group = 0;
-  set_block_divisors(pp, nQ, 0);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(kern, dim3(nQ * p.B * p.H), dim3(2 * NTHREADS), smem, s, pp);
-  return hipGetLastError();
-}
-
-template <typename Tag, int D, bool CAUSAL>
-static hipError_t launch_h64s2_one(const Params &p, hipStream_t s) {
-  constexpr int ROWS = 64;
-  const int nQ = (p.N + ROWS - 1) / ROWS;
-  const size_t vrow = D * 2;
-  const size_t group = 2 * BN * (std::is_same<Tag, FP8>::value ? (size_t)D : vrow) + 2 * BN * vrow;  // as launch_one
-  const size_t merge_end = (size_t)ROWS * vrow + (size_t)(ROWS / WM) * (16 * (D / 32) + 2) * 64 * 4;
-  const size_t smem = std::max(2 * group, merge_end);
-  auto kern = fwd_mfma_h64s2_kernel<Tag, D, CAUSAL>;
-  if (smem > 48 * 1024) {
-    hipError_t e = set_dyn_lds_once((const void *)kern, (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  Params pp = p;
-  pp.head_group = 0;
-  set_block_divisors(pp, nQ, 0);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(kern, dim3(nQ * p.B * p.H), dim3(NTHREADS), smem, s, pp);
-  return hipGetLastError();
+  return with_tag(dtype, [&](auto tag) {
+    return with_dim<64, 128>(p.D, [&](auto d) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_window_paged_kernel<decltype(tag), d()>, p, s); });
+  });
 }
 
 bool mfma_h64s2_supported(int dtype, int D) { return (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) && D == 64; }
 
+// (the two split forms: one global head group)
 hipError_t launch_mfma_h64s2(const Params &p, int dtype, hipStream_t s) {
-  if (p.D != 64) return hipErrorInvalidValue;
-  if (dtype == FA_DTYPE_F16) return p.is_causal ? launch_h64s2_one<F16, 64, true>(p, s) : launch_h64s2_one<F16, 64, false>(p, s);
-  return p.is_causal ? launch_h64s2_one<BF16, 64, true>(p, s) : launch_h64s2_one<BF16, 64, false>(p, s);
+  return with_tag(dtype, [&](auto tag) {
+    return with_dim_causal<64>(p.D, p.is_causal, [&](auto d, auto c) {
+      return launch_blocks(fwd_mfma_h64s2_kernel<decltype(tag), d(), c()>, p, 64, NTHREADS, mfma_lds_bytes<decltype(tag), d(), 2, 64>(), 0, s);
+    });
+  });
 }
 
 bool mfma_split2_supported(int dtype, int D) {
@@ -1127,32 +977,22 @@ bool mfma_split2_supported(int dtype, int D) {
 }
 
 hipError_t launch_mfma_split2(const Params &p, int dtype, hipStream_t s) {
-  auto go = [&](auto tag) -> hipError_t {
-    using Tag = decltype(tag);
-    if (p.D == 64) return p.is_causal ? launch_split2_one<Tag, 64, true>(p, s) : launch_split2_one<Tag, 64, false>(p, s);
-    if (p.D == 128) return p.is_causal ? launch_split2_one<Tag, 128, true>(p, s) : launch_split2_one<Tag, 128, false>(p, s);
-    return hipErrorInvalidValue;
+  auto go = [&](auto tag) {
+    return with_dim_causal<64, 128>(p.D, p.is_causal, [&](auto d, auto c) {
+      return launch_blocks(fwd_mfma_split2_kernel<decltype(tag), d(), c()>, p, BM, 2 * NTHREADS, mfma_lds_bytes<decltype(tag), d(), 2>(), 0, s);
+    });
   };
-  if (dtype == FA_DTYPE_FP8_E4M3) return go(FP8{});
-  return dtype == FA_DTYPE_F16 ? go(F16{}) : go(BF16{});
+  return dtype == FA_DTYPE_FP8_E4M3 ? go(FP8{}) : with_tag(dtype, go);
 }
 
-template <typename Tag>
+template <typename Tag, int... Ds>
 static hipError_t launch_dt(const Params &p, hipStream_t s) {
-  constexpr bool IS8 = std::is_same<Tag, FP8>::value;
-  switch (p.D) {
-    case 64: return p.is_causal ? launch_one<Tag, 64, true>(p, s) : launch_one<Tag, 64, false>(p, s);
-    case 128: return p.is_causal ? launch_one<Tag, 128, true>(p, s) : launch_one<Tag, 128, false>(p, s);
-    case 256: return p.is_causal ? launch_one<Tag, 256, true>(p, s) : launch_one<Tag, 256, false>(p, s);
-    case 32: if constexpr (!IS8) return p.is_causal ? launch_one<Tag, 32, true>(p, s) : launch_one<Tag, 32, false>(p, s); break;
-    case 96: if constexpr (!IS8) return p.is_causal ? launch_one<Tag, 96, true>(p, s) : launch_one<Tag, 96, false>(p, s); break;
-  }
-  return hipErrorInvalidValue;
+  return with_dim_causal<Ds...>(p.D, p.is_causal, [&](auto d, auto c) { return launch_one<Tag, d(), c()>(p, s); });
 }
 
 hipError_t launch_mfma(const Params &p, int dtype, hipStream_t s) {
-  if (dtype == FA_DTYPE_FP8_E4M3) return launch_dt<FP8>(p, s);
-  return dtype == FA_DTYPE_F16 ? launch_dt<F16>(p, s) : launch_dt<BF16>(p, s);
+  if (dtype == FA_DTYPE_FP8_E4M3) return launch_dt<FP8, 64, 128, 256>(p, s);  // (an fp8 row of head_dim 32 / 96 has no kernel)
+  return dtype == FA_DTYPE_F16 ? launch_dt<F16, 32, 64, 96, 128, 256>(p, s) : launch_dt<BF16, 32, 64, 96, 128, 256>(p, s);
 }
 
 }  // namespace fa

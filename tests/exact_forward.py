@@ -25,16 +25,16 @@ The bars, per element (no fitted factor; units of 2^-24 = one fp32 rounding, a h
      + EPI_O * 2^-24 |O|                           the epilogue: reciprocal or division of l (<= 2), its product with the accumulator
                                                    (1), one ulp on l in case the hardware exp2 of an integer is not the exact power of
                                                    two (2), the cross-lane addition of the row-sum halves (1): 6 covers every kernel
-                                                   (flash_attention_metal_amd/csrc/fa_mfma_kernel.hip:697-710, fa_mfma16_kernel.hip:510-526, fa_fp8_kernel.hip:326-336,
-                                                   fa_fwd_splitkv_kernel.hip:259-277, fa_decode_kernel.hip:488-491)
+                                                   (flash_attention_metal_amd/csrc/fa_mfma_kernel.hip:800-834, fa_mfma16_kernel.hip:648-668, fa_fp8_kernel.hip:325-343,
+                                                   fa_fwd_splitkv_kernel.hip:266-290, fa_decode_kernel.hip:508-511)
      + merge: 2 (S + 3) * 2^-24 sum_j p |v|        kernels that merge S key splits: a weight exp2(m_s - M) within one ulp (2), its
                                                    product (1) and S additions, once for the numerator and once for l
-                                                   (fa_mfma_kernel.hip:680-688, fa_fwd_splitkv_kernel.hip:246-271, fa_decode_kernel.hip:459-487)
+                                                   (fa_mfma_kernel.hip:784-792, fa_fwd_splitkv_kernel.hip:253-278, fa_decode_kernel.hip:468-507)
      + family B / unproven rows: n * 2^-24 sum_j p |v|,  n = visible keys + tiles  (one addition per key, one rescale per tile)
   LSE  EPI_L * 2^-23 (|m'| ln 2 + |ln l'| + |LSE|) + the relative error of l from the terms above, where m' / l' are the reference and
-       the row sum as the kernel holds them (m + shift, l / 2^shift: shift = BIAS 7 / 3 of fa_mfma16_kernel.hip:197-201, -SHIFT = -3 of
+       the row sum as the kernel holds them (m + shift, l / 2^shift: shift = BIAS 7 / 3 of fa_mfma16_kernel.hip:230-234, -SHIFT = -3 of
        fa_fp8_kernel.hip:13-15, else 0) and EPI_L = 4: log, product with ln 2 or with scale, the sum, fp32(ln 2) itself
-       (fa_mfma_kernel.hip:703, fa_mfma16_kernel.hip:519, fa_fp8_kernel.hip:327, fa_fwd_splitkv_kernel.hip:260, fa_decode_kernel.hip:492).
+       (fa_mfma_kernel.hip:819, fa_mfma16_kernel.hip:658, fa_fp8_kernel.hip:331, fa_fwd_splitkv_kernel.hip:267, fa_decode_kernel.hip:512).
 """
 from types import SimpleNamespace
 
@@ -65,7 +65,7 @@ def c2_of(scale):
 def reference_shift(variant, dtype):
     """How far the kernel's reference sits from the row maximum it was set from (log2 units), per the kernel headers."""
     if variant == "mfma16":
-        return 3.0 if dtype == "f16" else 7.0  # fa_mfma16_kernel.hip:197-201 (BIAS)
+        return 3.0 if dtype == "f16" else 7.0  # fa_mfma16_kernel.hip:230-234 (BIAS)
     if variant == "mfma_fp8pv":
         return -3.0  # fa_fp8_kernel.hip:13-15 (SHIFT)
     return 0.0
@@ -90,7 +90,7 @@ TILE_RISE_E4M3 = 6  # ... for the kernel with e4m3 probabilities (variant mfma_f
 
 def ramps(nk, rise=TILE_RISE):
     """The two integer ramps of family B over the keys (non-decreasing, 0 at key 0). A probability is formed against a reference that
-    is at least the largest score of its own tile (plus BIAS = 3 in the f16 16x16x32 kernel, fa_mfma16_kernel.hip:197-201), and f16
+    is at least the largest score of its own tile (plus BIAS = 3 in the f16 16x16x32 kernel, fa_mfma16_kernel.hip:230-234), and f16
     holds powers of two down to 2^-24 only: rise inside a tile (<= 15) + depth (3) + BIAS (3) stays below 24, so every P is exact in
     every type. The kernel with e4m3 probabilities forms P' = 8 P against its reference (fa_fp8_kernel.hip:13-15); e4m3 is normal down to
     2^-6, so its cases take rise <= 6: rise + depth (3) <= 9 keeps every P' a normal e4m3 power of two, and a step of 6 still sends
@@ -399,7 +399,7 @@ def _some_heads(B, Hq):
 
 def decode_splits(nk):
     """An upper estimate of the work items the decode kernels merge: at most one per 64-key tile, at most 256
-    (flash_attention_metal_amd/csrc/fa_decode_kernel.hip:444; the kernel picks S from the chip's item slots, never more)."""
+    (flash_attention_metal_amd/csrc/fa_decode_kernel.hip:449; the kernel picks S from the chip's item slots, never more)."""
     return min(256, (nk + TILE - 1) // TILE)
 
 

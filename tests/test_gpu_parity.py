@@ -403,6 +403,35 @@ def test_generalised_forward_gqa_and_rectangular(fa, oracle_mod, dtype):
         fa.flash_attention_forward(x, x[:, :3].contiguous(), x[:, :3].contiguous())
 
 
+def test_splitkv_lds_attribute_covers_every_split_count():
+    # The split-KV kernel's dynamic LDS depends on the RUN-TIME split count (csrc/fa_fwd_splitkv_kernel.hip), but the attribute that
+    # allows more than 48 KiB is declared once per (instantiation, device): it has to be declared for the largest size. In a FRESH
+    # process, so that no earlier test has declared it: four splits (N = 256: 64 KiB, the first size above 48 KiB), then eight
+    # (N = 1024: 128 KiB) of the same instantiation; a declaration of the first call's own size is FA_ERR_LAUNCH from the second.
+    # Then the causal bf16 instantiation in the opposite order.
+    import os
+    import subprocess
+    import sys
+
+    tests = os.path.dirname(os.path.abspath(__file__))
+    child = f"""
+import sys
+sys.path[:0] = [{os.path.dirname(tests)!r}, {tests!r}]
+import flash_attention_metal_amd as fa
+import oracle
+from util import check, make_qkv
+oracle.build()
+fa.load_library()
+for dtype, causal, lengths in (("f16", False, (256, 1024)), ("bf16", True, (1024, 256))):
+    for N in lengths:
+        q, k, v = make_qkv(oracle, 1, 2, N, 64, dtype)
+        check(fa, oracle, q, k, v, dtype, causal, "mfma_splitkv")
+print("both orders ok")
+"""
+    r = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", child], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("both orders ok"), r.stdout + r.stderr
+
+
 def test_reentrant_across_streams(fa, oracle_mod):
     # include/fa_mi355.h: "no state, re-entrant across devices/streams": two different problems launched
     # concurrently on two streams give the same bits as when run alone
