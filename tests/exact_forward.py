@@ -148,6 +148,85 @@ def build(family, B, Hq, Hkv, Nq, Nk, D, dtype, causal, kexp=0, span=7, seed=0, 
                            span=span, rise=rise, vbits=vb, lens=None if lens is None else [int(x) for x in lens], c=c)
 
 
+# ---- sliding-window cases (tests/window.py holds their catalogue) -------------------------------------------------------------------
+WINDOW_CSPAN = 1      # c_j = 1: the ramp, not c, spreads the scores, and a small c-span leaves the ramp the depth a proven row can have
+WINDOW_RESERVED = 6   # the last six coordinates carry the ramp; every query holds 1 there
+WINDOW_BUDGET = 21    # (largest - smallest visible score) + c-span of a shallow row: every probability >= 2^-24 with three units to spare
+WINDOW_STEP = {"shallow": 1, "steep": 1, "cliff": 3}  # the ramp's step (shallow: once per `every` keys; else per key)
+INT_CAP = {"bf16": 256, "f16": 2048, "fp8": 16}  # integers up to here are exact in the type
+
+
+def window_ramp(ramp, nk, every):
+    """The monotone integer ramp along the keys, one step per `every` keys: "fall" from key 0 down to 0 at the last key (keys in front
+    of a row's lower bound score above everything it sees), "rise" from 0 at key 0 (keys past its upper bound do)."""
+    j = np.arange(nk)
+    return (nk - 1 - j) // every if ramp == "fall" else j // every
+
+
+def _window_every(ramp, Lq, Lk, window, cap_total, cspan):
+    """The smallest step length at which, for every live row, the ramp over the keys it sees spans no more than
+    WINDOW_BUDGET - 2 * cspan (the scores add at most the c-span to that), a rising ramp climbs by no more than WINDOW_BUDGET - cspan
+    inside a 64-key tile, and the ramp's largest value fits the reserved coordinates."""
+    case = SimpleNamespace(q=np.zeros((1, 1, Lq, 1)), k=np.zeros((1, 1, Lk, 1)), lens=None, causal=False, window=window)
+    vis = visible(case, 0, np.arange(Lq))
+    live = vis.any(1)
+    first, last = vis.argmax(1)[live], (Lk - 1 - vis[:, ::-1].argmax(1))[live]
+    room = WINDOW_BUDGET - 2 * cspan
+    every = 1
+    while True:
+        r = window_ramp(ramp, Lk, every)
+        tile_rise = max(int(abs(r[min(t + TILE, Lk) - 1] - r[t])) for t in range(0, Lk, TILE))
+        tile_ok = ramp == "fall" or tile_rise <= WINDOW_BUDGET - cspan
+        if (not live.any() or int(np.abs(r[last] - r[first]).max()) <= room) and tile_ok and int(r.max()) <= cap_total:
+            return every
+        every += 1
+
+
+def build_window(ramp, slope, Hq, Hkv, Lq, Lk, D, dtype, window, kexp=0, seed=0, prove=None, cspan=WINDOW_CSPAN):
+    """One sequence under a sliding window (B = 1; case.window = (wl, wr) enters visible()): the construction of build() -- key j carries
+    -c_j (1 .. cspan) on coordinate j mod Dc, queries are 0/1 masks, V on its grid, scale = fp32(ln 2) 2^k -- plus a monotone
+    integer ramp along the keys (window_ramp) on the WINDOW_RESERVED last coordinates, which every query holds a 1 on.
+      slope "shallow": one step per `every` keys, `every` the smallest at which every row's visible depth plus the c-span stays within
+              WINDOW_BUDGET (_window_every) and -- with `prove`, the default -- criterion() proves every live row of every head: family
+              "A", case.span = the largest visible depth of the case.
+      slope "steep": one step per key (bf16: powers of two stay exact far below 2^-24); partial sums may round: family "B".
+      slope "cliff": three steps per key (bf16, narrow windows): a key 45 places in front of a row's bound -- every wave has such rows --
+              scores 135 above everything the row sees, which no bf16 probability survives. Family "B"."""
+    assert ramp in ("fall", "rise") and slope in WINDOW_STEP and Hq % Hkv == 0 and (slope == "shallow" or dtype == "bf16")
+    prove = (slope == "shallow") if prove is None else prove
+    vb = VBITS[dtype]
+    Dc = D - WINDOW_RESERVED
+    rng = np.random.default_rng(seed)
+    c = rng.integers(1, cspan + 1, (1, Hkv, Lk))
+    k = np.zeros((1, Hkv, Lk, D), np.float32)
+    j = np.arange(Lk)
+    k[:, :, j, j % Dc] = -c
+    q = np.zeros((1, Hq, Lq, D), np.float32)
+    q[..., :Dc] = rng.integers(0, 2, (1, Hq, Lq, Dc))
+    q[..., Dc:] = 1.0
+    q *= np.float32(2.0 ** -kexp)
+    v = (rng.integers(-(1 << vb), (1 << vb) + 1, (1, Hkv, Lk, D)) / float(1 << vb)).astype(np.float32)
+    case = SimpleNamespace(family="A" if slope == "shallow" else "B", q=q, k=k, v=v, dtype=dtype, causal=False, window=tuple(window), kexp=kexp,
+                           scale=exact_scale(kexp), span=0, vbits=vb, lens=None, c=c, ramp=ramp, slope=slope, every=1)
+    every = 1 if slope != "shallow" else _window_every(ramp, Lq, Lk, window, WINDOW_RESERVED * INT_CAP[dtype], cspan)
+    rows = np.arange(Lq)
+    vis = visible(case, 0, rows)
+    while True:
+        r = window_ramp(ramp, Lk, every) * WINDOW_STEP[slope]
+        for coord, part in zip(range(Dc, D), _spread(r, WINDOW_RESERVED, INT_CAP[dtype])):
+            k[..., coord] = part
+        depth = 0
+        for h in range(Hq):
+            s = scores(case, 0, h, rows)
+            live = vis.any(1)
+            if live.any():
+                depth = max(depth, int((np.where(vis, s, -np.inf).max(1)[live] - np.where(vis, s, np.inf).min(1)[live]).max()))
+        case.span, case.every = depth, every
+        if not prove or all(criterion(case, reference_head(case, 0, h), False)[vis.any(1)].all() for h in range(Hq)):
+            return case
+        every += max(1, every // 8)
+
+
 # ---- representability --------------------------------------------------------------------------------------------------------
 def round_bf16(x):
     b = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
@@ -181,11 +260,17 @@ def representable(x, dtype):
 
 # ---- the fp64 reference ------------------------------------------------------------------------------------------------------
 def visible(case, b, rows):
-    """[len(rows), Nk] mask of the keys row i of sequence b sees (bottom-right causal alignment on the sequence's own length)."""
+    """[len(rows), Nk] mask of the keys row i of sequence b sees (bottom-right causal alignment on the sequence's own length; a case
+    with `window = (wl, wr)` -- build_window() -- takes the sliding-window rule instead)."""
     Nq, Nk = case.q.shape[2], case.k.shape[2]
     L = Nk if case.lens is None else min(case.lens[b], Nk)
     jj = np.arange(Nk)[None, :]
     vis = np.broadcast_to(jj < L, (len(rows), Nk))
+    window = getattr(case, "window", None)
+    if window is not None:  # the rule of tests/window.py visible(): the same offset, a negative side is unbounded
+        wl, wr = window
+        ii = np.asarray(rows, np.int64)[:, None] + (L - Nq)
+        return vis & ((jj >= ii - wl) if wl >= 0 else True) & ((jj <= ii + wr) if wr >= 0 else True)
     if case.causal:
         vis = vis & (jj <= np.asarray(rows)[:, None] + (L - Nq))
     return vis
