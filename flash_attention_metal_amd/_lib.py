@@ -38,6 +38,8 @@ SYMBOLS = {
     "fa_bwd_workspace_bytes_ex": (c_longlong, [c_int] * 7 + [c_longlong] * 4),
     "fa_bwd_supported": (c_int, [c_int, c_int]),
     "fa_bwd_varlen": (c_int, [c_void_p] * 12 + [c_int] * 8 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_void_p]),
+    "fa_bwd_varlen_window": (c_int, [c_void_p] * 12 + [c_int] * 8 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_int, c_void_p]),
+    "fa_window_query_range": (c_int, [c_int] * 6 + [c_void_p, c_void_p]),
     "fa_bwd_varlen_workspace_bytes": (c_longlong, [c_int, c_int]),
     "fa_bwd_varlen_supported": (c_int, [c_int, c_int]),
     "fa_bwd_algorithmic_flops": (c_double, [c_int, c_int, c_int, c_int, c_int]),

@@ -31,7 +31,7 @@ int fail(int code, const char *fmt, ...) {
 //    B * Hq * Nq and B * Hkv * 256 for the decodes;
 //  - fa_fwd_varlen has row and head strides (no batch): each at least D and a multiple of 8, checked in its own lines; its size guard is
 //    (max_seqlen + 128) * row_stride * 2 < 4 GiB per sequence, for q and for k / v; its grid guard B * Hq * ceil(max_seqlen_q / 128);
-//  - fa_bwd_varlen: fa_fwd_varlen's rules, with the grid guard for both of its kernels (B * Hq * ceil(max_seqlen_q / 128) and
+//  - fa_bwd_varlen and fa_bwd_varlen_window (one bwd_varlen_impl): fa_fwd_varlen's rules, with the grid guard for both of its kernels (B * Hq * ceil(max_seqlen_q / 128) and
 //    B * Hkv * ceil(max_seqlen_k / 128));
 //  - fa_fwd_varlen_paged: fa_fwd_varlen's rules for q and the grid, page_pool_ok for the pools and tables (the paged decode's rules);
 //    fa_kv_append_paged: varlen_strides_ok for the new rows, page_pool_ok, and a grid of B * ceil(max_seqlen_new / 16) x Hkv;
@@ -750,34 +750,65 @@ int fa_bwd_ex(const void *q, const void *k, const void *v, const void *o, const 
 
 long long fa_bwd_varlen_workspace_bytes(int Hq, int total_q) { return Hq < 1 || total_q < 1 ? 0 : (long long)Hq * total_q * 4; }
 int fa_bwd_varlen_supported(int dtype, int D) { return fa::bwd_varlen_supported(dtype, D); }
-int fa_bwd_varlen(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq, float *dk,
-                  float *dv, void *workspace, const int *cu_seqlens_q, const int *cu_seqlens_k, int B, int Hq, int Hkv, int total_q,
-                  int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale, long long q_row_stride, long long q_head_stride,
-                  long long kv_row_stride, long long kv_head_stride, int is_causal, int dtype, void *hip_stream) {
+// fa_bwd_varlen (window_left = -1, window_right = is_causal ? 0 : -1) and fa_bwd_varlen_window: one set of rules, one launch path
+static int bwd_varlen_impl(const char *fn, const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse,
+                           float *dq, float *dk, float *dv, void *workspace, const int *cu_seqlens_q, const int *cu_seqlens_k, int B, int Hq,
+                           int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale, long long q_row_stride,
+                           long long q_head_stride, long long kv_row_stride, long long kv_head_stride, int window_left, int window_right,
+                           int dtype, void *hip_stream) {
   g_err[0] = 0;
-  const char *fn = "fa_bwd_varlen";
   TRY(nonnull(fn, {q, k, v, o, d_o, lse, dq, dk, dv, workspace, cu_seqlens_q, cu_seqlens_k}));
   TRY(positive(fn, {B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
   if (!fa_bwd_varlen_supported(dtype, D))
-    return fail(FA_ERR_UNSUPPORTED, "fa_bwd_varlen: needs f16 / bf16 and D = 64 | 128, got dtype=%s D=%d", fa_dtype_name(dtype), D);
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 and D = 64 | 128, got dtype=%s D=%d", fn, fa_dtype_name(dtype), D);
   if (max_seqlen_q > total_q || max_seqlen_k > total_k)
-    return fail(FA_ERR_INVALID_ARG, "fa_bwd_varlen: max_seqlen (%d, %d) exceeds the token count (%d, %d)", max_seqlen_q, max_seqlen_k, total_q, total_k);
+    return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen (%d, %d) exceeds the token count (%d, %d)", fn, max_seqlen_q, max_seqlen_k, total_q, total_k);
   TRY(varlen_strides_ok(fn, "", D, q_row_stride, q_head_stride, stride_mult(dtype)));
   TRY(varlen_strides_ok(fn, "key/value ", D, kv_row_stride, kv_head_stride, stride_mult(dtype)));
   TRY(aligned16(fn, "tensors", {q, k, v, o, d_o, dq, dk, dv}));
-  if (((uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "fa_bwd_varlen: cu_seqlens_q / cu_seqlens_k must be int32-aligned");
-  if (((uintptr_t)lse | (uintptr_t)workspace) & 3) return fail(FA_ERR_INVALID_ARG, "fa_bwd_varlen: lse / workspace must be fp32-aligned");
+  if (((uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q / cu_seqlens_k must be int32-aligned", fn);
+  if (((uintptr_t)lse | (uintptr_t)workspace) & 3) return fail(FA_ERR_INVALID_ARG, "%s: lse / workspace must be fp32-aligned", fn);
   // as fa_fwd_varlen: 32-bit byte offsets inside ONE sequence of one head of the 16-bit tensors (the gradients are stored through 64-bit
   // addresses), and the staging may address up to two 64-row tiles past its end
   TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
   TRY(head_fits(fn, (double)(max_seqlen_k + 128) * (double)kv_row_stride * 2, 4, " (one sequence of max_seqlen_k rows)"));
   TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));   // the dQ kernel's
   TRY(grid_fits(fn, (long long)B * Hkv, max_seqlen_k));  // the dK/dV kernel's
-  return launched(fn, fa::launch_bwd_varlen(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv,
-                                            total_q, total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride,
-                                            kv_row_stride, kv_head_stride, is_causal ? 1 : 0, dtype, (hipStream_t)hip_stream));
+  const int route = window_route(window_left, window_right);
+  if (route != WIN_KERNEL)
+    return launched(fn, fa::launch_bwd_varlen(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv,
+                                              total_q, total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride,
+                                              kv_row_stride, kv_head_stride, route == WIN_CAUSAL ? 1 : 0, dtype, (hipStream_t)hip_stream));
+  return launched(fn, fa::launch_bwd_varlen_window(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, cu_seqlens_q, cu_seqlens_k, B, Hq,
+                                                   Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride,
+                                                   kv_row_stride, kv_head_stride, window_clamp(window_left, max_seqlen_k),
+                                                   window_clamp(window_right, max_seqlen_q), dtype, (hipStream_t)hip_stream));
+}
+int fa_bwd_varlen(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq, float *dk,
+                  float *dv, void *workspace, const int *cu_seqlens_q, const int *cu_seqlens_k, int B, int Hq, int Hkv, int total_q,
+                  int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale, long long q_row_stride, long long q_head_stride,
+                  long long kv_row_stride, long long kv_head_stride, int is_causal, int dtype, void *hip_stream) {
+  return bwd_varlen_impl("fa_bwd_varlen", q, k, v, o, d_o, lse, dq, dk, dv, workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q, total_k,
+                         max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride, -1,
+                         is_causal ? 0 : -1, dtype, hip_stream);
+}
+int fa_bwd_varlen_window(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq, float *dk,
+                         float *dv, void *workspace, const int *cu_seqlens_q, const int *cu_seqlens_k, int B, int Hq, int Hkv, int total_q,
+                         int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale, long long q_row_stride,
+                         long long q_head_stride, long long kv_row_stride, long long kv_head_stride, int window_left, int window_right,
+                         int dtype, void *hip_stream) {
+  return bwd_varlen_impl("fa_bwd_varlen_window", q, k, v, o, d_o, lse, dq, dk, dv, workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q,
+                         total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride,
+                         window_left, window_right, dtype, hip_stream);
+}
+int fa_window_query_range(int Lq, int Lk, int window_left, int window_right, int key_first, int key_last, int *row_lo, int *row_hi) {
+  g_err[0] = 0;
+  if (!row_lo || !row_hi) return fail(FA_ERR_INVALID_ARG, "fa_window_query_range: null pointer");
+  if (Lq < 0 || Lk < 0) return fail(FA_ERR_INVALID_ARG, "fa_window_query_range: lengths must be >= 0");
+  fa::window_query_range(Lq, Lk, window_left, window_right, key_first, key_last, *row_lo, *row_hi);
+  return FA_OK;
 }
 
 }  // extern "C"

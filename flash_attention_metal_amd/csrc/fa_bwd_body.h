@@ -1,5 +1,6 @@
-// fa_bwd_body.h -- what the translation units of the backward share: fa_bwd_kernels.hip (dense: fa_bwd / fa_bwd_ex) and
-// fa_bwd_varlen_kernels.hip (packed variable-length sequences: fa_bwd_varlen). The algorithm and its history are described at the top of
+// fa_bwd_body.h -- what the translation units of the backward share: fa_bwd_kernels.hip (dense: fa_bwd / fa_bwd_ex),
+// fa_bwd_varlen_kernels.hip (packed variable-length sequences: fa_bwd_varlen) and fa_bwd_window_kernels.hip (the same under a sliding
+// window: fa_bwd_varlen_window, FA_BWD_WINDOW = 1 on top of FA_BWD_VARLEN = 1). The algorithm and its history are described at the top of
 // fa_bwd_kernels.hip. Here: the parameter blocks and the per-head-dim constants; the two kernel bodies themselves are the texts
 // fa_bwd_dq_body.inc and fa_bwd_dkdv_body.inc, which each __global__ function of either file includes as its body with FA_BWD_VARLEN
 // set to 0 or 1. Text, not a function: behind a forced-inline function the compiler copies the parameter block before it inlines, which
@@ -33,7 +34,18 @@ struct BwdVarlenParams : BwdParams {
   long long q_rs, kv_rs;   // row strides, elements
 };
 
+// one fa_bwd_varlen_window call (the window mode of the bodies, FA_BWD_WINDOW = 1 on top of the varlen mode; fa_bwd_window_kernels.hip):
+// the varlen call's parameters plus both bounds, which the host has made non-negative (an unbounded or oversized side is the smallest
+// value that can never bind: wl <= max_seqlen_k, wr <= max_seqlen_q -- so that coff - wl and row + coff + wr stay inside an int)
+struct BwdWindowParams : BwdVarlenParams {
+  int wl, wr;
+};
+
 constexpr float LOG2E = 1.4426950408889634f;
+
+#ifndef FA_BWD_WINDOW
+#define FA_BWD_WINDOW 0  // the bodies' window mode: 1 only around the kernels of fa_bwd_window_kernels.hip
+#endif
 
 #ifndef FA_BWD_DMA
 #define FA_BWD_DMA 1  // 1: the streamed tiles go global -> LDS by LDS-DMA (buffer_load ... lds; the chunk swizzle sits on the source address):

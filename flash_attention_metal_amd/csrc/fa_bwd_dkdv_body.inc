@@ -1,6 +1,7 @@
 // fa_bwd_dkdv_body.inc -- the body of the dK/dV kernels (fa_bwd_body.h says how it is used): included inside
 //   template <typename Tag, int D, bool CAUSAL, bool PAD> __global__ void kernel(BwdParams or BwdVarlenParams p)
-// with FA_BWD_VARLEN defined to 0 or 1.
+// with FA_BWD_VARLEN defined to 0 or 1, and FA_BWD_WINDOW (varlen only) to 0 or 1: the window mode, whose parameter block is
+// BwdWindowParams. Its arms are chosen in the preprocessor, so that the text the other kernels compile is the text they had.
 // dK, dV: workgroup = 128 keys, wave = 32 keys (key on the lane, queries in the registers)
 #if FA_BWD_VARLEN
 #define FA_VP p
@@ -11,6 +12,7 @@
 #define FA_NK (VARLEN ? LK : p.Nk)
   constexpr bool VARLEN = FA_BWD_VARLEN != 0;
   static_assert(!VARLEN || (!PAD && (D == 64 || D == 128) && FA_BWD_DMA != 0), "varlen mode: head_dim 64 / 128, LDS-DMA staging");
+  static_assert(FA_BWD_WINDOW == 0 || (VARLEN && CAUSAL), "window mode: on top of the varlen mode");
   FA_BWD_CONSTS(D, bwd_sub_kv(D));
   FA_BWD_PAD(PAD);
   using M = MT<Tag>;
@@ -107,8 +109,21 @@
     st_r[i] = row * BRB + ((ch ^ u_swz(row)) << 4);
   }
   // query tiles of BT rows; under the causal mask only tiles that reach this block's first key
+#if FA_BWD_WINDOW
+  // window (all wave-uniform, kept in scalar registers; per-lane limits are formed where they are used): key j is seen by queries
+  // j - cu <= i <= j - cl, so the walk is the query tiles [t_begin, nTq) of window_query_range of the block's keys -- a last tile as
+  // well as a first. No query sees any key of the block: an empty walk, and the zero accumulators are stored.
+  const int cl = coff - p.wl, cu = coff + p.wr;
+  int w_lo, w_hi;
+  window_query_range(LQ, LK, p.wl, p.wr, k0, k0 + BM - 1, w_lo, w_hi);
+  const int nTq = w_lo < w_hi ? (w_hi + BT - 1) / BT : 0;
+  const int t_begin = w_lo < w_hi ? w_lo / BT : 0;
+#define FA_DEAD_OFF cu
+#else
   const int nTq = (FA_NQ + BT - 1) / BT;
   const int t_begin = CAUSAL ? max(k0 - coff, 0) / BT : 0;  // the first query that sees key k0 is k0 - coff
+#define FA_DEAD_OFF coff
+#endif
   static_assert(2 * BT <= NTHREADS, "one thread per staged row constant");
 
   u32x4 qst[NCH], ost[NCH];
@@ -201,7 +216,8 @@
       const int qi = wt * BT + FA_TID_ROW;
       // (varlen under the mask, Lk < Lq: a row with no visible key -- the forward's integer test; its LSE is -inf and its delta of no
       // use -- is staged like a row past the end: -inf and 0, so the +inf never reaches a score chain and the row adds exactly nothing)
-      const float v = (VARLEN && CAUSAL) ? (FA_TID_LT(BT) ? ((qi < LQ && qi + coff >= 0) ? -rowv * LOG2E : -INFINITY) : ((qi < LQ && qi + coff >= 0) ? -rowv : 0.0f))
+      // (window: the row's upper bound qi + cu takes the place of qi + coff)
+      const float v = (VARLEN && CAUSAL) ? (FA_TID_LT(BT) ? ((qi < LQ && qi + FA_DEAD_OFF >= 0) ? -rowv * LOG2E : -INFINITY) : ((qi < LQ && qi + FA_DEAD_OFF >= 0) ? -rowv : 0.0f))
                                          : ((tid < BT) ? (qi < FA_NQ ? -rowv * LOG2E : -INFINITY) : (qi < FA_NQ ? -rowv : 0.0f));
       lds_write_b32(ROWS + buf * (2 * BT * 4) + FA_TID4, __builtin_bit_cast(unsigned, v));
     }
@@ -242,12 +258,23 @@
     for (int sub = 0; sub < BSUB; ++sub) {
     const int sub_c = sub;
     const int qt0 = t * BT + sub * BN;
+    // (window: some query of the sub-tile sees one of this wave's 32 keys -- its last query reaches the first key from below, its first
+    // query the last key from above)
+#if FA_BWD_WINDOW
+    if (qt0 < FA_NQ && qt0 + BN - 1 + cu >= kw0 && qt0 + cl <= kw0 + WM - 1) {
+#else
     if (qt0 < FA_NQ && (!CAUSAL || qt0 + BN - 1 + coff >= kw0)) {  // some query of the sub-tile sees this wave's first key
+#endif
       // (the buffer's offset is inside koff / voff / rowoff, toggled once per tile: everything added here is an immediate)
       const int QS = sub_c * BTILE, OS = 2 * STILE + sub_c * BTILE;  // Q / dO sub-tile images, relative to koff / voff
       const unsigned rows = rowoff + sub_c * (BN * 4);
       // only sub-tiles that cross the diagonal for this wave need the per-element mask (wave-uniform)
+      // (window: either edge crosses it)
+#if FA_BWD_WINDOW
+      const bool need_mask = (qt0 + cu < kw0 + WM - 1) || (qt0 + BN - 1 + cl > kw0);
+#else
       const bool need_mask = CAUSAL && (qt0 + coff < kw0 + WM - 1);
+#endif
       // One 32-query half (qb) at a time -- scores, P / dS, then its share of dV / dK -- so that only ONE score and ONE dP tuple
       // are live (round 3 first kept both halves': 212 VGPR, two waves per SIMD; this form fits three).
       static_for<0, 2>([&](auto qbc) {
@@ -303,6 +330,15 @@
         if (need_mask) {  // key > query (kernels.metal:748): S' = -inf there. A wave-uniform BRANCH: written as a per-element
           // condition hipcc turned it into 32 compare + select pairs on every tile (seen in the ISA). Register 4g+e holds query
           // qt0 + 32qb + 8g + 4h + e: compared as a constant against ONE per-lane limit (else: sixteen threshold registers)
+          // (window: query < key - cu or query > key - cl -> masked; the second limit is the first plus the scalar cu - cl)
+#if FA_BWD_WINDOW
+          int lane_m = lane;
+          asm volatile("" : "+v"(lane_m));
+          const int lim = kw0 + (lane_m & 31) - cu - 4 * (lane_m >> 5) - qt0 - 32 * qb;
+          const int lim_hi = lim + (cu - cl);
+#pragma unroll
+          for (int i = 0; i < 16; ++i) sq[i] = (8 * (i >> 2) + (i & 3) < lim || 8 * (i >> 2) + (i & 3) > lim_hi) ? -INFINITY : sq[i];
+#else
 #if FA_BWD_VARLEN
           int lane_m = lane;
           asm volatile("" : "+v"(lane_m));
@@ -312,6 +348,7 @@
 #endif
 #pragma unroll
           for (int i = 0; i < 16; ++i) sq[i] = (8 * (i >> 2) + (i & 3) < lim) ? -INFINITY : sq[i];
+#endif
         }
         vec8 pf[2], df[2];
 #pragma unroll
@@ -390,3 +427,4 @@
 #undef FA_TID_LT
 #undef FA_TID_ROW
 #undef FA_TID4
+#undef FA_DEAD_OFF

@@ -1,6 +1,7 @@
 // fa_bwd_dq_body.inc -- the body of the dQ kernels (fa_bwd_body.h says how it is used): included inside
 //   template <typename Tag, int D, bool CAUSAL, bool PAD> __global__ void kernel(BwdParams or BwdVarlenParams p)
-// with FA_BWD_VARLEN defined to 0 or 1.
+// with FA_BWD_VARLEN defined to 0 or 1, and FA_BWD_WINDOW (varlen only) to 0 or 1: the window mode, whose parameter block is
+// BwdWindowParams. Its arms are chosen in the preprocessor, so that the text the other kernels compile is the text they had.
 // dQ: workgroup = 128 query rows, wave = 32 rows (query on the lane, keys in the registers)
 #if FA_BWD_VARLEN
 #define FA_VP p
@@ -11,6 +12,7 @@
 #define FA_NK (VARLEN ? LK : p.Nk)
   constexpr bool VARLEN = FA_BWD_VARLEN != 0;
   static_assert(!VARLEN || (!PAD && (D == 64 || D == 128) && FA_BWD_DMA != 0), "varlen mode: head_dim 64 / 128, LDS-DMA staging");
+  static_assert(FA_BWD_WINDOW == 0 || (VARLEN && CAUSAL), "window mode: on top of the varlen mode, in the masked kernels' block order");
   FA_BWD_CONSTS(D, bwd_sub_dq(D));
   FA_BWD_PAD(PAD);
   using M = MT<Tag>;
@@ -33,6 +35,10 @@
   int LQ = 0, LK = 0;          // queries and keys of this block's sequence
   unsigned qrb = 0, kvrb = 0;  // row pitch of Q / O / dO and of K / V in global memory, bytes
   long long row_base = 0;      // first lse / delta element of this block's (head, sequence)
+#if FA_BWD_WINDOW
+  // window only (all wave-uniform): key j is visible to query i iff i + cl <= j <= i + cu; [w_lo, w_hi) = the keys this block's rows see
+  int cl = 0, cu = 0, w_lo = 0, w_hi = 0;
+#endif
   if constexpr (VARLEN) {
     // sequence b = the "batch" index. Both cu pairs are wave-uniform (scalar loads) and clamped exactly as the forward clamps them:
     // every entry to [0, total], a non-increasing pair is length 0, a length stops at max_seqlen -- whatever the tables hold, the
@@ -50,7 +56,15 @@
     kvrb = (unsigned)FA_VP.kv_rs * 2;
     // no key is visible to any row of the block (no keys at all, or causal with Lk < Lq: key j is visible to query i iff
     // j <= i + Lk - Lq): dQ = 0, and a defined delta for the dK/dV kernel, which discards it by the same integer test
+#if FA_BWD_WINDOW
+    cl = LK - LQ - p.wl;
+    cu = LK - LQ + p.wr;
+    window_key_range(LQ, LK, p.wl, p.wr, qb * BM, qb * BM + BM - 1, w_lo, w_hi);
+    // (window: the block's key range is empty -- no keys, or every row of the block in front of the first key's band)
+    if (w_lo >= w_hi) {
+#else
     if ((CAUSAL ? min(LK, qb * BM + BM + LK - LQ) : LK) <= 0) {
+#endif
       float *dqz = p.dq + base;
       for (int idx = threadIdx.x; idx < BM * (BD / 4); idx += NTHREADS) {
         const int row = qb * BM + idx / (BD / 4), c4 = idx % (BD / 4);
@@ -87,7 +101,12 @@
   // varlen under the mask, Lk < Lq: a row with no visible key carries LSE = -inf, and +inf as the start of a score chain would meet the
   // mask's -inf. Decided by the forward's integer test (the object is built without NaN handling): such a row starts from -inf like a
   // row past the end, so P = 0, dS = 0 and dQ = 0 exactly, and it adds nothing to anything.
+  // (window: the forward's test -- the row's upper bound reaches key 0; its lower bound is never past the last key)
+#if FA_BWD_WINDOW
+  const bool qlive = qvalid && LK > 0 && qrow + cu >= 0;
+#else
   const bool qlive = (VARLEN && CAUSAL) ? (qvalid && qrow + coff >= 0) : qvalid;
+#endif
   const float lse2 = qlive ? p.lse[(VARLEN ? row_base : (long long)bh * p.N) + qrow] * LOG2E : INFINITY;
   const float c2 = p.scale * LOG2E;
   // delta_i = rowsum(dO o O) (kernels.metal:983-990): this lane holds half of row i's dO (columns 16ks + 8h ..), loads the
@@ -134,7 +153,17 @@
     st_g[i] = row * BRB + ch * 16;
     st_r[i] = row * BRB + ((ch ^ u_swz(row)) << 4);
   }
+  // (window: the walk is tiles [t0, nT) of the block's key range; buffer parity and the flipped addresses follow the position in the
+  // walk -- the prologue stages tile t0 into buffer 0 -- not the tile's absolute index)
+#if FA_BWD_WINDOW
+  (void)coff;
+  const int kv_end = w_hi;
+  const int t0 = w_lo / BT;
+#define FA_T0 t0
+#else
   const int kv_end = CAUSAL ? min(FA_NK, q0 + BM + coff) : FA_NK;  // (varlen: >= 1 here)
+#define FA_T0 0
+#endif
   const int nT = (kv_end + BT - 1) / BT;
 
   constexpr bool DMA = FA_BWD_DMA != 0;
@@ -201,7 +230,7 @@
 #pragma unroll
     for (int i = 0; i < 16; ++i) dqacc[db][i] = 0.0f;
 
-  stage_load(0, 0);
+  stage_load(FA_T0, 0);
   stage_write(0);
 #pragma unroll
   for (int ks = 0; ks < BKS; ++ks)  // Q~ = round(c.Q): the very operand the forward multiplied (fa_mfma_kernel.hip)
@@ -211,17 +240,32 @@
   for (int ks = 0; ks < BKS; ++ks) asm volatile("" : "+v"(qf[ks]), "+v"(dof[ks]));  // retire the prologue loads
   __syncthreads();
 
+#if FA_BWD_WINDOW
+  for (int t = t0; t < nT; ++t) {
+    const int buf = (t - t0) & 1;
+#else
   for (int t = 0; t < nT; ++t) {
     const int buf = t & 1;
+#endif
     if (t + 1 < nT) stage_load(t + 1, buf ^ 1);
 #pragma unroll
     for (int sub = 0; sub < BSUB; ++sub) {
     const int kv0 = t * BT + sub * BN;
+    // (window: a wave skips a sub-tile wholly outside its own 32 rows' bounds, above or below)
+#if FA_BWD_WINDOW
+    if (kv0 < kv_end && kv0 <= qw0 + WM - 1 + cu && kv0 + BN - 1 >= qw0 + cl) {
+#else
     if (kv0 < kv_end && (!CAUSAL || kv0 <= qw0 + WM - 1 + coff)) {
+#endif
       const int KS = sub * BTILE, VS = 2 * STILE + sub * BTILE;  // K / V sub-tile images, relative to koff / voff
       // masked: key > query (causal), and -- the partial last tile -- key >= Nk: those K / V rows arrive as zeros through the
       // descriptor, S' = -lse.log2e there, and with a strongly negative lse P = exp2(S') overflows the cast of dS (inf x 0 = NaN in dQ)
+      // (window: two-sided, on sub-tiles that either edge of some row of the wave or the end of the keys crosses)
+#if FA_BWD_WINDOW
+      const bool need_mask = (kv0 + BN - 1 > qw0 + cu) || (kv0 < qw0 + WM - 1 + cl) || (kv0 + BN > FA_NK);
+#else
       const bool need_mask = (CAUSAL && (kv0 + BN - 1 > qw0 + coff)) || (kv0 + BN > FA_NK);
+#endif
       // One 32-key half (kb) at a time -- scores, dS, then its share of dQ -- so that only one score and one dP tuple are live
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
@@ -261,9 +305,16 @@
         __builtin_amdgcn_s_setprio(0);
         if (need_mask) {  // key > query -> masked (kernels.metal:748); a wave-uniform branch
           int lim = FA_NK - 1 - kv0 - 32 * kb - 4 * h;
+#if FA_BWD_WINDOW
+          lim = min(lim, qrow + cu - kv0 - 32 * kb - 4 * h);
+          const int lim_lo = qrow + cl - kv0 - 32 * kb - 4 * h;  // key < query + cl -> masked
+#pragma unroll
+          for (int i = 0; i < 16; ++i) sk[i] = ((i & 3) + 8 * (i >> 2) > lim || (i & 3) + 8 * (i >> 2) < lim_lo) ? -INFINITY : sk[i];
+#else
           if (CAUSAL) lim = min(lim, qrow + coff - kv0 - 32 * kb - 4 * h);
 #pragma unroll
           for (int i = 0; i < 16; ++i) sk[i] = ((i & 3) + 8 * (i >> 2) > lim) ? -INFINITY : sk[i];
+#endif
         }
         // dS^T = P^T o (dP^T - delta) (the softmax scale goes onto the finished dQ): keys in the registers, the query on the lane
 #pragma unroll
@@ -316,3 +367,4 @@
 #undef FA_NQ
 #undef FA_NK
 #undef FA_VP
+#undef FA_T0

@@ -81,6 +81,20 @@ __host__ __device__ inline void window_key_range(int Lq, int Lk, int wl, int wr,
   hi = (int)(b < 0 ? 0 : b > Lk ? Lk : b);
 }
 
+// The inverse: the half-open query range [lo, hi) of the rows that see at least one of the keys key_first .. key_last (clamped to the
+// sequence's keys) -- key j is seen by rows j - coff - wr <= i <= j - coff + wl, 0 <= i < Lq; empty iff lo >= hi. 64-bit arithmetic:
+// any int is a legal argument. fa_window_query_range is this function; the windowed dK/dV kernel takes its first and last query tile
+// from it.
+__host__ __device__ inline void window_query_range(int Lq, int Lk, int wl, int wr, int key_first, int key_last, int &lo, int &hi) {
+  const long long coff = (long long)Lk - Lq;
+  const long long k0 = key_first > 0 ? key_first : 0, k1 = key_last < Lk - 1 ? key_last : (long long)Lk - 1;
+  lo = hi = 0;
+  if (k0 > k1 || Lq <= 0) return;
+  const long long a = wr < 0 ? 0 : k0 - coff - wr, b = wl < 0 ? (long long)Lq : k1 - coff + wl + 1;
+  lo = (int)(a < 0 ? 0 : a > Lq ? Lq : a);
+  hi = (int)(b < 0 ? 0 : b > Lq ? Lq : b);
+}
+
 // the windowed modes of csrc/fa_mfma_kernel.hip (fa_fwd_varlen_window, fa_fwd_varlen_paged_window): the un-windowed call's parameters
 // plus both bounds, which the host has made non-negative (an unbounded or oversized side is the smallest value that can never bind: wl
 // <= max keys, wr <= max_seqlen_q -- so that coff - wl and row + coff + wr stay inside an int)
@@ -185,6 +199,11 @@ hipError_t launch_bwd_varlen(const void *q, const void *k, const void *v, const 
                              float *dk, float *dv, float *ws, const int *cu_q, const int *cu_k, int B, int H, int Hkv, int total_q,
                              int total_k, int max_q, int max_k, int D, float scale, long long q_rs, long long q_hs, long long kv_rs,
                              long long kv_hs, int causal, int dtype, hipStream_t s);
+// fa_bwd_varlen_window (csrc/fa_bwd_window_kernels.hip): the same under a window whose bounds the caller has made non-negative
+hipError_t launch_bwd_varlen_window(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq,
+                                    float *dk, float *dv, float *ws, const int *cu_q, const int *cu_k, int B, int H, int Hkv, int total_q,
+                                    int total_k, int max_q, int max_k, int D, float scale, long long q_rs, long long q_hs, long long kv_rs,
+                                    long long kv_hs, int wl, int wr, int dtype, hipStream_t s);
 
 // ---- host-side launch helper shared by every kernel file that needs more than 48 KiB of dynamic LDS
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device) instead of on every launch.

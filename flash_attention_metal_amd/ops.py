@@ -530,6 +530,7 @@ def flash_attention_varlen_backward(
     dv: Optional[torch.Tensor] = None,
     workspace: Optional[torch.Tensor] = None,
     stream: Optional[int] = None,
+    window: Optional[Tuple[int, int]] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The backward over packed variable-length sequences (include/fa_mi355.h fa_bwd_varlen), the counterpart of
     flash_attention_varlen: q, o, d_o [total_q, Hq, D] under one set of strides, k, v [total_k, Hkv, D] under another, f16 / bf16,
@@ -538,7 +539,10 @@ def flash_attention_varlen_backward(
     projection). Only tokens owned by a sequence are written (allocate with zeros if the rest is read); a query row without a visible
     key gets dQ = 0 and adds nothing to dK / dV. With dq, dk, dv and `workspace` (uint8, at least
     varlen_backward_workspace_bytes(Hq, total_q) bytes) given the call allocates nothing, and it never synchronises or reads a device
-    value: it can be captured in a graph and replayed after the tables change in place."""
+    value: it can be captured in a graph and replayed after the tables change in place.
+    window=(left, right): the backward of flash_attention_varlen(window=...) (fa_bwd_varlen_window: key j visible to query i iff
+    i + Lk_b - Lq_b - left <= j <= i + Lk_b - Lq_b + right, a negative side unbounded; with is_causal the right side is 0); a key no
+    query sees gets dK = dV = 0. None: the call above, untouched."""
     lib = load_library()
     if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or o.shape != q.shape or d_o.shape != q.shape:
         raise ValueError(f"q, o, d_o one [total_q,Hq,D] shape and k, v one [total_k,Hkv,D] shape, got {tuple(q.shape)} {tuple(o.shape)} "
@@ -578,11 +582,12 @@ def flash_attention_varlen_backward(
     ws = _workspace(workspace, need, q.device)
     if ws.numel() < need:
         raise ValueError(f"workspace of {ws.numel()} bytes, varlen_backward_workspace_bytes() asks for {need}")
-    _call(lib, "fa_bwd_varlen",
+    mask = (int(bool(is_causal)),) if window is None else _window(window, is_causal)
+    _call(lib, "fa_bwd_varlen" if window is None else "fa_bwd_varlen_window",
           (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
            dv.data_ptr(), ws.data_ptr(), cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), B, Hq, Hkv, total_q, total_k,
            int(max_seqlen_q), int(max_seqlen_k), D, _scale(scale, D), q.stride(0), q.stride(1), k.stride(0), k.stride(1),
-           int(bool(is_causal)), _TORCH2FA[q.dtype]), q.device, stream)
+           *mask, _TORCH2FA[q.dtype]), q.device, stream)
     return dq, dk, dv
 
 

@@ -17,6 +17,12 @@ raise instead of returning a silent zero gradient; so does a gradient flowing in
 The same over packed variable-length sequences (fa_fwd_varlen / fa_bwd_varlen): q [total_q, Hq, D], k / v [total_k, Hkv, D], lse
 [Hq, total_q]. Its backward writes into zero-initialised fp32 buffers, so tokens that belong to no sequence get a zero gradient, and
 returns the gradients in the input dtype.
+
+    torch.ops.fa_mi355.attention_varlen_window(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window_left, window_right,
+                                               scale) -> (o, lse)
+
+attention_varlen under a sliding window (fa_fwd_varlen_window / fa_bwd_varlen_window; a negative side is unbounded), differentiable in the
+same way. attention_varlen(..., window=(left, right)) dispatches to it.
 """
 from __future__ import annotations
 
@@ -24,7 +30,7 @@ from typing import Tuple
 
 import torch
 
-from .ops import (_TORCH2FA, FaError, _out_dtype, flash_attention_backward, flash_attention_forward, flash_attention_varlen,
+from .ops import (_TORCH2FA, FaError, _out_dtype, _window, flash_attention_backward, flash_attention_forward, flash_attention_varlen,
                   flash_attention_varlen_backward, load_library)
 
 _LIB = torch.library.Library("fa_mi355", "DEF")
@@ -133,5 +139,64 @@ def _varlen_backward(ctx, grad_o, grad_lse):
 torch.library.register_autograd("fa_mi355::attention_varlen", _varlen_backward, setup_context=_varlen_setup_context, lib=_LIB)
 
 
-def attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_seqlen_k: int, is_causal: bool = False, scale: float = 0.0):
-    return torch.ops.fa_mi355.attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, scale)
+_LIB.define("attention_varlen_window(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor cu_seqlens_k, int max_seqlen_q, "
+            "int max_seqlen_k, int window_left, int window_right, float scale=0.0) -> (Tensor, Tensor)")
+
+
+def _varlen_window_impl(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window_left, window_right, scale=0.0):
+    out = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device).zero_()
+    lse = torch.full((q.shape[1], q.shape[0]), float("-inf"), dtype=torch.float32, device=q.device)
+    return flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale=(scale if scale > 0 else None),
+                                  out=out, lse=lse, window=(window_left, window_right))
+
+
+def _varlen_window_meta(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window_left, window_right, scale=0.0):
+    return torch.empty_like(q), q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32)
+
+
+_LIB.impl("attention_varlen_window", _varlen_window_impl, "CUDA")
+_LIB.impl("attention_varlen_window", _varlen_window_meta, "Meta")
+
+
+def _varlen_window_setup_context(ctx, inputs, output):
+    q, k, v, cu_q, cu_k, max_q, max_k, window_left, window_right, scale = inputs
+    o, lse = output
+    ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k)
+    ctx.max_q, ctx.max_k, ctx.window, ctx.scale = int(max_q), int(max_k), (int(window_left), int(window_right)), float(scale)
+    ctx.set_materialize_grads(False)
+
+
+def _varlen_window_backward(ctx, grad_o, grad_lse):
+    q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
+    if grad_lse is not None:
+        raise NotImplementedError("fa_mi355::attention_varlen_window: no gradient through the LSE output")
+    none = (None,) * 10
+    if grad_o is None:
+        return none
+    if q.dtype not in _TORCH2FA or not load_library().fa_bwd_varlen_supported(_TORCH2FA[q.dtype], q.shape[2]):
+        raise FaError(-2, f"no varlen backward kernel for q {tuple(q.shape)} {q.dtype} (f16 / bf16, head_dim 64 or 128)", "fa_bwd_varlen_window")
+    go = grad_o.to(o.dtype)
+    if go.stride() != q.stride():  # d_o is addressed under q's strides
+        go = torch.empty_strided(q.shape, q.stride(), dtype=o.dtype, device=q.device).copy_(go)
+    if o.stride() != q.stride():
+        o = torch.empty_strided(q.shape, q.stride(), dtype=o.dtype, device=q.device).copy_(o)
+    # zero-initialised: tokens owned by no sequence are not written by the kernels and get a zero gradient
+    dq = torch.empty_strided(q.shape, q.stride(), dtype=torch.float32, device=q.device).zero_()
+    dk = torch.empty_strided(k.shape, k.stride(), dtype=torch.float32, device=q.device).zero_()
+    dv = torch.empty_strided(k.shape, k.stride(), dtype=torch.float32, device=q.device).zero_()
+    flash_attention_varlen_backward(q, k, v, o, go, lse, cu_q, cu_k, ctx.max_q, ctx.max_k, scale=(ctx.scale if ctx.scale > 0 else None),
+                                    dq=dq, dk=dk, dv=dv, window=ctx.window)
+    return (dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)) + none[3:]
+
+
+torch.library.register_autograd("fa_mi355::attention_varlen_window", _varlen_window_backward, setup_context=_varlen_window_setup_context,
+                                lib=_LIB)
+
+
+def attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_seqlen_k: int, is_causal: bool = False, scale: float = 0.0,
+                     window=None):
+    """window=(left, right): fa_mi355::attention_varlen_window (differentiable through fa_bwd_varlen_window); None: the op above."""
+    if window is None:
+        return torch.ops.fa_mi355.attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, scale)
+    left, right = _window(window, is_causal)
+    return torch.ops.fa_mi355.attention_varlen_window(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, left, right, scale)

@@ -469,6 +469,34 @@ int fa_bwd_varlen(const void *q, const void *k, const void *v, const void *o, co
 long long fa_bwd_varlen_workspace_bytes(int Hq, int total_q);
 int fa_bwd_varlen_supported(int dtype, int D);
 
+/*
+ * The backward of fa_fwd_varlen_window: fa_bwd_varlen with is_causal replaced by (window_left, window_right); the visibility rule is that
+ * of "Sliding window" above (key j visible to query i iff i + coff - window_left <= j <= i + coff + window_right and 0 <= j < Lk_b,
+ * coff = Lk_b - Lq_b, a negative side unbounded). Every argument rule, status and the workspace (fa_bwd_varlen_workspace_bytes,
+ * fa_bwd_varlen_supported) are fa_bwd_varlen's. Routing is by sign only: (< 0, < 0) and (< 0, 0) launch fa_bwd_varlen's kernels without
+ * and with the mask and are bit-identical to it; every other pair launches the windowed kernels, an unbounded or oversized side clamped
+ * to max_seqlen_k (left) / max_seqlen_q (right), which can never bind.
+ * What is written: as fa_bwd_varlen -- the dQ row of every owned query token and the dK and dV rows of every owned key token; a key no
+ * query sees gets dK = dV = 0. Dead rows: a query row without a visible key (Lk_b = 0 or i + coff + window_right < 0, the forward's
+ * integer test; O = 0 and LSE = -inf there) gets dQ = 0 exactly and contributes exactly nothing to dK / dV; its delta is still written.
+ * Through the windowed kernels (INT_MAX, 0) is bit-identical to the causal call and (INT_MAX, INT_MAX) to the full call on every
+ * sequence with Lk_b >= Lq_b >= 1. "Backward accuracy" above applies per sequence under the window's visibility.
+ * Inputs must be finite: the mask discards a hidden score, not its operands -- a NaN in a key that no query sees still reaches that
+ * key's own dK / dV.
+ * The dQ kernel walks the key tiles [lo / 64, ceil(hi / 64)) of fa_window_key_range of each 128-row block; the dK/dV kernel the query
+ * tiles [lo / 64, ceil(hi / 64)) of fa_window_query_range of each 128-key block, for every query head of the group.
+ */
+int fa_bwd_varlen_window(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse,
+                         float *dq, float *dk, float *dv, void *workspace,
+                         const int *cu_seqlens_q, const int *cu_seqlens_k,
+                         int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
+                         long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
+                         int window_left, int window_right, int dtype, void *hip_stream);
+/* The inverse of fa_window_key_range (host only, any int is legal, 64-bit arithmetic): the half-open range [*row_lo, *row_hi) of the
+ * query rows that see at least one of the keys key_first .. key_last (clamped to the sequence's keys); empty iff *row_lo >= *row_hi.
+ * FA_ERR_INVALID_ARG for a null pointer or a negative length. */
+int fa_window_query_range(int Lq, int Lk, int window_left, int window_right, int key_first, int key_last, int *row_lo, int *row_hi);
+
 /* 1 if fa_fwd has a kernel for the combination, else 0 (no GPU needed). */
 int fa_supported(int dtype, int variant, int D);
 
