@@ -35,6 +35,7 @@ int fail(int code, const char *fmt, ...) {
 //    B * Hkv * ceil(max_seqlen_k / 128));
 //  - fa_fwd_varlen_paged: fa_fwd_varlen's rules for q and the grid, page_pool_ok for the pools and tables (the paged decode's rules);
 //    fa_kv_append_paged: varlen_strides_ok for the new rows, page_pool_ok, and a grid of B * ceil(max_seqlen_new / 16) x Hkv;
+//  - the four *_sink entry points: the impl function, and with it every rule, of their *_window call, plus sinks_ok (and dsinks' alignment);
 //  - a missing device: FA_ERR_NO_DEVICE from fa_fwd, FA_ERR_LAUNCH from every other entry point.
 #define TRY(check) do { if (const int st_ = (check)) return st_; } while (0)
 
@@ -131,6 +132,11 @@ int window_route(int wl, int wr) { return wl < 0 && wr < 0 ? WIN_FULL : wl < 0 &
 // cannot bind (wl: the most keys a sequence of the call can hold; wr: the most query rows), so that the kernels' 32-bit coff - wl and
 // row + coff + wr cannot wrap
 int window_clamp(int w, int never) { return w < 0 || w > never ? never : w; }
+// the *_sink entry points: one fp32 logit per query head in device memory, read by the kernels only
+int sinks_ok(const char *fn, const float *sinks) {
+  if (!sinks) return fail(FA_ERR_INVALID_ARG, "%s: null pointer", fn);
+  return (uintptr_t)sinks & 3 ? fail(FA_ERR_INVALID_ARG, "%s: sinks must be fp32-aligned", fn) : FA_OK;
+}
 int launched(const char *fn, hipError_t e) {
   return e == hipSuccess ? FA_OK : fail(FA_ERR_LAUNCH, "%s: launch failed: %s", fn, hipGetErrorString(e));
 }
@@ -400,13 +406,16 @@ int fa_fwd_exv(const void *q, const void *k, const void *v, void *o, float *lse,
 }
 
 int fa_fwd_varlen_supported(int dtype, int D) { return fa::mfma_varlen_supported(dtype, D); }
-// fa_fwd_varlen (window_left = -1, window_right = is_causal ? 0 : -1) and fa_fwd_varlen_window: one set of rules, one launch path
+// fa_fwd_varlen (window_left = -1, window_right = is_causal ? 0 : -1), fa_fwd_varlen_window and fa_fwd_varlen_sink (`sinks`: its own
+// argument; null for the other two): one set of rules, one launch path. With sinks the call always runs the windowed kernels in their
+// sink mode, an unbounded side clamped to the never-binding width.
 static int varlen_impl(const char *fn, const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q,
                        const int *cu_seqlens_k, int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D,
                        float scale, long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
-                       int window_left, int window_right, int dtype, void *hip_stream) {
+                       int window_left, int window_right, int dtype, void *hip_stream, const float *const *sinks = nullptr) {
   g_err[0] = 0;
   TRY(nonnull(fn, {q, k, v, o, cu_seqlens_q, cu_seqlens_k}));
+  if (sinks) TRY(sinks_ok(fn, *sinks));
   TRY(positive(fn, {B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
@@ -425,8 +434,8 @@ static int varlen_impl(const char *fn, const void *q, const void *k, const void 
   TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
   TRY(head_fits(fn, (double)(max_seqlen_k + 128) * (double)kv_row_stride * 2, 4, " (one sequence of max_seqlen_k rows)"));
   TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));
-  const int route = window_route(window_left, window_right);
-  fa::VarlenWindowParams p;
+  const int route = sinks ? WIN_KERNEL : window_route(window_left, window_right);
+  fa::VarlenSinkParams p;
   p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
   p.B = B; p.H = Hq; p.Hkv = Hkv; p.N = max_seqlen_q; p.Nk = max_seqlen_k; p.D = D; p.scale = scale;
   p.batch_stride = 0; p.head_stride = q_head_stride; p.kv_batch_stride = 0; p.kv_head_stride = kv_head_stride;
@@ -437,7 +446,9 @@ static int varlen_impl(const char *fn, const void *q, const void *k, const void 
   if (route != WIN_KERNEL) return launched(fn, fa::launch_mfma_varlen(p, dtype, (hipStream_t)hip_stream));
   p.wl = window_clamp(window_left, max_seqlen_k);
   p.wr = window_clamp(window_right, max_seqlen_q);
-  return launched(fn, fa::launch_mfma_varlen_window(p, dtype, (hipStream_t)hip_stream));
+  if (!sinks) return launched(fn, fa::launch_mfma_varlen_window(p, dtype, (hipStream_t)hip_stream));
+  p.sinks = *sinks;
+  return launched(fn, fa::launch_mfma_varlen_sink(p, dtype, (hipStream_t)hip_stream));
 }
 int fa_fwd_varlen(const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q, const int *cu_seqlens_k,
                   int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
@@ -453,6 +464,14 @@ int fa_fwd_varlen_window(const void *q, const void *k, const void *v, void *o, f
   return varlen_impl("fa_fwd_varlen_window", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q, total_k, max_seqlen_q,
                      max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride, window_left, window_right, dtype,
                      hip_stream);
+}
+int fa_fwd_varlen_sink(const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q, const int *cu_seqlens_k,
+                       int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
+                       long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
+                       int window_left, int window_right, const float *sinks, int dtype, void *hip_stream) {
+  return varlen_impl("fa_fwd_varlen_sink", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q, total_k, max_seqlen_q,
+                     max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride, window_left, window_right, dtype,
+                     hip_stream, &sinks);
 }
 int fa_window_key_range(int Lq, int Lk, int window_left, int window_right, int row_first, int row_last, int *key_lo, int *key_hi) {
   g_err[0] = 0;
@@ -534,9 +553,11 @@ static int decode_paged_impl(const char *fn, const void *q, const void *k_pages,
                              const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages,
                              int max_pages_per_seq, float scale, long long q_batch_stride, long long q_head_stride, long long kv_page_stride,
                              long long kv_head_stride, long long kv_row_stride, long long block_table_stride, int window_left,
-                             int window_right, int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes, void *hip_stream) {
+                             int window_right, int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes, void *hip_stream,
+                             const float *const *sinks = nullptr) {
   g_err[0] = 0;
   TRY(nonnull(fn, {q, k_pages, v_pages, o, block_table, seqlens_k, workspace}));
+  if (sinks) TRY(sinks_ok(fn, *sinks));
   TRY(positive(fn, {B, Hq, Hkv, Nq, D, page_size, num_pages, max_pages_per_seq}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
@@ -552,7 +573,7 @@ static int decode_paged_impl(const char *fn, const void *q, const void *k_pages,
   TRY(page_tables_ok(fn, page_size, max_pages_per_seq, block_table, seqlens_k));
   const int cap = page_size * max_pages_per_seq;
   TRY(workspace_fits(fn, workspace_bytes, fa::decode_workspace_bytes(B, Hq, Hkv, Nq, cap, D), "fa_fwd_decode_paged_workspace_bytes"));
-  const int route = window_route(window_left, window_right);
+  const int route = sinks ? WIN_KERNEL : window_route(window_left, window_right);
   fa::DecodeWindowParams p;
   // Nk = the capacity, hence the dense decode's split rule there: bit-identical to it on full caches
   TRY(decode_params(fn, p, q, k_pages, v_pages, o, lse, workspace, B, Hq, Hkv, Nq, cap, D, scale, q_batch_stride, q_head_stride, route != WIN_FULL, kv8));
@@ -564,7 +585,8 @@ static int decode_paged_impl(const char *fn, const void *q, const void *k_pages,
   if (route != WIN_KERNEL) return launched(fn, fa::launch_decode_paged(p, D, q_dtype, kv8, (hipStream_t)hip_stream));
   p.wl = window_clamp(window_left, cap);
   p.wr = window_clamp(window_right, Nq);
-  return launched(fn, fa::launch_decode_paged_window(p, D, q_dtype, kv8, (hipStream_t)hip_stream));
+  if (!sinks) return launched(fn, fa::launch_decode_paged_window(p, D, q_dtype, kv8, (hipStream_t)hip_stream));
+  return launched(fn, fa::launch_decode_paged_sink(p, *sinks, D, q_dtype, kv8, (hipStream_t)hip_stream));
 }
 int fa_fwd_decode_paged(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *block_table,
                         const int *seqlens_k, int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages, int max_pages_per_seq,
@@ -584,15 +606,27 @@ int fa_fwd_decode_paged_window(const void *q, const void *k_pages, const void *v
                            num_pages, max_pages_per_seq, scale, q_batch_stride, q_head_stride, kv_page_stride, kv_head_stride, kv_row_stride,
                            block_table_stride, window_left, window_right, q_dtype, kv_dtype, workspace, workspace_bytes, hip_stream);
 }
+int fa_fwd_decode_paged_sink(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *block_table,
+                             const int *seqlens_k, int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages,
+                             int max_pages_per_seq, float scale, long long q_batch_stride, long long q_head_stride, long long kv_page_stride,
+                             long long kv_head_stride, long long kv_row_stride, long long block_table_stride, int window_left,
+                             int window_right, const float *sinks, int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes,
+                             void *hip_stream) {
+  return decode_paged_impl("fa_fwd_decode_paged_sink", q, k_pages, v_pages, o, lse, block_table, seqlens_k, B, Hq, Hkv, Nq, D, page_size,
+                           num_pages, max_pages_per_seq, scale, q_batch_stride, q_head_stride, kv_page_stride, kv_head_stride, kv_row_stride,
+                           block_table_stride, window_left, window_right, q_dtype, kv_dtype, workspace, workspace_bytes, hip_stream, &sinks);
+}
 
 int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size) { return fa::mfma_varlen_paged_supported(dtype, D, page_size); }
 static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
                              const int *cu_seqlens_q, const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q,
                              int max_seqlen_q, int D, int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride,
                              long long q_head_stride, long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
-                             long long block_table_stride, int window_left, int window_right, int dtype, void *hip_stream) {
+                             long long block_table_stride, int window_left, int window_right, int dtype, void *hip_stream,
+                             const float *const *sinks = nullptr) {
   g_err[0] = 0;
   TRY(nonnull(fn, {q, k_pages, v_pages, o, cu_seqlens_q, block_table, seqlens_k}));
+  if (sinks) TRY(sinks_ok(fn, *sinks));
   TRY(positive(fn, {B, Hq, Hkv, total_q, max_seqlen_q, D, page_size, num_pages, max_pages_per_seq}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
@@ -607,8 +641,8 @@ static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages,
   if ((uintptr_t)cu_seqlens_q & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q must be int32-aligned", fn);
   TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
   TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));
-  const int route = window_route(window_left, window_right);
-  fa::VarlenPagedWindowParams p;
+  const int route = sinks ? WIN_KERNEL : window_route(window_left, window_right);
+  fa::VarlenPagedSinkParams p;
   p.q = q; p.k = k_pages; p.v = v_pages; p.o = o; p.lse = lse;
   p.B = B; p.H = Hq; p.Hkv = Hkv; p.N = max_seqlen_q; p.Nk = page_size * max_pages_per_seq; p.D = D; p.scale = scale;
   p.batch_stride = 0; p.head_stride = q_head_stride; p.kv_batch_stride = 0; p.kv_head_stride = kv_head_stride;
@@ -623,7 +657,9 @@ static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages,
   if (route != WIN_KERNEL) return launched(fn, fa::launch_mfma_varlen_paged(p, dtype, (hipStream_t)hip_stream));
   p.wl = window_clamp(window_left, p.Nk);
   p.wr = window_clamp(window_right, max_seqlen_q);
-  return launched(fn, fa::launch_mfma_varlen_paged_window(p, dtype, (hipStream_t)hip_stream));
+  if (!sinks) return launched(fn, fa::launch_mfma_varlen_paged_window(p, dtype, (hipStream_t)hip_stream));
+  p.sinks = *sinks;
+  return launched(fn, fa::launch_mfma_varlen_paged_sink(p, dtype, (hipStream_t)hip_stream));
 }
 int fa_fwd_varlen_paged(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *cu_seqlens_q,
                         const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
@@ -642,6 +678,16 @@ int fa_fwd_varlen_paged_window(const void *q, const void *k_pages, const void *v
   return varlen_paged_impl("fa_fwd_varlen_paged_window", q, k_pages, v_pages, o, lse, cu_seqlens_q, block_table, seqlens_k, B, Hq, Hkv, total_q,
                            max_seqlen_q, D, page_size, num_pages, max_pages_per_seq, scale, q_row_stride, q_head_stride, kv_page_stride,
                            kv_head_stride, kv_row_stride, block_table_stride, window_left, window_right, dtype, hip_stream);
+}
+int fa_fwd_varlen_paged_sink(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *cu_seqlens_q,
+                             const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                             int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride,
+                             long long q_head_stride, long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                             long long block_table_stride, int window_left, int window_right, const float *sinks, int dtype,
+                             void *hip_stream) {
+  return varlen_paged_impl("fa_fwd_varlen_paged_sink", q, k_pages, v_pages, o, lse, cu_seqlens_q, block_table, seqlens_k, B, Hq, Hkv, total_q,
+                           max_seqlen_q, D, page_size, num_pages, max_pages_per_seq, scale, q_row_stride, q_head_stride, kv_page_stride,
+                           kv_head_stride, kv_row_stride, block_table_stride, window_left, window_right, dtype, hip_stream, &sinks);
 }
 
 int fa_kv_append_paged(const void *k_new, const void *v_new, void *k_pages, void *v_pages, const int *cu_seqlens_new, const int *block_table,
@@ -750,14 +796,20 @@ int fa_bwd_ex(const void *q, const void *k, const void *v, const void *o, const 
 
 long long fa_bwd_varlen_workspace_bytes(int Hq, int total_q) { return Hq < 1 || total_q < 1 ? 0 : (long long)Hq * total_q * 4; }
 int fa_bwd_varlen_supported(int dtype, int D) { return fa::bwd_varlen_supported(dtype, D); }
-// fa_bwd_varlen (window_left = -1, window_right = is_causal ? 0 : -1) and fa_bwd_varlen_window: one set of rules, one launch path
+// fa_bwd_varlen (window_left = -1, window_right = is_causal ? 0 : -1), fa_bwd_varlen_window and fa_bwd_varlen_sink (`sinks`: its own
+// argument, null for the other two; dsinks may be null): one set of rules, one launch path. The sinks need nothing of the dQ and dK/dV
+// kernels -- the forward's LSE contains them -- so those launch exactly as for fa_bwd_varlen_window; the dsink reduction follows them.
 static int bwd_varlen_impl(const char *fn, const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse,
                            float *dq, float *dk, float *dv, void *workspace, const int *cu_seqlens_q, const int *cu_seqlens_k, int B, int Hq,
                            int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale, long long q_row_stride,
                            long long q_head_stride, long long kv_row_stride, long long kv_head_stride, int window_left, int window_right,
-                           int dtype, void *hip_stream) {
+                           int dtype, void *hip_stream, const float *const *sinks = nullptr, float *dsinks = nullptr) {
   g_err[0] = 0;
   TRY(nonnull(fn, {q, k, v, o, d_o, lse, dq, dk, dv, workspace, cu_seqlens_q, cu_seqlens_k}));
+  if (sinks) {
+    TRY(sinks_ok(fn, *sinks));
+    if ((uintptr_t)dsinks & 3) return fail(FA_ERR_INVALID_ARG, "%s: dsinks must be fp32-aligned", fn);
+  }
   TRY(positive(fn, {B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
@@ -777,14 +829,19 @@ static int bwd_varlen_impl(const char *fn, const void *q, const void *k, const v
   TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));   // the dQ kernel's
   TRY(grid_fits(fn, (long long)B * Hkv, max_seqlen_k));  // the dK/dV kernel's
   const int route = window_route(window_left, window_right);
+  hipError_t e;
   if (route != WIN_KERNEL)
-    return launched(fn, fa::launch_bwd_varlen(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv,
-                                              total_q, total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride,
-                                              kv_row_stride, kv_head_stride, route == WIN_CAUSAL ? 1 : 0, dtype, (hipStream_t)hip_stream));
-  return launched(fn, fa::launch_bwd_varlen_window(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, cu_seqlens_q, cu_seqlens_k, B, Hq,
-                                                   Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride,
-                                                   kv_row_stride, kv_head_stride, window_clamp(window_left, max_seqlen_k),
-                                                   window_clamp(window_right, max_seqlen_q), dtype, (hipStream_t)hip_stream));
+    e = fa::launch_bwd_varlen(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q, total_k,
+                              max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride,
+                              route == WIN_CAUSAL ? 1 : 0, dtype, (hipStream_t)hip_stream);
+  else
+    e = fa::launch_bwd_varlen_window(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q,
+                                     total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride,
+                                     kv_head_stride, window_clamp(window_left, max_seqlen_k), window_clamp(window_right, max_seqlen_q),
+                                     dtype, (hipStream_t)hip_stream);
+  if (e == hipSuccess && sinks && dsinks)
+    e = fa::launch_dsink(*sinks, lse, (const float *)workspace, dsinks, cu_seqlens_q, B, Hq, total_q, max_seqlen_q, (hipStream_t)hip_stream);
+  return launched(fn, e);
 }
 int fa_bwd_varlen(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq, float *dk,
                   float *dv, void *workspace, const int *cu_seqlens_q, const int *cu_seqlens_k, int B, int Hq, int Hkv, int total_q,
@@ -802,6 +859,15 @@ int fa_bwd_varlen_window(const void *q, const void *k, const void *v, const void
   return bwd_varlen_impl("fa_bwd_varlen_window", q, k, v, o, d_o, lse, dq, dk, dv, workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q,
                          total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride,
                          window_left, window_right, dtype, hip_stream);
+}
+int fa_bwd_varlen_sink(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq, float *dk,
+                       float *dv, void *workspace, const int *cu_seqlens_q, const int *cu_seqlens_k, int B, int Hq, int Hkv, int total_q,
+                       int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale, long long q_row_stride, long long q_head_stride,
+                       long long kv_row_stride, long long kv_head_stride, int window_left, int window_right, const float *sinks,
+                       float *dsinks, int dtype, void *hip_stream) {
+  return bwd_varlen_impl("fa_bwd_varlen_sink", q, k, v, o, d_o, lse, dq, dk, dv, workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q,
+                         total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride,
+                         window_left, window_right, dtype, hip_stream, &sinks, dsinks);
 }
 int fa_window_query_range(int Lq, int Lk, int window_left, int window_right, int key_first, int key_last, int *row_lo, int *row_hi) {
   g_err[0] = 0;

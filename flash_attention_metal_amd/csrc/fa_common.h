@@ -105,6 +105,16 @@ struct VarlenPagedWindowParams : VarlenPagedParams {
   int wl, wr;
 };
 
+// the sink modes of the windowed modes (fa_fwd_varlen_sink, fa_fwd_varlen_paged_sink; include/fa_mi355.h, "Attention sinks"): the windowed
+// call's parameters plus one fp32 logit per QUERY head (natural-log units, the softmax scale is not applied to it), device memory read
+// by the kernels only. It enters the row's denominator once, in the epilogue.
+struct VarlenSinkParams : VarlenWindowParams {
+  const float *sinks;  // [H]
+};
+struct VarlenPagedSinkParams : VarlenPagedWindowParams {
+  const float *sinks;  // [H]
+};
+
 // one fa_fwd_decode call (csrc/fa_decode_kernel.hip)
 struct DecodeParams {
   const void *q, *k, *v;
@@ -134,6 +144,12 @@ struct DecodeWindowParams : DecodePagedParams {
   int wl, wr;
 };
 
+// the combine step of fa_fwd_decode_paged_sink: what the combine kernel reads of a decode call, plus the sinks ([Hq] fp32, natural-log
+// units). The partial kernels of the windowed call run unchanged; the sink is folded once per row behind the splits' reduction.
+struct CombineSinkParams : DecodeParams {
+  const float *sinks;
+};
+
 // dtype tags
 struct F32 {};
 struct F16 {};
@@ -153,6 +169,8 @@ bool mfma_varlen_paged_supported(int dtype, int D, int page_size);
 inline bool page_size_ok(int page_size) { return page_size >= 16 && page_size <= 256 && (page_size & (page_size - 1)) == 0; }
 hipError_t launch_mfma_varlen_window(const VarlenWindowParams &p, int dtype, hipStream_t s);
 hipError_t launch_mfma_varlen_paged_window(const VarlenPagedWindowParams &p, int dtype, hipStream_t s);
+hipError_t launch_mfma_varlen_sink(const VarlenSinkParams &p, int dtype, hipStream_t s);
+hipError_t launch_mfma_varlen_paged_sink(const VarlenPagedSinkParams &p, int dtype, hipStream_t s);
 // fa_kv_append_paged (csrc/fa_decode_kernel.hip): a byte copy of new K / V rows into their slots of the page pools
 struct AppendPagedParams {
   const void *k_new, *v_new;
@@ -182,6 +200,8 @@ int decode_splits(int B, int Hkv, int Nk, int D, int kv8);  // kv8: e4m3 inputs 
 long long decode_workspace_bytes(int B, int Hq, int Hkv, int Nq, int Nk, int D);
 hipError_t launch_decode_paged(const DecodePagedParams &p, int D, int dtype, int kv8, hipStream_t s);
 hipError_t launch_decode_paged_window(const DecodeWindowParams &p, int D, int dtype, int kv8, hipStream_t s);
+// fa_fwd_decode_paged_sink: the windowed partial kernels, then the combine kernel that folds sinks[hq] into every row
+hipError_t launch_decode_paged_sink(const DecodeWindowParams &p, const float *sinks, int D, int dtype, int kv8, hipStream_t s);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);
@@ -204,6 +224,10 @@ hipError_t launch_bwd_varlen_window(const void *q, const void *k, const void *v,
                                     float *dk, float *dv, float *ws, const int *cu_q, const int *cu_k, int B, int H, int Hkv, int total_q,
                                     int total_k, int max_q, int max_k, int D, float scale, long long q_rs, long long q_hs, long long kv_rs,
                                     long long kv_hs, int wl, int wr, int dtype, hipStream_t s);
+// the sinks' gradient of fa_bwd_varlen_sink (csrc/fa_sink_kernels.hip): dsinks[h] = -sum_i exp(sinks[h] - lse[h, i]) * delta[h, i] over the
+// query tokens a sequence owns, one workgroup per head, launched behind the dQ kernel that wrote delta
+hipError_t launch_dsink(const float *sinks, const float *lse, const float *delta, float *dsinks, const int *cu_q, int B, int H, int total_q,
+                        int max_q, hipStream_t s);
 
 // ---- host-side launch helper shared by every kernel file that needs more than 48 KiB of dynamic LDS
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device) instead of on every launch.

@@ -512,6 +512,78 @@ __global__ __launch_bounds__(64) void decode_combine_kernel(DecodeParams p) {
   if (p.lse != nullptr && lane == 0) p.lse[row_id] = (PAGED && !(lsum > 0.0f)) ? -INFINITY : (M + log2f(lsum)) * 0.6931471805599453f;
 }
 
+// fa_fwd_decode_paged_sink: decode_combine_kernel<.., PAGED = true> with the row's sink logit (sinks[hq], natural-log units) folded in
+// behind the reduction of the splits' (M, lsum): s2 = sink . log2(e), Mm = max(M, s2), lsum' = lsum 2^(M - Mm) + 2^(s2 - Mm), O = acc
+// 2^(M - Mm) / lsum', LSE = (Mm + log2 lsum') ln 2. Neither exponent is positive: nothing overflows; a sink whose 2^(s2 - M) underflows
+// leaves Mm = M, a factor of exactly 1 and lsum' = lsum + 0, the bits of the plain combine. A row whose splits saw no visible key
+// (lsum = 0) has the sink alone in its softmax: O = 0 exactly, LSE = sinks[hq] bit for bit.
+template <typename Tag, int D, int QT>
+__global__ __launch_bounds__(64) void decode_combine_sink_kernel(CombineSinkParams p) {
+  using elem = typename MD16<Tag>::elem;
+  __shared__ float wgt[256];
+  const int lane = threadIdx.x;
+  const int row_id = blockIdx.x;  // (b * Hq + hq) * Nq + iq
+  const int iq = row_id % p.Nq, bh = row_id / p.Nq;
+  const int hq = bh % p.Hq, b = bh / p.Hq;
+  const int G = p.Hq / p.Hkv, hkv = hq / G, gi = hq - hkv * G;
+  const int r = gi * p.Nq + iq;
+  const int S = p.S;  // <= 256
+  const float sink = p.sinks[hq];
+  constexpr int IST = (16 * QT) * (D + 2);
+  const float *w0 = p.ws + (size_t)(b * p.Hkv + hkv) * S * IST;
+  const float *ml = w0 + (16 * QT) * D + 2 * r;
+  float ms[4], ls[4];
+  float M = -INFINITY;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int s = lane + 64 * e;
+    ms[e] = s < S ? ml[(size_t)s * IST] : -INFINITY;
+    ls[e] = s < S ? ml[(size_t)s * IST + 1] : 0.0f;
+    M = fmaxf(M, ms[e]);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) M = fmaxf(M, __shfl_xor(M, o, 64));
+  float lsum = 0.0f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float f = (ms[e] == -INFINITY) ? 0.0f : __builtin_amdgcn_exp2f(ms[e] - M);  // a split that saw no visible key weighs nothing
+    wgt[lane + 64 * e] = f;
+    lsum += ls[e] * f;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) lsum += __shfl_xor(lsum, o, 64);
+  __syncthreads();
+  float acc[D / 64];
+#pragma unroll
+  for (int e = 0; e < D / 64; ++e) acc[e] = 0.0f;
+  const float *wr = w0 + r * D + lane;
+  int s = 0;
+  for (; s + 8 <= S; s += 8) {
+    float x[8][D / 64];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+      for (int e = 0; e < D / 64; ++e) x[u][e] = wr[(size_t)(s + u) * IST + 64 * e];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+      for (int e = 0; e < D / 64; ++e) acc[e] += x[u][e] * wgt[s + u];
+  }
+  for (; s < S; ++s)
+#pragma unroll
+    for (int e = 0; e < D / 64; ++e) acc[e] += wr[(size_t)s * IST + 64 * e] * wgt[s];
+  const bool dead = !(lsum > 0.0f);  // (then M = -inf: no exponent is formed from it)
+  const float s2 = sink * 1.4426950408889634f;
+  const float Mm = dead ? s2 : fmaxf(M, s2);
+  const float ow = dead ? 0.0f : __builtin_amdgcn_exp2f(M - Mm);
+  const float lt = lsum * ow + __builtin_amdgcn_exp2f(s2 - Mm);
+  const float inv = ow * (1.0f / lt);
+  elem *op = (elem *)p.o + (long long)b * p.q_bs + (long long)hq * p.q_hs + (long long)iq * D;
+#pragma unroll
+  for (int e = 0; e < D / 64; ++e) op[lane + 64 * e] = (elem)(acc[e] * inv);
+  if (p.lse != nullptr && lane == 0) p.lse[row_id] = dead ? sink : (Mm + log2f(lt)) * 0.6931471805599453f;
+}
+
 // ---------------------------------------------------------------------------
 bool decode_supported(int dtype, int D) {
   return (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16 || dtype == FA_DTYPE_FP8_E4M3) && (D == 64 || D == 128);
@@ -554,6 +626,23 @@ static hipError_t launch_decode_pair(KP partial, KC combine, size_t smem, const 
   return hipGetLastError();
 }
 
+// fa_fwd_decode_paged_sink: the pair above with the sink combine in the second launch
+template <typename Tag, int D, int QT, bool KV8>
+static hipError_t launch_decode_sink_q(const DecodeWindowParams &p, const float *sinks, hipStream_t s) {
+  auto partial = decode_partial_kernel<Tag, D, QT, true, KV8, DecodeWindowParams>;
+  constexpr size_t smem = decode_lds_bytes<D, KV8>();
+  (void)hipGetLastError();
+  if (smem > 48 * 1024) { hipError_t e = set_dyn_lds_once((const void *)partial, (int)smem); if (e != hipSuccess) return e; }
+  hipLaunchKernelGGL(partial, dim3(p.B * p.Hkv * p.S), dim3(64), smem, s, p);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  CombineSinkParams c;
+  (DecodeParams &)c = (const DecodeParams &)p;
+  c.sinks = sinks;
+  hipLaunchKernelGGL((decode_combine_sink_kernel<Tag, D, QT>), dim3(p.B * p.Hq * p.Nq), dim3(64), 0, s, c);
+  return hipGetLastError();
+}
+
 template <typename Tag, int D, int QT, bool KV8, typename PRM>
 static hipError_t launch_decode_q(const PRM &p, hipStream_t s) {
   constexpr bool PAGED = std::is_base_of<DecodePagedParams, PRM>::value, WINDOW = std::is_same<PRM, DecodeWindowParams>::value;
@@ -583,6 +672,18 @@ static hipError_t dispatch_decode(const PRM &p0, int D, int dtype, int kv8, hipS
 hipError_t launch_decode(const DecodeParams &p, int D, int dtype, int kv8, hipStream_t s) { return dispatch_decode(p, D, dtype, kv8, s); }
 hipError_t launch_decode_paged(const DecodePagedParams &p, int D, int dtype, int kv8, hipStream_t s) { return dispatch_decode(p, D, dtype, kv8, s); }
 hipError_t launch_decode_paged_window(const DecodeWindowParams &p, int D, int dtype, int kv8, hipStream_t s) { return dispatch_decode(p, D, dtype, kv8, s); }
+hipError_t launch_decode_paged_sink(const DecodeWindowParams &p0, const float *sinks, int D, int dtype, int kv8, hipStream_t s) {
+  DecodeWindowParams p = p0;
+  p.q8 = (dtype == FA_DTYPE_FP8_E4M3);
+  const int R = (p.Hq / p.Hkv) * p.Nq, QT = (R + 15) / 16;
+  auto go = [&](auto tag, auto k8) {
+    return with_dim<64, 128>(D, [&](auto d) {
+      return QT == 1 ? launch_decode_sink_q<decltype(tag), d(), 1, k8()>(p, sinks, s) : launch_decode_sink_q<decltype(tag), d(), 2, k8()>(p, sinks, s);
+    });
+  };
+  if (kv8 || dtype == FA_DTYPE_FP8_E4M3) return go(BF16{}, std::true_type{});
+  return with_tag(dtype, [&](auto tag) { return go(tag, std::false_type{}); });
+}
 
 // fa_kv_append_paged: new K / V rows -> their slots of the page pools, a byte copy (BYTES = element size). One 16-byte chunk per lane and
 // step: a workgroup takes APPEND_ROWS new rows of one (sequence, key head), K and V alike. The sequence lookup and its clamps are the

@@ -116,7 +116,11 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   // scalars, made non-negative by the host). Instantiated with CAUSAL: cu takes coff's place wherever the mask's upper limit is used,
   // and the lower limit is new -- the tile loop starts at the tile of the block's first row's bound, a wave skips tiles wholly below
   // ITS first row's bound, and its first ACTIVE tile takes the exact path.
-  constexpr bool WINDOW = std::is_same<PT, VarlenWindowParams>::value || std::is_same<PT, VarlenPagedWindowParams>::value;
+  constexpr bool WINDOW = std::is_base_of<VarlenWindowParams, PT>::value || std::is_base_of<VarlenPagedWindowParams, PT>::value;
+  // SINK (PT = VarlenSinkParams / VarlenPagedSinkParams; fa_fwd_varlen_sink, fa_fwd_varlen_paged_sink): window mode with one more term in
+  // every row's denominator, exp(sinks[head]), which carries no value. The tile loop does not know of it: the logit is one wave-uniform
+  // scalar load per block, turned to log2 units, and the epilogue folds it into (m, l) by the larger of the row's reference and the sink.
+  constexpr bool SINK = std::is_same<PT, VarlenSinkParams>::value || std::is_same<PT, VarlenPagedSinkParams>::value;
   static_assert(!WINDOW || CAUSAL, "window mode: the upper bound is the causal one with its own offset");
   static_assert(!VARLEN || (SPLIT == 1 && ROWS == BM && PRESC && !std::is_same<Tag, FP8>::value && (D == 64 || D == 128)),
                 "varlen mode: the plain 128-row kernel, 16-bit inputs, LDS-DMA staging");
@@ -187,6 +191,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   const int *ptbl = nullptr;   // varlen paged: this sequence's row of the block table
   int cl = 0, cu = 0;          // window mode: key j is visible to row i iff i + cl <= j <= i + cu
   int t_lo = 0, kv_hi = 0;     // window mode: the block's first tile and the end of its key range
+  float sink = 0.0f;           // sink mode: sinks[head], natural-log units
 #define FA_NQ (VARLEN ? LQ : p.N)
 #define FA_NK (VARLEN ? LK : p.Nk)
   if constexpr (VARLEN) {
@@ -205,6 +210,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
     base_kv = (long long)sk * p.kv_rs + (long long)fdiv((unsigned)hq, p.fd_gq) * p.kv_head_stride;  // (varlen paged: the key head's offset inside a page)
     if constexpr (PAGEDV) ptbl = p.block_table + (long long)b * p.bt_stride;
     lse_base = (long long)hq * p.total_q + sq;
+    if constexpr (SINK) sink = p.sinks[hq];
     qrb = (unsigned)p.q_rs * 2;
     kvrb = (unsigned)p.kv_rs * 2;
     // no key is visible to any row of the block (no keys at all, or causal with Lk < Lq: key j is visible to query i iff
@@ -225,7 +231,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         if (row < LQ) *reinterpret_cast<u32x4 *>(Oz + (long long)row * p.q_rs + ch * 8) = u32x4{0u, 0u, 0u, 0u};
       }
       const int row = qb * ROWS + (int)threadIdx.x;
-      if (p.lse != nullptr && (int)threadIdx.x < ROWS && row < LQ) p.lse[lse_base + row] = -INFINITY;
+      if (p.lse != nullptr && (int)threadIdx.x < ROWS && row < LQ) p.lse[lse_base + row] = SINK ? sink : -INFINITY;  // (sink mode: the sink alone)
       return;
     }
   } else {
@@ -810,10 +816,21 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
       asm volatile("" : "+s"(coff_e));
       no_key = qrow + coff_e < 0;
     }
-    const float inv_l = (VARLEN && CAUSAL) ? (no_key ? 0.0f : 1.0f / l) : 1.0f / l;
+    // sink mode: the row's softmax gets the term 2^s2, s2 = sink . log2(e), against the reference mm = max(m, s2): l' = l 2^(m - mm) +
+    // 2^(s2 - mm) and O = oacc . 2^(m - mm) / l'. Neither exponent is positive, so nothing overflows whichever side is far larger; a sink
+    // whose 2^(s2 - m) underflows leaves mm = m, a factor of exactly 1 and l' = l + 0: the bits of the call without sinks.
+    float o_w = 1.0f;  // the factor 2^(m - mm) on O
+    if constexpr (SINK) {
+      const float s2 = sink * 1.4426950408889634f;
+      const float mm = fmaxf(m, s2);
+      o_w = __builtin_amdgcn_exp2f(m - mm);
+      l = l * o_w + __builtin_amdgcn_exp2f(s2 - mm);
+      m = mm;
+    }
+    const float inv_l = (VARLEN && CAUSAL) ? (no_key ? 0.0f : (SINK ? o_w * (1.0f / l) : 1.0f / l)) : 1.0f / l;
     if constexpr (VARLEN) {
       if (p.lse != nullptr && h == 0 && qrow < LQ)
-        p.lse[lse_base + qrow] = no_key ? -INFINITY : m * 0.6931471805599453f + logf(l);
+        p.lse[lse_base + qrow] = no_key ? (SINK ? sink : -INFINITY) : m * 0.6931471805599453f + logf(l);
     } else {
     if (p.lse != nullptr && h == 0 && qrow < p.N)
       p.lse[(long long)bh * p.N + qrow] = m * (PRE ? 0.6931471805599453f : p.scale) + logf(l);
@@ -894,6 +911,16 @@ __global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_window_p
   fwd_mfma_body<Tag, D, true, 1, true, BM, VarlenPagedWindowParams>(p);
 }
 
+// fa_fwd_varlen_sink / fa_fwd_varlen_paged_sink: the two window kernels in sink mode, at their occupancy
+template <typename Tag, int D>
+__global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_sink_kernel(VarlenSinkParams p) {
+  fwd_mfma_body<Tag, D, true, 1, true, BM, VarlenSinkParams>(p);
+}
+template <typename Tag, int D>
+__global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_sink_paged_kernel(VarlenPagedSinkParams p) {
+  fwd_mfma_body<Tag, D, true, 1, true, BM, VarlenPagedSinkParams>(p);
+}
+
 // ---------------------------------------------------------------------------
 bool mfma_supported(int dtype, int D) {
   if (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) return D == 32 || D == 64 || D == 96 || D == 128 || D == 256;
@@ -958,6 +985,18 @@ hipError_t launch_mfma_varlen_window(const VarlenWindowParams &p, int dtype, hip
 hipError_t launch_mfma_varlen_paged_window(const VarlenPagedWindowParams &p, int dtype, hipStream_t s) {
   return with_tag(dtype, [&](auto tag) {
     return with_dim<64, 128>(p.D, [&](auto d) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_window_paged_kernel<decltype(tag), d()>, p, s); });
+  });
+}
+
+hipError_t launch_mfma_varlen_sink(const VarlenSinkParams &p, int dtype, hipStream_t s) {
+  return with_tag(dtype, [&](auto tag) {
+    return with_dim<64, 128>(p.D, [&](auto d) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_sink_kernel<decltype(tag), d()>, p, s); });
+  });
+}
+
+hipError_t launch_mfma_varlen_paged_sink(const VarlenPagedSinkParams &p, int dtype, hipStream_t s) {
+  return with_tag(dtype, [&](auto tag) {
+    return with_dim<64, 128>(p.D, [&](auto d) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_sink_paged_kernel<decltype(tag), d()>, p, s); });
   });
 }
 

@@ -247,6 +247,20 @@ def _window(window, is_causal: bool) -> Tuple[int, int]:
     return left, right
 
 
+def _sinks(sinks: torch.Tensor, Hq: int, device: torch.device) -> torch.Tensor:
+    """The sinks of a *_sink entry point (include/fa_mi355.h, "Attention sinks"): one logit per query head, as contiguous fp32 on `device`."""
+    if not isinstance(sinks, torch.Tensor) or sinks.dim() != 1 or sinks.shape[0] != Hq:
+        raise ValueError(f"sinks must be a [Hq] = [{Hq}] tensor, one logit per query head")
+    if not sinks.is_cuda or sinks.device != device:
+        raise ValueError("sinks must be on q's device: the kernels read them, the host never does")
+    return sinks.detach().to(torch.float32).contiguous()
+
+
+def _sink_window(window, is_causal: bool) -> Tuple[int, int]:
+    """The window of a call with sinks: None is (-1, 0) under is_causal and (-1, -1) without."""
+    return ((-1, 0) if is_causal else (-1, -1)) if window is None else _window(window, is_causal)
+
+
 def decode_paged_workspace_bytes(B: int, Hq: int, Hkv: int, Nq: int, D: int, page_size: int, max_pages_per_seq: int) -> int:
     return int(load_library().fa_fwd_decode_paged_workspace_bytes(B, Hq, Hkv, Nq, D, page_size, max_pages_per_seq))
 
@@ -266,6 +280,7 @@ def flash_attention_decode_paged(
     workspace: Optional[torch.Tensor] = None,
     stream: Optional[int] = None,
     window: Optional[Tuple[int, int]] = None,
+    sinks: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """A decode step against a paged KV cache (include/fa_mi355.h fa_fwd_decode_paged): q [B,Hq,Nq,D]; k_pages / v_pages one pool
     each, [num_pages, Hkv, P, D] (layout "HND") or [num_pages, P, Hkv, D] ("NHD"), P in {16, 32, 64, 128, 256}; block_table int32
@@ -274,7 +289,9 @@ def flash_attention_decode_paged(
     dtypes as flash_attention_decode (f16, bf16, e4m3, or bf16 queries on an e4m3 pool). A row with no visible key gets O = 0 and
     LSE = -inf. `workspace`: a uint8 device tensor of at least decode_paged_workspace_bytes(...) bytes (allocated here if None).
     window=(left, right): a sliding window (fa_fwd_decode_paged_window: key j visible to query i iff i + L_b - Nq - left <= j <=
-    i + L_b - Nq + right; negative = unbounded; with is_causal=True right must be 0 or negative). None: the call above, untouched."""
+    i + L_b - Nq + right; negative = unbounded; with is_causal=True right must be 0 or negative). None: the call above, untouched.
+    sinks: a [Hq] tensor of per-head sink logits (fa_fwd_decode_paged_sink: exp(sinks[h]) joins every softmax denominator of head h and
+    carries no value; a row with no visible key then gets O = 0 and LSE = sinks[h]). None: the calls above, untouched."""
     lib = load_library()
     if q.dim() != 4 or k_pages.dim() != 4 or k_pages.shape != v_pages.shape:
         raise ValueError("q [B,Hq,Nq,D], k_pages / v_pages one [num_pages,Hkv,P,D] (HND) or [num_pages,P,Hkv,D] (NHD) shape")
@@ -304,7 +321,11 @@ def flash_attention_decode_paged(
     out, lse = _out(out, q, qs), _lse(lse, return_lse, q)
     ws = _workspace(workspace, decode_paged_workspace_bytes(B, Hq, Hkv, Nq, D, P, max(max_pages, 1)), q.device)
     mask = (int(bool(is_causal)),) if window is None else _window(window, is_causal)
-    _call(lib, "fa_fwd_decode_paged" if window is None else "fa_fwd_decode_paged_window",
+    entry = "fa_fwd_decode_paged" if window is None else "fa_fwd_decode_paged_window"
+    if sinks is not None:
+        sinks = _sinks(sinks, Hq, q.device)
+        entry, mask = "fa_fwd_decode_paged_sink", _sink_window(window, is_causal) + (sinks.data_ptr(),)
+    _call(lib, entry,
           (q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(), _ptr(lse), block_table.data_ptr(), seqlens_k.data_ptr(),
            B, Hq, Hkv, Nq, D, P, num_pages, max_pages, _scale(scale, D), *qs, ps, hs, rs, block_table.stride(0), *mask,
            _TORCH2FA[q.dtype], _TORCH2FA[k_pages.dtype], ws.data_ptr(), ws.numel()), q.device, stream)
@@ -330,6 +351,7 @@ def flash_attention_varlen(
     lse: Optional[torch.Tensor] = None,
     stream: Optional[int] = None,
     window: Optional[Tuple[int, int]] = None,
+    sinks: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """The forward over packed variable-length sequences (include/fa_mi355.h fa_fwd_varlen): q [total_q, Hq, D], k / v
     [total_k, Hkv, D], f16 / bf16, D = 64 | 128. Strides are taken from the tensors: any view with unit element stride works ([H, total, D]
@@ -340,8 +362,10 @@ def flash_attention_varlen(
     sequence; a row with no visible key gets O = 0 and LSE = -inf; tokens at or past cu_seqlens_q[B] and rows beyond max_seqlen_q of a
     sequence are not written. window=(left, right): a sliding window (fa_fwd_varlen_window: key j visible to query i iff
     i + Lk_b - Lq_b - left <= j <= i + Lk_b - Lq_b + right; negative = unbounded; with is_causal=True right must be 0 or negative);
-    None: the call above, untouched. Returns (out, lse): out like q ([total_q, Hq, D], q's strides unless `out` is given), lse
-    [Hq, total_q]."""
+    None: the call above, untouched. sinks: a [Hq] tensor of per-head sink logits (fa_fwd_varlen_sink: exp(sinks[h]) joins every softmax
+    denominator of head h and carries no value -- natural-log units, the scale is not applied to it; a row with no visible key then gets
+    O = 0 and LSE = sinks[h]; window=None with sinks is (-1, 0) under is_causal, else (-1, -1)); None: the calls above, untouched.
+    Returns (out, lse): out like q ([total_q, Hq, D], q's strides unless `out` is given), lse [Hq, total_q]."""
     lib = load_library()
     if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape:
         raise ValueError(f"q [total_q,Hq,D] and k, v one [total_k,Hkv,D] shape, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
@@ -372,7 +396,11 @@ def flash_attention_varlen(
     elif not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.shape != (Hq, total_q):
         raise ValueError("lse must be contiguous fp32 [Hq, total_q] on q's device")
     mask = (int(bool(is_causal)),) if window is None else _window(window, is_causal)
-    _call(lib, "fa_fwd_varlen" if window is None else "fa_fwd_varlen_window",
+    entry = "fa_fwd_varlen" if window is None else "fa_fwd_varlen_window"
+    if sinks is not None:
+        sinks = _sinks(sinks, Hq, q.device)
+        entry, mask = "fa_fwd_varlen_sink", _sink_window(window, is_causal) + (sinks.data_ptr(),)
+    _call(lib, entry,
           (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
            B, Hq, Hkv, total_q, total_k, int(max_seqlen_q), int(max_seqlen_k), D, _scale(scale, D), q.stride(0), q.stride(1),
            k.stride(0), k.stride(1), *mask, _TORCH2FA[q.dtype]), q.device, stream)
@@ -426,6 +454,7 @@ def flash_attention_varlen_paged(
     lse: Optional[torch.Tensor] = None,
     stream: Optional[int] = None,
     window: Optional[Tuple[int, int]] = None,
+    sinks: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Packed queries against a paged KV cache (include/fa_mi355.h fa_fwd_varlen_paged): chunked prefill, prefix caching, verification of
     many speculated tokens. q [total_q, Hq, D] as in flash_attention_varlen (any view with a unit element stride), cu_seqlens_q int32
@@ -436,7 +465,8 @@ def flash_attention_varlen_paged(
     captured in a graph and replayed after the tables change in place. A row with no visible key gets O = 0 and LSE = -inf; tokens at or
     past cu_seqlens_q[B] and rows beyond max_seqlen_q of a sequence are not written. An inference path: no torch custom op and no
     backward. window=(left, right): a sliding window as in flash_attention_varlen, with seqlens_k[b] in Lk_b's place
-    (fa_fwd_varlen_paged_window); None: the call above, untouched. Returns (out, lse): out like q, lse [Hq, total_q]."""
+    (fa_fwd_varlen_paged_window); None: the call above, untouched. sinks: [Hq] per-head sink logits as in flash_attention_varlen
+    (fa_fwd_varlen_paged_sink); None: the calls above, untouched. Returns (out, lse): out like q, lse [Hq, total_q]."""
     lib = load_library()
     entry = "flash_attention_varlen_paged"
     if q.dim() != 3:
@@ -461,7 +491,11 @@ def flash_attention_varlen_paged(
     elif not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.shape != (Hq, total_q):
         raise ValueError("lse must be contiguous fp32 [Hq, total_q] on q's device")
     mask = (int(bool(is_causal)),) if window is None else _window(window, is_causal)
-    _call(lib, "fa_fwd_varlen_paged" if window is None else "fa_fwd_varlen_paged_window",
+    entry = "fa_fwd_varlen_paged" if window is None else "fa_fwd_varlen_paged_window"
+    if sinks is not None:
+        sinks = _sinks(sinks, Hq, q.device)
+        entry, mask = "fa_fwd_varlen_paged_sink", _sink_window(window, is_causal) + (sinks.data_ptr(),)
+    _call(lib, entry,
           (q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), block_table.data_ptr(),
            seqlens_k.data_ptr(), B, Hq, Hkv, total_q, int(max_seqlen_q), D, P, num_pages, block_table.shape[1], _scale(scale, D),
            q.stride(0), q.stride(1), ps, hs, rs, block_table.stride(0), *mask, _TORCH2FA[q.dtype]), q.device, stream)
@@ -531,7 +565,9 @@ def flash_attention_varlen_backward(
     workspace: Optional[torch.Tensor] = None,
     stream: Optional[int] = None,
     window: Optional[Tuple[int, int]] = None,
-) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    sinks: Optional[torch.Tensor] = None,
+    dsinks: Optional[torch.Tensor] = None,
+):
     """The backward over packed variable-length sequences (include/fa_mi355.h fa_bwd_varlen), the counterpart of
     flash_attention_varlen: q, o, d_o [total_q, Hq, D] under one set of strides, k, v [total_k, Hkv, D] under another, f16 / bf16,
     D = 64 | 128; lse the forward's [Hq, total_q]; the tables as in flash_attention_varlen. Returns (dq, dk, dv) in fp32 under the
@@ -542,7 +578,10 @@ def flash_attention_varlen_backward(
     value: it can be captured in a graph and replayed after the tables change in place.
     window=(left, right): the backward of flash_attention_varlen(window=...) (fa_bwd_varlen_window: key j visible to query i iff
     i + Lk_b - Lq_b - left <= j <= i + Lk_b - Lq_b + right, a negative side unbounded; with is_causal the right side is 0); a key no
-    query sees gets dK = dV = 0. None: the call above, untouched."""
+    query sees gets dK = dV = 0. None: the call above, untouched.
+    sinks: the [Hq] sink logits of the forward that wrote o and lse (fa_bwd_varlen_sink). The call then returns (dq, dk, dv, dsinks):
+    dsinks fp32 [Hq] (written, not accumulated; allocated unless given), dq / dk / dv bit for bit those of the call without sinks on the
+    same tensors. None: the calls above, untouched, three gradients."""
     lib = load_library()
     if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or o.shape != q.shape or d_o.shape != q.shape:
         raise ValueError(f"q, o, d_o one [total_q,Hq,D] shape and k, v one [total_k,Hkv,D] shape, got {tuple(q.shape)} {tuple(o.shape)} "
@@ -583,12 +622,22 @@ def flash_attention_varlen_backward(
     if ws.numel() < need:
         raise ValueError(f"workspace of {ws.numel()} bytes, varlen_backward_workspace_bytes() asks for {need}")
     mask = (int(bool(is_causal)),) if window is None else _window(window, is_causal)
-    _call(lib, "fa_bwd_varlen" if window is None else "fa_bwd_varlen_window",
+    entry = "fa_bwd_varlen" if window is None else "fa_bwd_varlen_window"
+    if sinks is not None:
+        sinks = _sinks(sinks, Hq, q.device)
+        if dsinks is None:
+            dsinks = torch.empty(Hq, dtype=torch.float32, device=q.device)
+        elif not dsinks.is_cuda or dsinks.device != q.device or dsinks.dtype != torch.float32 or dsinks.shape != (Hq,) or not dsinks.is_contiguous():
+            raise ValueError("dsinks must be a contiguous fp32 [Hq] tensor on q's device")
+        entry, mask = "fa_bwd_varlen_sink", _sink_window(window, is_causal) + (sinks.data_ptr(), dsinks.data_ptr())
+    elif dsinks is not None:
+        raise ValueError("dsinks without sinks")
+    _call(lib, entry,
           (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
            dv.data_ptr(), ws.data_ptr(), cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), B, Hq, Hkv, total_q, total_k,
            int(max_seqlen_q), int(max_seqlen_k), D, _scale(scale, D), q.stride(0), q.stride(1), k.stride(0), k.stride(1),
            *mask, _TORCH2FA[q.dtype]), q.device, stream)
-    return dq, dk, dv
+    return (dq, dk, dv) if sinks is None else (dq, dk, dv, dsinks)
 
 
 def flash_attention_backward(

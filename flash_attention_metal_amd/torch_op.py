@@ -23,6 +23,13 @@ returns the gradients in the input dtype.
 
 attention_varlen under a sliding window (fa_fwd_varlen_window / fa_bwd_varlen_window; a negative side is unbounded), differentiable in the
 same way. attention_varlen(..., window=(left, right)) dispatches to it.
+
+    torch.ops.fa_mi355.attention_varlen_sink(q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window_left,
+                                             window_right, scale) -> (o, lse)
+
+attention_varlen_window with one learnt sink logit per query head in every softmax denominator (fa_fwd_varlen_sink / fa_bwd_varlen_sink):
+sinks [Hq], any float dtype. Autograd gives q, k, v AND sinks their gradients, the sinks' in the parameter's own dtype.
+attention_varlen(..., sinks=) dispatches to it.
 """
 from __future__ import annotations
 
@@ -30,7 +37,7 @@ from typing import Tuple
 
 import torch
 
-from .ops import (_TORCH2FA, FaError, _out_dtype, _window, flash_attention_backward, flash_attention_forward, flash_attention_varlen,
+from .ops import (_TORCH2FA, FaError, _out_dtype, _sink_window, _window, flash_attention_backward, flash_attention_forward, flash_attention_varlen,
                   flash_attention_varlen_backward, load_library)
 
 _LIB = torch.library.Library("fa_mi355", "DEF")
@@ -193,9 +200,68 @@ torch.library.register_autograd("fa_mi355::attention_varlen_window", _varlen_win
                                 lib=_LIB)
 
 
+_LIB.define("attention_varlen_sink(Tensor q, Tensor k, Tensor v, Tensor sinks, Tensor cu_seqlens_q, Tensor cu_seqlens_k, int max_seqlen_q, "
+            "int max_seqlen_k, int window_left, int window_right, float scale=0.0) -> (Tensor, Tensor)")
+
+
+def _varlen_sink_impl(q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window_left, window_right, scale=0.0):
+    out = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device).zero_()
+    lse = torch.full((q.shape[1], q.shape[0]), float("-inf"), dtype=torch.float32, device=q.device)
+    return flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale=(scale if scale > 0 else None),
+                                  out=out, lse=lse, window=(window_left, window_right), sinks=sinks)
+
+
+def _varlen_sink_meta(q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window_left, window_right, scale=0.0):
+    return torch.empty_like(q), q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32)
+
+
+_LIB.impl("attention_varlen_sink", _varlen_sink_impl, "CUDA")
+_LIB.impl("attention_varlen_sink", _varlen_sink_meta, "Meta")
+
+
+def _varlen_sink_setup_context(ctx, inputs, output):
+    q, k, v, sinks, cu_q, cu_k, max_q, max_k, window_left, window_right, scale = inputs
+    o, lse = output
+    ctx.save_for_backward(q, k, v, sinks, o, lse, cu_q, cu_k)
+    ctx.max_q, ctx.max_k, ctx.window, ctx.scale = int(max_q), int(max_k), (int(window_left), int(window_right)), float(scale)
+    ctx.set_materialize_grads(False)
+
+
+def _varlen_sink_backward(ctx, grad_o, grad_lse):
+    q, k, v, sinks, o, lse, cu_q, cu_k = ctx.saved_tensors
+    if grad_lse is not None:
+        raise NotImplementedError("fa_mi355::attention_varlen_sink: no gradient through the LSE output")
+    none = (None,) * 11
+    if grad_o is None:
+        return none
+    if q.dtype not in _TORCH2FA or not load_library().fa_bwd_varlen_supported(_TORCH2FA[q.dtype], q.shape[2]):
+        raise FaError(-2, f"no varlen backward kernel for q {tuple(q.shape)} {q.dtype} (f16 / bf16, head_dim 64 or 128)", "fa_bwd_varlen_sink")
+    go = grad_o.to(o.dtype)
+    if go.stride() != q.stride():  # d_o is addressed under q's strides
+        go = torch.empty_strided(q.shape, q.stride(), dtype=o.dtype, device=q.device).copy_(go)
+    if o.stride() != q.stride():
+        o = torch.empty_strided(q.shape, q.stride(), dtype=o.dtype, device=q.device).copy_(o)
+    # zero-initialised: tokens owned by no sequence are not written by the kernels and get a zero gradient
+    dq = torch.empty_strided(q.shape, q.stride(), dtype=torch.float32, device=q.device).zero_()
+    dk = torch.empty_strided(k.shape, k.stride(), dtype=torch.float32, device=q.device).zero_()
+    dv = torch.empty_strided(k.shape, k.stride(), dtype=torch.float32, device=q.device).zero_()
+    _, _, _, dsinks = flash_attention_varlen_backward(q, k, v, o, go, lse, cu_q, cu_k, ctx.max_q, ctx.max_k,
+                                                      scale=(ctx.scale if ctx.scale > 0 else None), dq=dq, dk=dk, dv=dv, window=ctx.window,
+                                                      sinks=sinks)
+    return (dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), dsinks.to(sinks.dtype)) + none[4:]
+
+
+torch.library.register_autograd("fa_mi355::attention_varlen_sink", _varlen_sink_backward, setup_context=_varlen_sink_setup_context, lib=_LIB)
+
+
 def attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_seqlen_k: int, is_causal: bool = False, scale: float = 0.0,
-                     window=None):
-    """window=(left, right): fa_mi355::attention_varlen_window (differentiable through fa_bwd_varlen_window); None: the op above."""
+                     window=None, sinks=None):
+    """window=(left, right): fa_mi355::attention_varlen_window (differentiable through fa_bwd_varlen_window); None: the op above.
+    sinks=[Hq] logits: fa_mi355::attention_varlen_sink (differentiable in q, k, v and sinks; window=None is (-1, 0) under is_causal, else
+    (-1, -1))."""
+    if sinks is not None:
+        left, right = _sink_window(window, is_causal)
+        return torch.ops.fa_mi355.attention_varlen_sink(q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, left, right, scale)
     if window is None:
         return torch.ops.fa_mi355.attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, scale)
     left, right = _window(window, is_causal)

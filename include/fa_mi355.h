@@ -497,6 +497,84 @@ int fa_bwd_varlen_window(const void *q, const void *k, const void *v, const void
  * FA_ERR_INVALID_ARG for a null pointer or a negative length. */
 int fa_window_query_range(int Lq, int Lk, int window_left, int window_right, int key_first, int key_last, int *row_lo, int *row_hi);
 
+/*
+ * Attention sinks: fa_fwd_varlen_sink, fa_fwd_varlen_paged_sink, fa_fwd_decode_paged_sink and fa_bwd_varlen_sink are the four *_window
+ * entry points with one learnt logit per QUERY head in every softmax (the layers of models that alternate sliding-window and full causal
+ * attention): a term in the denominator that carries no value,
+ *     P_ij  = exp(scale s_ij) / (sum_{j' visible} exp(scale s_ij') + exp(sinks[h]))
+ *     O_i   = sum_j P_ij v_j
+ *     LSE_i = ln(sum_{j visible} exp(scale s_ij) + exp(sinks[h])).
+ * `sinks` is a DEVICE pointer to Hq fp32 values, read by the kernels only (the host never reads them: the calls stay graph-capturable and
+ * the values may change between replays). Units are natural-log logits: the softmax scale is NOT applied to them. They must be finite.
+ * Visibility is the rule of "Sliding window" above under (window_left, window_right), unchanged. A row with no visible key (that section's
+ * integer test) has the sink alone in its softmax: O = 0 exactly and LSE = sinks[h], the fp32 value bit for bit -- not -inf.
+ * Each forward takes the matching *_window signature with `const float *sinks` added behind the window, and shares that call's validation,
+ * status codes, error texts, support tables and decode workspace; sinks == NULL (or not fp32-aligned) is FA_ERR_INVALID_ARG.
+ * ROUTING: the three forwards ALWAYS run the window-mode kernels, in their sink mode -- (-1, 0) with sinks is the causal layer, (127, 0) the
+ * windowed one, (-1, -1) the full one, through one kernel family (eight 128-row kernels; the decode reuses the windowed partial kernels and
+ * folds the sink in its combine step). An unbounded or oversized side is clamped on the host to the never-binding width, as in
+ * "Sliding window". Never-binding bounds were measured at 0.2-6 % over the un-windowed kernels (README, round 14; round 18: 0.9-5.2 %, in one
+ * session 10 % on the paged head_dim-64 prefill); that price is accepted here instead of sixteen more kernels.
+ * The sink enters once per row, where the row is normalised; the tile loops do not know of it. With the row's reference m and sum l
+ * (log2 units, as the kernels keep them) and s2 = sinks[h] * log2(e):
+ *     mm = max(m, s2),   l' = l * 2^(m - mm) + 2^(s2 - mm),   O = acc * 2^(m - mm) / l',   LSE = (mm + log2 l') * ln 2.
+ * Neither exponent is positive, so the merge overflows in neither direction: a sink far above every score gives finite, tiny O and
+ * LSE ~ sink; a sink whose 2^(s2 - m) underflows to 0 in fp32 (e.g. sinks[h] = -1e4) leaves mm = m, a factor of exactly 1
+ * and l' = l + 0: O and LSE are then BIT-IDENTICAL to the *_window call. The paged prefill with sinks is bit-identical to the packed call
+ * with sinks on every sequence with L_b >= Lq_b >= 1, as without.
+ * Accuracy. By the identity O' = O * exp(lse - lse'), lse' = ln(exp(lse) + exp(sink)), with (O, lse) the results without the sink:
+ * d lse' / d lse = exp(lse - lse') <= 1, so the route's own LSE error ("LSE accuracy") enters with a weight of at most 1, and the fold
+ * costs a handful of fp32 roundings -- sinks[h] * log2(e) (felt through the sink's share 1 - exp(lse - lse') of the sum), the two exp2, the
+ * sum, log and the product by ln 2:
+ *     |LSE' - exact| <= lse_tol + 2^-22 * ((1 - exp(lse - lse')) * |sinks[h]| + |lse'| + 4) =: lse_tol'
+ *     |O'_d - exact| <= o_tol + |O'_d| * lse_tol'
+ * (the factor exp(lse - lse') on O carries the error of both logarithms; o_tol itself shrinks with it and is kept as it is).
+ *
+ * fa_bwd_varlen_sink: fa_bwd_varlen_window plus `const float *sinks, float *dsinks`. lse is the forward's, which contains the sink, so
+ * P = exp(scale s - lse) and delta = rowsum(dO o O) are exactly what the dQ and dK/dV kernels compute already: they run UNCHANGED, routed by
+ * sign as in fa_bwd_varlen_window, and dQ, dK, dV are BIT-IDENTICAL to fa_bwd_varlen_window on the same six tensors. "Backward accuracy"
+ * applies with the sink-including LSE and lse_tol' / the O bound above as its forward terms. dsinks is [Hq] fp32, WRITTEN, not accumulated;
+ * it may be NULL, then the reduction is skipped. One more launch on the same stream, behind the pair:
+ *     dsinks[h] = - sum_i exp(sinks[h] - lse[h, i]) * delta[h, i]
+ * over the query tokens i a sequence OWNS (cu_seqlens_q walked with the dQ kernel's clamps; tokens owned by nobody and rows past the
+ * max_seqlen_q clamp hold stale workspace and are never read). One workgroup per head, thread t adds rows t, t + 1024, ... of every
+ * sequence in order, then a fixed binary tree: no atomics, bitwise reproducible; the grid is Hq, host scalars only. A dead row adds
+ * exp(0) * 0 = 0. Against the fp64 formula on the lse and delta it was given, with x_i = sinks[h] - lse_i, t_i = exp(x_i) delta_i and
+ * c = sum_b ceil(Lq_b / 1024) + 10 additions on the longest path:
+ *     |dsinks[h] - exact| <= 2^-24 * sum_i |t_i| * (|x_i| + 3 + c)
+ * (the subtraction moves exp by a factor within 2^-24 |x_i|, expf and the product add 2.5 ulp, the sum c per term). Against the true
+ * gradient the chain adds sum_i p_i exp(lse_err_i) (|delta_i| lse_err_i + delta_err_i), delta_err_i = sum_d |dO_id| o_err_id (p moves by a
+ * factor within exp(+-lse_err), delta by delta_err). tests/sink.py spells the bars out, tests/test_sink_cases.py holds an fp32 model of the
+ * epilogues and of the reduction to them, tests/test_gpu_sink.py and test_gpu_sink_bwd.py the kernels.
+ */
+int fa_fwd_varlen_sink(const void *q, const void *k, const void *v, void *o, float *lse,
+                       const int *cu_seqlens_q, const int *cu_seqlens_k,
+                       int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k,
+                       int D, float scale, long long q_row_stride, long long q_head_stride,
+                       long long kv_row_stride, long long kv_head_stride,
+                       int window_left, int window_right, const float *sinks, int dtype, void *hip_stream);
+int fa_fwd_varlen_paged_sink(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                             const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                             int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                             int page_size, int num_pages, int max_pages_per_seq, float scale,
+                             long long q_row_stride, long long q_head_stride,
+                             long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                             long long block_table_stride, int window_left, int window_right, const float *sinks, int dtype,
+                             void *hip_stream);
+int fa_fwd_decode_paged_sink(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                             const int *block_table, const int *seqlens_k,
+                             int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages, int max_pages_per_seq,
+                             float scale, long long q_batch_stride, long long q_head_stride,
+                             long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                             long long block_table_stride, int window_left, int window_right, const float *sinks,
+                             int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes, void *hip_stream);
+int fa_bwd_varlen_sink(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse,
+                       float *dq, float *dk, float *dv, void *workspace,
+                       const int *cu_seqlens_q, const int *cu_seqlens_k,
+                       int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
+                       long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
+                       int window_left, int window_right, const float *sinks, float *dsinks, int dtype, void *hip_stream);
+
 /* 1 if fa_fwd has a kernel for the combination, else 0 (no GPU needed). */
 int fa_supported(int dtype, int variant, int D);
 
