@@ -30,6 +30,7 @@ from .ops import (  # noqa: F401
     supported,
     varlen_backward_supported,
     varlen_backward_workspace_bytes,
+    varlen_paged_kv8_supported,
     varlen_paged_supported,
     varlen_supported,
 )

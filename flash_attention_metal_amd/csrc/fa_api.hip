@@ -35,6 +35,8 @@ int fail(int code, const char *fmt, ...) {
 //    B * Hkv * ceil(max_seqlen_k / 128));
 //  - fa_fwd_varlen_paged: fa_fwd_varlen's rules for q and the grid, page_pool_ok for the pools and tables (the paged decode's rules);
 //    fa_kv_append_paged: varlen_strides_ok for the new rows, page_pool_ok, and a grid of B * ceil(max_seqlen_new / 16) x Hkv;
+//  - fa_fwd_varlen_paged_kv8: varlen_paged_impl with the pools' own type (strides of 16 elements, a page counted in bytes of 1), its own
+//    support table, sinks optional; fa_kv_append_paged_quant: kv_append_impl with e4m3 pools, plus the two multipliers;
 //  - the four *_sink entry points: the impl function, and with it every rule, of their *_window call, plus sinks_ok (and dsinks' alignment);
 //  - a missing device: FA_ERR_NO_DEVICE from fa_fwd, FA_ERR_LAUNCH from every other entry point.
 #define TRY(check) do { if (const int st_ = (check)) return st_; } while (0)
@@ -623,25 +625,33 @@ static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages,
                              int max_seqlen_q, int D, int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride,
                              long long q_head_stride, long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
                              long long block_table_stride, int window_left, int window_right, int dtype, void *hip_stream,
-                             const float *const *sinks = nullptr) {
+                             const float *const *sinks = nullptr, const int *kv8_dtype = nullptr) {
+  // kv8_dtype (fa_fwd_varlen_paged_kv8): `dtype` is q's and *kv8_dtype the pools'. Every rule below is the one path of both families;
+  // what differs is the support table with its text, the pools' stride multiple and bytes per element (page_pool_ok under the pools'
+  // type), and the routing: that call always runs its own kernel family, with or without sinks.
   g_err[0] = 0;
   TRY(nonnull(fn, {q, k_pages, v_pages, o, cu_seqlens_q, block_table, seqlens_k}));
   if (sinks) TRY(sinks_ok(fn, *sinks));
   TRY(positive(fn, {B, Hq, Hkv, total_q, max_seqlen_q, D, page_size, num_pages, max_pages_per_seq}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
-  if (!fa_fwd_varlen_paged_supported(dtype, D, page_size))
+  const int kv_dtype = kv8_dtype ? *kv8_dtype : dtype;
+  if (kv8_dtype && !fa_fwd_varlen_paged_kv8_supported(dtype, kv_dtype, D, page_size))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs bf16 queries on an fp8_e4m3 pool, D = 64 | 128 and a page size of 16, 32, 64, 128 or 256; "
+                "got q=%s kv=%s D=%d page_size=%d (q and the pool of one 16-bit type: fa_fwd_varlen_paged)", fn, fa_dtype_name(dtype),
+                fa_dtype_name(kv_dtype), D, page_size);
+  if (!kv8_dtype && !fa_fwd_varlen_paged_supported(dtype, D, page_size))
     return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 (q and the pool alike), D = 64 | 128 and a page size of 16, 32, 64, 128 or 256; "
                 "got dtype=%s D=%d page_size=%d (an e4m3 pool: fa_fwd_decode_paged)", fn, fa_dtype_name(dtype), D, page_size);
   if (max_seqlen_q > total_q)
     return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen_q=%d exceeds the token count %d", fn, max_seqlen_q, total_q);
   TRY(varlen_strides_ok(fn, "", D, q_row_stride, q_head_stride, stride_mult(dtype)));
-  TRY(page_pool_ok(fn, D, page_size, max_pages_per_seq, kv_page_stride, kv_head_stride, kv_row_stride, block_table_stride, dtype, block_table, seqlens_k));
+  TRY(page_pool_ok(fn, D, page_size, max_pages_per_seq, kv_page_stride, kv_head_stride, kv_row_stride, block_table_stride, kv_dtype, block_table, seqlens_k));
   TRY(aligned16(fn, "tensors", {q, k_pages, v_pages, o}));
   if ((uintptr_t)cu_seqlens_q & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q must be int32-aligned", fn);
   TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
   TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));
-  const int route = sinks ? WIN_KERNEL : window_route(window_left, window_right);
+  const int route = (sinks || kv8_dtype) ? WIN_KERNEL : window_route(window_left, window_right);
   fa::VarlenPagedSinkParams p;
   p.q = q; p.k = k_pages; p.v = v_pages; p.o = o; p.lse = lse;
   p.B = B; p.H = Hq; p.Hkv = Hkv; p.N = max_seqlen_q; p.Nk = page_size * max_pages_per_seq; p.D = D; p.scale = scale;
@@ -657,8 +667,9 @@ static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages,
   if (route != WIN_KERNEL) return launched(fn, fa::launch_mfma_varlen_paged(p, dtype, (hipStream_t)hip_stream));
   p.wl = window_clamp(window_left, p.Nk);
   p.wr = window_clamp(window_right, max_seqlen_q);
+  p.sinks = sinks ? *sinks : nullptr;
+  if (kv8_dtype) return launched(fn, fa::launch_mfma_varlen_paged_kv8(p, sinks != nullptr, (hipStream_t)hip_stream));
   if (!sinks) return launched(fn, fa::launch_mfma_varlen_paged_window(p, dtype, (hipStream_t)hip_stream));
-  p.sinks = *sinks;
   return launched(fn, fa::launch_mfma_varlen_paged_sink(p, dtype, (hipStream_t)hip_stream));
 }
 int fa_fwd_varlen_paged(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *cu_seqlens_q,
@@ -689,25 +700,72 @@ int fa_fwd_varlen_paged_sink(const void *q, const void *k_pages, const void *v_p
                            max_seqlen_q, D, page_size, num_pages, max_pages_per_seq, scale, q_row_stride, q_head_stride, kv_page_stride,
                            kv_head_stride, kv_row_stride, block_table_stride, window_left, window_right, dtype, hip_stream, &sinks);
 }
+int fa_fwd_varlen_paged_kv8_supported(int q_dtype, int kv_dtype, int D, int page_size) {
+  return fa::mfma_varlen_paged_kv8_supported(q_dtype, kv_dtype, D, page_size);
+}
+int fa_fwd_varlen_paged_kv8(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *cu_seqlens_q,
+                            const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                            int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride,
+                            long long q_head_stride, long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                            long long block_table_stride, int window_left, int window_right, const float *sinks, int q_dtype, int kv_dtype,
+                            void *hip_stream) {
+  // sinks may be NULL here: the call without a sink term (a non-NULL pointer is held to sinks_ok)
+  return varlen_paged_impl("fa_fwd_varlen_paged_kv8", q, k_pages, v_pages, o, lse, cu_seqlens_q, block_table, seqlens_k, B, Hq, Hkv, total_q,
+                           max_seqlen_q, D, page_size, num_pages, max_pages_per_seq, scale, q_row_stride, q_head_stride, kv_page_stride,
+                           kv_head_stride, kv_row_stride, block_table_stride, window_left, window_right, q_dtype, hip_stream,
+                           sinks ? &sinks : nullptr, &kv_dtype);
+}
+
+// fa_kv_append_paged and fa_kv_append_paged_quant: one path. quant: `dtype` is the new rows' (f16 / bf16), the pools are e4m3
+static int kv_append_impl(const char *fn, const void *k_new, const void *v_new, void *k_pages, void *v_pages, const int *cu_seqlens_new,
+                          const int *block_table, const int *seqlens_k, int B, int Hkv, int total_new, int max_seqlen_new, int D,
+                          int page_size, int num_pages, int max_pages_per_seq, long long new_row_stride, long long new_head_stride,
+                          long long kv_page_stride, long long kv_head_stride, long long kv_row_stride, long long block_table_stride,
+                          int dtype, bool quant, float k_mul, float v_mul, void *hip_stream);
 
 int fa_kv_append_paged(const void *k_new, const void *v_new, void *k_pages, void *v_pages, const int *cu_seqlens_new, const int *block_table,
                        const int *seqlens_k, int B, int Hkv, int total_new, int max_seqlen_new, int D, int page_size, int num_pages,
                        int max_pages_per_seq, long long new_row_stride, long long new_head_stride, long long kv_page_stride,
                        long long kv_head_stride, long long kv_row_stride, long long block_table_stride, int dtype, void *hip_stream) {
+  return kv_append_impl("fa_kv_append_paged", k_new, v_new, k_pages, v_pages, cu_seqlens_new, block_table, seqlens_k, B, Hkv, total_new,
+                        max_seqlen_new, D, page_size, num_pages, max_pages_per_seq, new_row_stride, new_head_stride, kv_page_stride,
+                        kv_head_stride, kv_row_stride, block_table_stride, dtype, false, 1.0f, 1.0f, hip_stream);
+}
+int fa_kv_append_paged_quant(const void *k_new, const void *v_new, void *k_pages, void *v_pages, const int *cu_seqlens_new,
+                             const int *block_table, const int *seqlens_k, int B, int Hkv, int total_new, int max_seqlen_new, int D,
+                             int page_size, int num_pages, int max_pages_per_seq, long long new_row_stride, long long new_head_stride,
+                             long long kv_page_stride, long long kv_head_stride, long long kv_row_stride, long long block_table_stride,
+                             int new_dtype, float k_mul, float v_mul, void *hip_stream) {
+  return kv_append_impl("fa_kv_append_paged_quant", k_new, v_new, k_pages, v_pages, cu_seqlens_new, block_table, seqlens_k, B, Hkv, total_new,
+                        max_seqlen_new, D, page_size, num_pages, max_pages_per_seq, new_row_stride, new_head_stride, kv_page_stride,
+                        kv_head_stride, kv_row_stride, block_table_stride, new_dtype, true, k_mul, v_mul, hip_stream);
+}
+static int kv_append_impl(const char *fn, const void *k_new, const void *v_new, void *k_pages, void *v_pages, const int *cu_seqlens_new,
+                          const int *block_table, const int *seqlens_k, int B, int Hkv, int total_new, int max_seqlen_new, int D,
+                          int page_size, int num_pages, int max_pages_per_seq, long long new_row_stride, long long new_head_stride,
+                          long long kv_page_stride, long long kv_head_stride, long long kv_row_stride, long long block_table_stride,
+                          int dtype, bool quant, float k_mul, float v_mul, void *hip_stream) {
   g_err[0] = 0;
-  const char *fn = "fa_kv_append_paged";
   TRY(nonnull(fn, {k_new, v_new, k_pages, v_pages, cu_seqlens_new, block_table, seqlens_k}));
   TRY(positive(fn, {B, Hkv, total_new, max_seqlen_new, D, page_size, num_pages, max_pages_per_seq}));
-  const int bytes = fa_dtype_in_bytes(dtype);
-  if ((dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_FP8_E4M3) || ((long long)D * bytes) % 16 || !fa::page_size_ok(page_size))
-    return fail(FA_ERR_UNSUPPORTED, "fa_kv_append_paged: needs f16 / bf16 / fp8_e4m3, rows of whole 16-byte chunks and a page size of 16, 32, 64, 128 "
-                "or 256; got dtype=%s D=%d page_size=%d", fa_dtype_name(dtype), D, page_size);
+  const int pool_dtype = quant ? FA_DTYPE_FP8_E4M3 : dtype;
+  const int bytes = fa_dtype_in_bytes(pool_dtype);
+  if (quant) {
+    if ((dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16) || D % 16 || !fa::page_size_ok(page_size))
+      return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 new rows (the pools are fp8_e4m3), rows of whole 16-byte chunks and a page size of "
+                  "16, 32, 64, 128 or 256; got new_dtype=%s D=%d page_size=%d", fn, fa_dtype_name(dtype), D, page_size);
+    // (the negated form refuses NaN as well)
+    if (!(k_mul > 0.0f && k_mul <= 3.4028234663852886e38f) || !(v_mul > 0.0f && v_mul <= 3.4028234663852886e38f))
+      return fail(FA_ERR_INVALID_ARG, "%s: k_mul=%g and v_mul=%g must be > 0 and finite", fn, (double)k_mul, (double)v_mul);
+  } else if ((dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_FP8_E4M3) || ((long long)D * bytes) % 16 || !fa::page_size_ok(page_size))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 / fp8_e4m3, rows of whole 16-byte chunks and a page size of 16, 32, 64, 128 "
+                "or 256; got dtype=%s D=%d page_size=%d", fn, fa_dtype_name(dtype), D, page_size);
   if (max_seqlen_new > total_new)
-    return fail(FA_ERR_INVALID_ARG, "fa_kv_append_paged: max_seqlen_new=%d exceeds the token count %d", max_seqlen_new, total_new);
+    return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen_new=%d exceeds the token count %d", fn, max_seqlen_new, total_new);
   TRY(varlen_strides_ok(fn, "new key/value ", D, new_row_stride, new_head_stride, stride_mult(dtype)));
-  TRY(page_pool_ok(fn, D, page_size, max_pages_per_seq, kv_page_stride, kv_head_stride, kv_row_stride, block_table_stride, dtype, block_table, seqlens_k));
+  TRY(page_pool_ok(fn, D, page_size, max_pages_per_seq, kv_page_stride, kv_head_stride, kv_row_stride, block_table_stride, pool_dtype, block_table, seqlens_k));
   TRY(aligned16(fn, "tensors", {k_new, v_new, k_pages, v_pages}));
-  if ((uintptr_t)cu_seqlens_new & 3) return fail(FA_ERR_INVALID_ARG, "fa_kv_append_paged: cu_seqlens_new must be int32-aligned");
+  if ((uintptr_t)cu_seqlens_new & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_new must be int32-aligned", fn);
   const long long nblk = (max_seqlen_new + fa::APPEND_ROWS - 1) / fa::APPEND_ROWS;
   if (Hkv > 65535 || (long long)B * nblk > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
   fa::AppendPagedParams p;
@@ -718,6 +776,7 @@ int fa_kv_append_paged(const void *k_new, const void *v_new, void *k_pages, void
   p.page_stride = kv_page_stride; p.head_stride = kv_head_stride; p.row_stride = kv_row_stride;
   p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
   p.lp = log2_of(page_size);
+  if (quant) return launched(fn, fa::launch_kv_append_paged_quant(p, dtype, k_mul, v_mul, (hipStream_t)hip_stream));
   return launched(fn, fa::launch_kv_append_paged(p, bytes, (hipStream_t)hip_stream));
 }
 

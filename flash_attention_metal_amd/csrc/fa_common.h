@@ -115,6 +115,12 @@ struct VarlenPagedSinkParams : VarlenPagedWindowParams {
   const float *sinks;  // [H]
 };
 
+// the KV8 modes of the paged window / sink modes (fa_fwd_varlen_paged_kv8; include/fa_mi355.h, "e4m3 pools in the prefill"): the same
+// parameters over pools of OCP e4m3 bytes -- page_stride, kv_head_stride and kv_rs count elements of ONE byte. Types of their own, because
+// the kernel body picks the register staging with the widening by the parameter type.
+struct VarlenPagedKv8Params : VarlenPagedWindowParams {};
+struct VarlenPagedKv8SinkParams : VarlenPagedSinkParams {};
+
 // one fa_fwd_decode call (csrc/fa_decode_kernel.hip)
 struct DecodeParams {
   const void *q, *k, *v;
@@ -171,6 +177,9 @@ hipError_t launch_mfma_varlen_window(const VarlenWindowParams &p, int dtype, hip
 hipError_t launch_mfma_varlen_paged_window(const VarlenPagedWindowParams &p, int dtype, hipStream_t s);
 hipError_t launch_mfma_varlen_sink(const VarlenSinkParams &p, int dtype, hipStream_t s);
 hipError_t launch_mfma_varlen_paged_sink(const VarlenPagedSinkParams &p, int dtype, hipStream_t s);
+// fa_fwd_varlen_paged_kv8: bf16 queries on e4m3 pools, always the KV8 window-mode kernels (with_sink: p.sinks is read, their sink mode)
+hipError_t launch_mfma_varlen_paged_kv8(const VarlenPagedSinkParams &p, bool with_sink, hipStream_t s);
+bool mfma_varlen_paged_kv8_supported(int q_dtype, int kv_dtype, int D, int page_size);
 // fa_kv_append_paged (csrc/fa_decode_kernel.hip): a byte copy of new K / V rows into their slots of the page pools
 struct AppendPagedParams {
   const void *k_new, *v_new;
@@ -183,6 +192,9 @@ struct AppendPagedParams {
 };
 constexpr int APPEND_ROWS = 16;  // new rows per workgroup of the append kernel
 hipError_t launch_kv_append_paged(const AppendPagedParams &p, int elem_bytes, hipStream_t s);
+// fa_kv_append_paged_quant: the same placement with 16-bit new rows (new_dtype f16 / bf16) quantised into e4m3 pools,
+// byte = e4m3_rne(clamp(fp32(x) * mul, -448, 448))
+hipError_t launch_kv_append_paged_quant(const AppendPagedParams &p, int new_dtype, float k_mul, float v_mul, hipStream_t s);
 hipError_t launch_mfma_split2(const Params &p, int dtype, hipStream_t s);
 bool mfma_split2_supported(int dtype, int D);
 hipError_t launch_mfma_h64s2(const Params &p, int dtype, hipStream_t s);

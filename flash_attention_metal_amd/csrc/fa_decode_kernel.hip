@@ -714,6 +714,64 @@ __global__ __launch_bounds__(256) void kv_append_paged_kernel(AppendPagedParams 
   }
 }
 
+// fa_kv_append_paged_quant: the same placement -- sequence lookup, clamps, skipped positions, grid: the lines of the kernel above -- with
+// 16-bit new rows (T = _Float16 / __bf16) quantised into e4m3 pools. A lane takes 16 elements: two 16-byte loads, one 16-byte store.
+// byte = e4m3_rne(clamp(fp32(x) * mul, -448, 448)): ONE fp32 multiply, the clamp BEFORE the conversion (v_cvt_pk_fp8_f32 gives NaN above
+// 448 instead of saturating, see fa_fp8_kernel.hip), the conversion rounds to nearest even, subnormals included, and keeps the sign of -0.
+template <typename T>
+__device__ __forceinline__ u32x4 quant16_e4m3(u32x4 a, u32x4 b, float mul) {
+  u32x4 out;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned w0 = j < 2 ? a[2 * j] : b[2 * j - 4], w1 = j < 2 ? a[2 * j + 1] : b[2 * j - 3];
+    float f[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const unsigned short h = (unsigned short)((e < 2 ? w0 : w1) >> (16 * (e & 1)));
+      f[e] = fminf(fmaxf((float)__builtin_bit_cast(T, h) * mul, -448.0f), 448.0f);
+    }
+    int w;
+    asm volatile("" : "=v"(w));  // (the first conversion keeps the other half of its destination: start from an undefined register)
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
+    out[j] = (unsigned)w;
+  }
+  return out;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void kv_quant_append_paged_kernel(AppendPagedParams p, float k_mul, float v_mul) {
+  const int nblk = (p.max_new + APPEND_ROWS - 1) / APPEND_ROWS;
+  const int b = (int)blockIdx.x / nblk, rb = (int)blockIdx.x - b * nblk, hk = blockIdx.y;
+  const int s0 = min(max(p.cu_new[b], 0), p.total_new), e0 = min(max(p.cu_new[b + 1], 0), p.total_new);
+  const int n = min(max(e0 - s0, 0), p.max_new);
+  const long long first = (long long)p.seqlens[b] - n;  // key position of the sequence's first new token
+  const long long cap = (long long)p.max_pages << p.lp;
+  const int cpr = p.D / 16;  // 16-byte chunks per row of the POOL (16 elements: 32 bytes of the new row)
+  const int *tbl = p.block_table + (long long)b * p.bt_stride;
+  for (int idx = threadIdx.x; idx < APPEND_ROWS * cpr; idx += 256) {
+    const int i = rb * APPEND_ROWS + idx / cpr, c = idx % cpr;
+    if (i >= n) continue;
+    const long long pos = first + i;
+    if (pos < 0 || pos >= cap) continue;
+    const int page = tbl[(int)(pos >> p.lp)];
+    if ((unsigned)page >= (unsigned)p.num_pages) continue;
+    const long long src = ((long long)(s0 + i) * p.new_rs + (long long)hk * p.new_hs) * 2 + 32 * c;
+    const long long dst = (long long)page * p.page_stride + (long long)hk * p.head_stride + (pos & ((1 << p.lp) - 1)) * p.row_stride + 16 * c;
+    const u32x4 k0 = *reinterpret_cast<const u32x4 *>((const char *)p.k_new + src), k1 = *reinterpret_cast<const u32x4 *>((const char *)p.k_new + src + 16);
+    const u32x4 v0 = *reinterpret_cast<const u32x4 *>((const char *)p.v_new + src), v1 = *reinterpret_cast<const u32x4 *>((const char *)p.v_new + src + 16);
+    *reinterpret_cast<u32x4 *>((char *)p.k_pages + dst) = quant16_e4m3<T>(k0, k1, k_mul);
+    *reinterpret_cast<u32x4 *>((char *)p.v_pages + dst) = quant16_e4m3<T>(v0, v1, v_mul);
+  }
+}
+
+hipError_t launch_kv_append_paged_quant(const AppendPagedParams &p, int new_dtype, float k_mul, float v_mul, hipStream_t s) {
+  const int nblk = (p.max_new + APPEND_ROWS - 1) / APPEND_ROWS;
+  (void)hipGetLastError();
+  if (new_dtype == FA_DTYPE_F16) hipLaunchKernelGGL(kv_quant_append_paged_kernel<_Float16>, dim3(p.B * nblk, p.Hkv), dim3(256), 0, s, p, k_mul, v_mul);
+  else hipLaunchKernelGGL(kv_quant_append_paged_kernel<__bf16>, dim3(p.B * nblk, p.Hkv), dim3(256), 0, s, p, k_mul, v_mul);
+  return hipGetLastError();
+}
+
 hipError_t launch_kv_append_paged(const AppendPagedParams &p, int elem_bytes, hipStream_t s) {
   const int nblk = (p.max_new + APPEND_ROWS - 1) / APPEND_ROWS;
   (void)hipGetLastError();

@@ -120,7 +120,14 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   // SINK (PT = VarlenSinkParams / VarlenPagedSinkParams; fa_fwd_varlen_sink, fa_fwd_varlen_paged_sink): window mode with one more term in
   // every row's denominator, exp(sinks[head]), which carries no value. The tile loop does not know of it: the logit is one wave-uniform
   // scalar load per block, turned to log2 units, and the epilogue folds it into (m, l) by the larger of the row's reference and the sink.
-  constexpr bool SINK = std::is_same<PT, VarlenSinkParams>::value || std::is_same<PT, VarlenPagedSinkParams>::value;
+  constexpr bool SINK = std::is_same<PT, VarlenSinkParams>::value || std::is_base_of<VarlenPagedSinkParams, PT>::value;
+  // KV8 (PT = VarlenPagedKv8Params / VarlenPagedKv8SinkParams; fa_fwd_varlen_paged_kv8): the paged window / sink mode over pools of OCP
+  // e4m3 bytes. K and V tiles cannot travel by LDS-DMA (the LDS image is bf16): every thread loads NCH 16-byte chunks (16 elements) of
+  // K and of V into registers through the page's range-checked descriptor, and writes each, widened exactly by fp8x8_to_bf16, as the two
+  // bf16 chunks it stands for in the SAME swizzled images. The two LDS buffers and everything from LDS onwards are the bf16 kernel's, so
+  // the results are bit for bit those of the paged window / sink kernels on the widened pool.
+  constexpr bool KV8 = std::is_same<PT, VarlenPagedKv8Params>::value || std::is_same<PT, VarlenPagedKv8SinkParams>::value;
+  static_assert(!KV8 || std::is_same<Tag, BF16>::value, "KV8 mode: bf16 queries, e4m3 pools widened to bf16");
   static_assert(!WINDOW || CAUSAL, "window mode: the upper bound is the causal one with its own offset");
   static_assert(!VARLEN || (SPLIT == 1 && ROWS == BM && PRESC && !std::is_same<Tag, FP8>::value && (D == 64 || D == 128)),
                 "varlen mode: the plain 128-row kernel, 16-bit inputs, LDS-DMA staging");
@@ -138,7 +145,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   constexpr int TILE = BN * RB;             // bytes of one K (or V) tile in LDS
   constexpr bool IS_FP8 = std::is_same<Tag, FP8>::value;  // Q,K,V are e4m3 in HBM, bf16 from LDS onwards
   constexpr int GB = IS_FP8 ? 1 : 2;        // bytes per element in HBM
-  constexpr int GRB = D * GB;               // global row bytes
+  constexpr int GRB = KV8 ? D : D * GB;     // global row bytes (of a K / V row; the dense modes: of a Q row too)
   constexpr int GTILE = BN * GRB;           // global bytes of one K (or V) tile
   constexpr int NCH = BN * (GRB / 16) / ST;  // staged 16-byte global chunks per thread per tile
   // (varlen without the mask keeps the prefetch and three workgroups: at 128 registers its extra row pitch and sequence base spill 20 B,
@@ -212,7 +219,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
     lse_base = (long long)hq * p.total_q + sq;
     if constexpr (SINK) sink = p.sinks[hq];
     qrb = (unsigned)p.q_rs * 2;
-    kvrb = (unsigned)p.kv_rs * 2;
+    kvrb = (unsigned)p.kv_rs * (KV8 ? 1 : 2);
     // no key is visible to any row of the block (no keys at all, or causal with Lk < Lq: key j is visible to query i iff
     // j <= i + Lk - Lq): O = 0, LSE = -inf, as the paged decode defines it
     // (window mode: the block's rows see keys [k_lo, kv_hi) together; none when the range is empty: kv_hi = 0 then)
@@ -318,7 +325,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
     st_g[i] = (VARLEN ? (int)(row * kvrb) : row * GRB) + gch * 16;
     const int skx = (D == 32) ? ((row >> 2) & 3) : (D == 64) ? ((row >> 1) & 7) : (row & 15);
     const int svx = (D == 32) ? 0 : (D == 64) ? (((row >> 1) & 1) << 2) : ((row & 3) << 2);
-    const int ch = IS_FP8 ? 2 * gch : gch;
+    const int ch = (IS_FP8 || KV8) ? 2 * gch : gch;
     st_v[i] = row * RB + ((ch ^ svx) << 4);
     if constexpr (IS_FP8) {
       const int skx8 = (D == 64) ? ((row >> 2) & 3) : (D == 128) ? ((row >> 1) & 7) : (row & 15);
@@ -326,7 +333,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
       st_k1[i] = 0;
       st_v1[i] = row * RB + (((ch + 1) ^ svx) << 4);
     } else {
-      st_k[i] = row * RB + ((ch ^ skx) << 4);
+      st_k[i] = row * RB + ((ch ^ skx) << 4);  // (KV8: K is widened as well; chunk 2c + 1 of either image is the address of 2c XOR 16)
     }
   }
 
@@ -337,7 +344,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
 
   // LDS-DMA staging (FA_MFMA_DMA): wave w of a split moves the 1-KiB pieces w, w + RW, ... of each tile; inside a piece the
   // LDS image is lane-linear, so the chunk swizzle sits on the SOURCE address (one per-lane offset for K, one for V)
-  constexpr bool DMA = (FA_MFMA_DMA != 0) && !IS_FP8 && (D == 32 || D == 64 || D == 128);
+  constexpr bool DMA = (FA_MFMA_DMA != 0) && !IS_FP8 && !KV8 && (D == 32 || D == 64 || D == 128);
   constexpr int RPP = 1024 / RB;                 // rows per piece
   constexpr int NPW = (BN / RPP) / RW;           // pieces per wave, tile and operand
   unsigned dma_kvo = 0, dma_vvo = 0;
@@ -359,9 +366,17 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   // drain the K / V pieces that have just been issued, in front of the tile's MFMAs. A piece starts at key t * BN + (wave + RW * j) * RPP;
   // the index never leaves the row's max_pages entries (a tile may reach past the capacity: those pieces have no valid row and read as
   // zeros whatever the entry says).
+  // KV8 mode: the same one tile ahead for the wave's NCH register loads of a tile. Load i of a wave covers the 64 chunks wave * 64 +
+  // i * ST .., i.e. RPL = 64 / GCPR whole rows (16 at head_dim 64, 8 at 128) from row wave * RPL + i * (ST / GCPR) of the tile: aligned to
+  // RPL <= 16 rows, hence inside ONE page, and the descriptor of a load is wave-uniform.
+  constexpr int RPL = 64 / GCPR;
+  const unsigned kv8_vo = KV8 ? (unsigned)(lane / GCPR) * kvrb + (lane % GCPR) * 16 : 0u;  // the lane's chunk inside its load's rows
   int pgv = 0;
   auto fetch_pages = [&](int t) __attribute__((always_inline)) {
-    if constexpr (PAGEDV) {
+    if constexpr (KV8) {
+      const int kp = t * BN + wave * RPL + (lane & (NCH - 1)) * (ST / GCPR);
+      pgv = ptbl[min(kp >> p.lp, p.max_pages - 1)];
+    } else if constexpr (PAGEDV) {
       const int kp = t * BN + (wave + RW * (lane & (NPW - 1))) * RPP;
       pgv = ptbl[min(kp >> p.lp, p.max_pages - 1)];
     }
@@ -422,11 +437,32 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   };
   u32x4 kst[NCH], vst[NCH];
   auto stage_load = [&](int t) {
+    if constexpr (KV8) {
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        // this load's page, as in stage_dma's paged arm: a descriptor on the page's 64-bit base (+ the key head) that ends with the last
+        // valid row's D BYTES (rows >= L_b, and every row of a page index outside the pool, read as zeros: 0 records); the in-page offset
+        // goes into voffset, so no address is formed outside the page's valid rows
+        const int P = 1 << p.lp, kp = t * BN + wave * RPL + i * (ST / GCPR);
+        const int page = __builtin_amdgcn_readlane(pgv, i);
+        const int nv = min(LK - (kp & -P), P);  // valid rows of the page
+        const bool ok = nv > 0 && (unsigned)page < (unsigned)p.num_pages;
+        const long long off = ok ? (long long)page * p.page_stride + base_kv : 0;
+        const unsigned nrec = ok ? (unsigned)(nv - 1) * kvrb + GRB : 0u;
+        const __amdgpu_buffer_rsrc_t rkp = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.k + off), 0, nrec, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rvp = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.v + off), 0, nrec, 0x00020000);
+        const unsigned vo = kv8_vo + (unsigned)(kp & (P - 1)) * kvrb;
+        kst[i] = __builtin_amdgcn_raw_buffer_load_b128(rkp, vo, 0, 0);
+        vst[i] = __builtin_amdgcn_raw_buffer_load_b128(rvp, vo, 0, 0);
+      }
+      fetch_pages(t + 1);  // behind the tile's loads; nothing reads it before the next tile's stage_load
+    } else {
     const unsigned g0 = VARLEN ? (unsigned)t * BN * kvrb : (unsigned)t * GTILE;  // tile t starts at key t*BN
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       if constexpr (!DMA_K8) kst[i] = __builtin_amdgcn_raw_buffer_load_b128(rk, g0 + st_g[i], 0, 0);
       vst[i] = __builtin_amdgcn_raw_buffer_load_b128(rv, g0 + st_g[i], 0, 0);
+    }
     }
   };
   auto stage_write = [&](int buf) {
@@ -436,6 +472,11 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         if constexpr (!DMA_K8) lds_write_b128(Kbuf + buf * KTILE + st_k[i], kst[i]);
         lds_write_b128(Vbuf + buf * TILE + st_v[i], fp8x8_to_bf16(u32x2{vst[i][0], vst[i][1]}));
         lds_write_b128(Vbuf + buf * TILE + st_v1[i], fp8x8_to_bf16(u32x2{vst[i][2], vst[i][3]}));
+      } else if constexpr (KV8) {  // K and V: e4m3 -> bf16 is exact, 16 elements = two bf16 chunks of the row image
+        lds_write_b128(Kbuf + buf * KTILE + st_k[i], fp8x8_to_bf16(u32x2{kst[i][0], kst[i][1]}));
+        lds_write_b128(Kbuf + buf * KTILE + (st_k[i] ^ 16), fp8x8_to_bf16(u32x2{kst[i][2], kst[i][3]}));
+        lds_write_b128(Vbuf + buf * TILE + st_v[i], fp8x8_to_bf16(u32x2{vst[i][0], vst[i][1]}));
+        lds_write_b128(Vbuf + buf * TILE + (st_v[i] ^ 16), fp8x8_to_bf16(u32x2{vst[i][2], vst[i][3]}));
       } else {
         lds_write_b128(Kbuf + buf * KTILE + st_k[i], kst[i]);
         lds_write_b128(Vbuf + buf * TILE + st_v[i], vst[i]);
@@ -465,7 +506,8 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   } else {
     if constexpr (DMA_K8) stage_dma_k8(sp, 0);
-    stage_load(sp);  // this split's first tile (past the end of a short head: zeros through the descriptor, never used)
+    if constexpr (KV8) fetch_pages(tb);
+    stage_load(KV8 ? tb : sp);  // this split's first tile (past the end of a short head: zeros through the descriptor, never used)
     stage_write(0);
     if constexpr (DMA_K8) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
@@ -921,6 +963,17 @@ __global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_sink_pag
   fwd_mfma_body<Tag, D, true, 1, true, BM, VarlenPagedSinkParams>(p);
 }
 
+// fa_fwd_varlen_paged_kv8: the paged window / sink kernels in KV8 mode (bf16 queries, e4m3 pools), at their occupancy: the 8 / 16 staging
+// registers fit (168 / 222 VGPR, no scratch)
+template <int D>
+__global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_kv8_kernel(VarlenPagedKv8Params p) {
+  fwd_mfma_body<BF16, D, true, 1, true, BM, VarlenPagedKv8Params>(p);
+}
+template <int D>
+__global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_kv8_sink_kernel(VarlenPagedKv8SinkParams p) {
+  fwd_mfma_body<BF16, D, true, 1, true, BM, VarlenPagedKv8SinkParams>(p);
+}
+
 // ---------------------------------------------------------------------------
 bool mfma_supported(int dtype, int D) {
   if (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) return D == 32 || D == 64 || D == 96 || D == 128 || D == 256;
@@ -997,6 +1050,26 @@ hipError_t launch_mfma_varlen_sink(const VarlenSinkParams &p, int dtype, hipStre
 hipError_t launch_mfma_varlen_paged_sink(const VarlenPagedSinkParams &p, int dtype, hipStream_t s) {
   return with_tag(dtype, [&](auto tag) {
     return with_dim<64, 128>(p.D, [&](auto d) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_sink_paged_kernel<decltype(tag), d()>, p, s); });
+  });
+}
+
+bool mfma_varlen_paged_kv8_supported(int q_dtype, int kv_dtype, int D, int page_size) {
+  return q_dtype == FA_DTYPE_BF16 && kv_dtype == FA_DTYPE_FP8_E4M3 && (D == 64 || D == 128) && page_size_ok(page_size);
+}
+
+// (causal_head_group sized for rows of one byte: the issue order only, never the results)
+hipError_t launch_mfma_varlen_paged_kv8(const VarlenPagedSinkParams &p, bool with_sink, hipStream_t s) {
+  return with_dim<64, 128>(p.D, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    const int hg = causal_head_group(p, D, 1);
+    if (with_sink) {
+      VarlenPagedKv8SinkParams pk;
+      static_cast<VarlenPagedSinkParams &>(pk) = p;
+      return launch_blocks(fwd_mfma_kv8_sink_kernel<D>, pk, BM, NTHREADS, mfma_lds_bytes<BF16, D>(), hg, s);
+    }
+    VarlenPagedKv8Params pk;
+    static_cast<VarlenPagedWindowParams &>(pk) = p;
+    return launch_blocks(fwd_mfma_kv8_kernel<D>, pk, BM, NTHREADS, mfma_lds_bytes<BF16, D>(), hg, s);
   });
 }
 

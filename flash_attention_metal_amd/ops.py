@@ -411,6 +411,10 @@ def varlen_paged_supported(dtype: str, D: int, page_size: int) -> bool:
     return bool(load_library().fa_fwd_varlen_paged_supported(DTYPES[dtype], D, int(page_size)))
 
 
+def varlen_paged_kv8_supported(q_dtype: str, kv_dtype: str, D: int, page_size: int) -> bool:
+    return bool(load_library().fa_fwd_varlen_paged_kv8_supported(DTYPES[q_dtype], DTYPES[kv_dtype], D, int(page_size)))
+
+
 def _pool(entry: str, k_pages: torch.Tensor, v_pages: torch.Tensor, layout: str):
     """(num_pages, Hkv, P, D, page stride, head stride, row stride) of a pool pair in layout HND / NHD."""
     if k_pages.dim() != 4 or k_pages.shape != v_pages.shape:
@@ -466,7 +470,10 @@ def flash_attention_varlen_paged(
     past cu_seqlens_q[B] and rows beyond max_seqlen_q of a sequence are not written. An inference path: no torch custom op and no
     backward. window=(left, right): a sliding window as in flash_attention_varlen, with seqlens_k[b] in Lk_b's place
     (fa_fwd_varlen_paged_window); None: the call above, untouched. sinks: [Hq] per-head sink logits as in flash_attention_varlen
-    (fa_fwd_varlen_paged_sink); None: the calls above, untouched. Returns (out, lse): out like q, lse [Hq, total_q]."""
+    (fa_fwd_varlen_paged_sink); None: the calls above, untouched. bf16 q on float8_e4m3fn pools (fa_fwd_varlen_paged_kv8, "e4m3 pools in
+    the prefill"): the pool of flash_attention_decode_paged, read as plain e4m3 values -- no scales: fold a K scale into `scale`, a V scale
+    into what consumes `out`; window, is_causal and sinks mean what they mean with sinks, and the result is bit for bit the bf16 call on
+    the widened pool. Returns (out, lse): out like q, lse [Hq, total_q]."""
     lib = load_library()
     entry = "flash_attention_varlen_paged"
     if q.dim() != 3:
@@ -475,8 +482,10 @@ def flash_attention_varlen_paged(
     total_q, Hq, D = q.shape
     if Dk != D or Hkv < 1 or Hq % Hkv:
         raise ValueError(f"incompatible q {tuple(q.shape)} and pools {tuple(k_pages.shape)} (same D, Hq % Hkv == 0)")
-    if q.dtype not in (torch.float16, torch.bfloat16) or k_pages.dtype != q.dtype:
-        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k_pages.dtype} {v_pages.dtype} (f16 or bf16, q and the pools alike)")
+    kv8 = _FP8 is not None and q.dtype == torch.bfloat16 and k_pages.dtype == _FP8
+    if not kv8 and (q.dtype not in (torch.float16, torch.bfloat16) or k_pages.dtype != q.dtype):
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k_pages.dtype} {v_pages.dtype} (f16 or bf16, q and the pools alike; or bf16 q "
+                         "on float8_e4m3fn pools)")
     if q.stride(2) != 1:
         raise ValueError("q needs a unit element stride (a head of a token is D contiguous elements)")
     B = _tables(entry, cu_seqlens_q, "cu_seqlens_q", block_table, seqlens_k)
@@ -495,10 +504,14 @@ def flash_attention_varlen_paged(
     if sinks is not None:
         sinks = _sinks(sinks, Hq, q.device)
         entry, mask = "fa_fwd_varlen_paged_sink", _sink_window(window, is_causal) + (sinks.data_ptr(),)
+    dtypes = (_TORCH2FA[q.dtype],)
+    if kv8:  # one entry point with or without sinks; the mask as the sink path maps it
+        entry, mask = "fa_fwd_varlen_paged_kv8", _sink_window(window, is_causal) + (_ptr(sinks),)
+        dtypes = (_TORCH2FA[q.dtype], _TORCH2FA[k_pages.dtype])
     _call(lib, entry,
           (q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), block_table.data_ptr(),
            seqlens_k.data_ptr(), B, Hq, Hkv, total_q, int(max_seqlen_q), D, P, num_pages, block_table.shape[1], _scale(scale, D),
-           q.stride(0), q.stride(1), ps, hs, rs, block_table.stride(0), *mask, _TORCH2FA[q.dtype]), q.device, stream)
+           q.stride(0), q.stride(1), ps, hs, rs, block_table.stride(0), *mask, *dtypes), q.device, stream)
     return out, lse
 
 
@@ -513,29 +526,39 @@ def kv_append_paged(
     max_seqlen_new: int,
     layout: str = "HND",
     stream: Optional[int] = None,
+    k_mul: float = 1.0,
+    v_mul: float = 1.0,
 ) -> None:
     """Write new K / V rows into the page pools, in place (include/fa_mi355.h fa_kv_append_paged): k_new / v_new [total_new, Hkv, D] views
     with one set of strides, f16 / bf16 / e4m3 like the pools; token i of sequence b (tokens cu_seqlens_new[b] .. cu_seqlens_new[b+1)) goes to
     key position seqlens_k[b] - n_b + i, i.e. seqlens_k holds the lengths AFTER the append -- the table flash_attention_varlen_paged and
     flash_attention_decode_paged then read. Positions outside the capacity or on table entries outside the pool are skipped; nothing else
-    is written. Nothing here synchronises or reads device values: graph-capturable. An inference path: no torch custom op, no backward."""
+    is written. Nothing here synchronises or reads device values: graph-capturable. An inference path: no torch custom op, no backward.
+    f16 / bf16 new rows with float8_e4m3fn pools: the quantising append (fa_kv_append_paged_quant), every element stored as
+    e4m3_rne(clamp(fp32(x) * mul, -448, 448)) with mul = k_mul / v_mul (> 0, finite; host scalars), placed by the same rules. Equal dtypes
+    stay the byte copy, which takes no multipliers (anything but 1.0 is refused there)."""
     lib = load_library()
     entry = "kv_append_paged"
     num_pages, Hkv, P, D, ps, hs, rs = _pool(entry, k_pages, v_pages, layout)
     if k_new.dim() != 3 or k_new.shape != v_new.shape or k_new.shape[1:] != (Hkv, D):
         raise ValueError(f"k_new / v_new one [total_new,Hkv,D] shape matching the pools, got {tuple(k_new.shape)} {tuple(v_new.shape)} "
                          f"for pools {tuple(k_pages.shape)}")
-    if k_pages.dtype not in (torch.float16, torch.bfloat16, _FP8) or k_new.dtype != k_pages.dtype or v_new.dtype != k_pages.dtype:
-        raise ValueError(f"unsupported / mixed dtypes {k_new.dtype} {v_new.dtype} {k_pages.dtype} (f16 / bf16 / e4m3, new rows and pools alike)")
+    quant = _FP8 is not None and k_pages.dtype == _FP8 and k_new.dtype in (torch.float16, torch.bfloat16) and v_new.dtype == k_new.dtype
+    if not quant and (float(k_mul) != 1.0 or float(v_mul) != 1.0):
+        raise ValueError("k_mul / v_mul belong to the quantising append (16-bit new rows, float8_e4m3fn pools): the byte copy has none")
+    if not quant and (k_pages.dtype not in (torch.float16, torch.bfloat16, _FP8) or k_new.dtype != k_pages.dtype or v_new.dtype != k_pages.dtype):
+        raise ValueError(f"unsupported / mixed dtypes {k_new.dtype} {v_new.dtype} {k_pages.dtype} (f16 / bf16 / e4m3, new rows and pools alike; "
+                         "or f16 / bf16 new rows into e4m3 pools)")
     if k_new.stride(2) != 1 or v_new.stride() != k_new.stride():
         raise ValueError("k_new and v_new need a unit element stride and one set of row/head strides")
     B = _tables(entry, cu_seqlens_new, "cu_seqlens_new", block_table, seqlens_k)
     if not all(t.is_cuda and t.device == k_pages.device for t in (k_new, v_new, k_pages, v_pages, cu_seqlens_new, block_table, seqlens_k)):
         raise RuntimeError("kv_append_paged needs the new rows, the pools and the tables on one device: there is no CPU path")
-    _call(lib, "fa_kv_append_paged",
+    tail = (_TORCH2FA[k_new.dtype], float(k_mul), float(v_mul)) if quant else (_TORCH2FA[k_pages.dtype],)
+    _call(lib, "fa_kv_append_paged_quant" if quant else "fa_kv_append_paged",
           (k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), cu_seqlens_new.data_ptr(), block_table.data_ptr(),
            seqlens_k.data_ptr(), B, Hkv, k_new.shape[0], int(max_seqlen_new), D, P, num_pages, block_table.shape[1], k_new.stride(0),
-           k_new.stride(1), ps, hs, rs, block_table.stride(0), _TORCH2FA[k_pages.dtype]), k_pages.device, stream)
+           k_new.stride(1), ps, hs, rs, block_table.stride(0), *tail), k_pages.device, stream)
 
 
 def varlen_backward_supported(dtype: str, D: int) -> bool:

@@ -279,7 +279,8 @@ int fa_fwd_decode_paged_supported(int q_dtype, int kv_dtype, int D, int Hq, int 
  * exactly and LSE = -inf. The host reads neither table nor the lengths; the grid is B * Hq * ceil(max_seqlen_q / 128) workgroups, so
  * one captured graph serves every step under the same scalars. No workspace and no key split; asynchronous, allocates nothing.
  * f16 / bf16 with q and the pool of the same type, D = 64 | 128, P in {16, 32, 64, 128, 256}: anything else FA_ERR_UNSUPPORTED. An
- * e4m3 pool is out of scope here: the 128-row kernel's varlen mode has no widening stage (fa_fwd_decode_paged takes such pools).
+ * e4m3 pool is out of scope here: the 128-row kernel's varlen mode has no widening stage (fa_fwd_varlen_paged_kv8 below and
+ * fa_fwd_decode_paged take such pools).
  * Null pointers (lse may be NULL), sizes < 1, Hq % Hkv != 0, scale <= 0, bad strides or alignment, max_seqlen_q > total_q,
  * block_table_stride < max_pages_per_seq, a capacity above 2^30, a page of one head at or above 2 GiB,
  * (max_seqlen_q + 128) * q_row_stride * 2 >= 4 GiB or a grid that does not fit an int: FA_ERR_INVALID_ARG before any launch.
@@ -574,6 +575,60 @@ int fa_bwd_varlen_sink(const void *q, const void *k, const void *v, const void *
                        int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
                        long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
                        int window_left, int window_right, const float *sinks, float *dsinks, int dtype, void *hip_stream);
+
+/*
+ * e4m3 pools in the prefill: fa_fwd_varlen_paged_kv8 is fa_fwd_varlen_paged_sink with `int dtype` replaced by `int q_dtype, int kv_dtype`,
+ * for bf16 queries on page pools of OCP e4m3 (e4m3fn) bytes -- the serving layout fa_fwd_decode_paged takes at decode time, here for chunked
+ * prefill, a prompt behind a cached prefix and the verification of many speculated tokens. fa_fwd_varlen_paged_kv8_supported answers 1
+ * for (FA_DTYPE_BF16, FA_DTYPE_FP8_E4M3), D = 64 | 128, P in {16, 32, 64, 128, 256} and 0 for everything else -- (f16, e4m3) and (e4m3,
+ * e4m3) included --, and the call answers FA_ERR_UNSUPPORTED there. fa_fwd_varlen_paged_supported(FA_DTYPE_FP8_E4M3, ...) stays 0 and the
+ * fa_fwd_varlen_paged* calls are untouched.
+ * q and o are bf16 under the q strides and lse is [Hq, total_q] fp32 or NULL, as in fa_fwd_varlen_paged; k_pages / v_pages are e4m3, HND or
+ * NHD; the three kv strides count ELEMENTS (= bytes), are multiples of 16 and at least D (fa_fwd_decode_paged's rule for e4m3 pools); a
+ * page of one head stays below 2 GiB, counted in bytes of 1. `sinks` may be NULL: NULL runs without a sink term, non-NULL has the
+ * semantics of "Attention sinks". (window_left, window_right) follows "Sliding window": (-1, 0) is causal, (-1, -1) full. ROUTING is not by
+ * sign: as the sink forwards do, the call always runs ONE kernel family (the paged window / sink kernels in their KV8 mode, four kernels),
+ * with never-binding bounds clamped on the host. Validation is fa_fwd_varlen_paged_sink's path: every rule the two calls share carries the
+ * same status and the same error text; only the dtype pair and the 16-element stride rule differ.
+ * NO SCALES, as in fa_fwd_decode_kv8: the bytes are read as plain e4m3 values. A caller with a per-tensor K scale folds it into `scale`,
+ * and a V scale into whatever consumes O (fa_kv_append_paged_quant's k_mul / v_mul are their reciprocals).
+ * The result is the bf16 call on the exactly widened pool: for every owned query token O and LSE are BIT-IDENTICAL to the bf16 call on a
+ * bf16 pool that holds the same values widened (same page order and strides in elements, the same slots unused, the same entries out of
+ * range) -- with sinks == NULL fa_fwd_varlen_paged_window routed through the window kernels ((INT_MAX, 0) / (INT_MAX, INT_MAX) where
+ * the sign routing would pick the un-windowed ones), with sinks fa_fwd_varlen_paged_sink. The kernels load e4m3 chunks into registers
+ * through per-page range-checked descriptors, widen them exactly and write the bf16 LDS images of the bf16 kernels; everything from LDS
+ * onwards is the same code. Tolerances, "LSE accuracy", dead rows (O = 0; LSE = -inf, or sinks[h] bit for bit), the clamping of the tables
+ * and graph capturability are inherited unchanged. Slots >= L_b, spare pages and table entries outside [0, num_pages) read as zeros and
+ * touch nothing: the e4m3 NaN bytes 0x7F / 0xFF there are harmless.
+ */
+int fa_fwd_varlen_paged_kv8(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                            const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                            int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                            int page_size, int num_pages, int max_pages_per_seq, float scale,
+                            long long q_row_stride, long long q_head_stride,
+                            long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                            long long block_table_stride, int window_left, int window_right, const float *sinks,
+                            int q_dtype, int kv_dtype, void *hip_stream);
+int fa_fwd_varlen_paged_kv8_supported(int q_dtype, int kv_dtype, int D, int page_size);
+/*
+ * The quantising append: fa_kv_append_paged's argument list with `int dtype` replaced by `int new_dtype` (FA_DTYPE_F16 | FA_DTYPE_BF16, the
+ * type of k_new / v_new; the pools are e4m3) and two host scalars k_mul, v_mul (> 0 and finite, else FA_ERR_INVALID_ARG). Every element
+ * is stored as the byte
+ *     e4m3_rne(clamp(fp32(x) * mul, -448, 448))
+ * -- ONE fp32 multiply; the clamp FIRST (the hardware conversion gives NaN above 448 instead of saturating); round to nearest even,
+ * subnormals included; -0 keeps its sign; inputs must be finite. Placement, skipping, clamping, footprint and grid are
+ * fa_kv_append_paged's, word for word: token i goes to seqlens_k[b] - n_b + i, positions out of capacity or on bad table entries are
+ * skipped, nothing else in the pools is written. New-row strides are multiples of 8 elements, pool strides multiples of 16, D a multiple
+ * of 16; every other rule, status and text is fa_kv_append_paged's. No scales are stored: a caller that quantises with k_mul = 1 / s_k
+ * passes scale * s_k to the attention calls.
+ */
+int fa_kv_append_paged_quant(const void *k_new, const void *v_new, void *k_pages, void *v_pages,
+                             const int *cu_seqlens_new, const int *block_table, const int *seqlens_k,
+                             int B, int Hkv, int total_new, int max_seqlen_new, int D,
+                             int page_size, int num_pages, int max_pages_per_seq,
+                             long long new_row_stride, long long new_head_stride,
+                             long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                             long long block_table_stride, int new_dtype, float k_mul, float v_mul, void *hip_stream);
 
 /* 1 if fa_fwd has a kernel for the combination, else 0 (no GPU needed). */
 int fa_supported(int dtype, int variant, int D);
