@@ -18,8 +18,9 @@
 //     exponent bits decide per tile whether m is stale (threshold 2^4; bf16 at head_dim 128: 2^8), and a stale tile is done again on the
 //     true maxima. bf16 at head_dim 64 and its padded head dims (LAZY):
 //     no per-tile test -- bf16 P' keeps its 8 bits at any scale, so a stale m loses nothing; the row sums the matrix core delivers are
-//     looked at one tile later (one compare), a sum of 2^20 and more takes an exact power of two out of O, the sum and m, and a sum that
-//     left the trusted range (2^64 and more, inf, NaN) makes the workgroup run once more on the exact path (slow mode)
+//     looked at inside the NEXT tile's PV product (one compare in an MFMA gap, the verdict scalar), a sum of 2^20 and more takes an exact
+//     power of two out of O, the sum and m behind that product, and a sum that left the trusted range (2^64 and more, inf, NaN) makes the
+//     workgroup run once more on the exact path (slow mode)
 //   * P^T feeds PV straight from the score registers: the B operand's k index (8g + j) is key 16(j >> 2) + 4g + (j & 3) of a
 //     32-key step, and V^T is read with ds_read_b64_tr_b16 in the same order (V stays row-major in HBM and LDS)
 //   * K/V tiles of 64 keys double-buffered in LDS, global -> LDS by LDS-DMA with the chunk swizzle on the source address;
@@ -55,10 +56,24 @@
                      // test of the packed exponent bits, as f16; 2 = no test at all (TIMING ONLY, the ceiling of 1: wrong for rows that rise)
 #endif
 #ifndef FA16_LAZY_THR
-#define FA16_LAZY_THR 0x1p20f  // LAZY: a row whose sum reached this is renormalised by an exact power of two in front of the next tile
+#define FA16_LAZY_THR 0x1p20f  // LAZY: a row whose sum reached this is renormalised by an exact power of two behind the PV product of the tile that looks at it
 #endif
 #ifndef FA16_LAZY_POISON
 #define FA16_LAZY_POISON 0x1p64f  // LAZY: a row sum at or above this (inf and NaN included) is not trusted: the block runs again in slow mode
+#endif
+#ifndef FA16_LOOK
+#define FA16_LOOK 1  // LAZY, where the row sums are looked at: 1 = in the PV product, behind its first MFMAs (the sums have no pending writer there),
+                     // the repair behind the product's last MFMA; 0 = in front of the tile, directly behind the barrier (round 11's form: a VALU
+                     // read of the youngest matrix results and a branch on it in front of the score MFMAs); 3 = nowhere (TIMING ONLY)
+#endif
+#ifndef FA16_COLD
+#define FA16_COLD 3  // LAZY, what parts the code behind the score MFMAs: 3 = the mask's branch alone, on a scalar sign bit -- slow mode enters the exact
+                     // path at the head of the tile, through the redo flag; 0 = slow mode's exit and the mask's branch one behind the other, the
+                     // mask flag through a VGPR (round 11's form); 2 = 0 without the slow-mode exit (TIMING ONLY)
+#endif
+#ifndef FA16_TAIL
+#define FA16_TAIL 1  // LAZY: 1 = the block's last barrier and the test of the last tile's sums in front of it stand behind the tile loop; 0 = inside
+                     // the last unit, on a condition every tile's tail evaluates (round 11's form)
 #endif
 #ifndef FA16_HALVES
 #define FA16_HALVES 0  // 1: the hot pass works on one 32-key half at a time (16 live score registers instead of 32)
@@ -223,6 +238,9 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
   // (config 4 shard, profiles/r11/ab_lazy.log) -- it keeps the per-tile test.
   constexpr bool LAZY = ONES && std::is_same<Tag, BF16>::value && D == 64 && (FA16_LAZY != 0);
   constexpr bool LAZY_TEST = LAZY && (FA16_LAZY == 1);
+  constexpr bool LOOK_PV = LAZY_TEST && (FA16_LOOK == 1), LOOK_FRONT = LAZY_TEST && (FA16_LOOK == 0);
+  constexpr bool COLD3 = LAZY_TEST && (FA16_COLD == 3);
+  constexpr bool TAIL_OUT = LAZY_TEST && (FA16_TAIL == 1);
   static_assert(4 * SUB * TILE + (LAZY_TEST ? 4 : 0) <= mfma16_lds_bytes<Tag, D, SUB>() && RW * WM * RB <= 4 * SUB * TILE,
                 "the launcher's LDS size covers the K / V buffers, the flag word and the epilogue's O tiles");
   lds_char *poison_flag = smem + 4 * SUB * TILE;  // LAZY: one word behind the K / V buffers, the workgroup's OR of the waves' poison flags
@@ -335,15 +353,21 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
   // the hot pass over NKT key tiles: P = exp2(S') -> pf (and `bits`, or the row sums ls)
   // (LAZY, `leave`: slow mode's way into the exact path -- the pass is left behind its score MFMAs, where the mask's branch already
   // parts the code, and the tile comes back after the true maxima; returns true then)
+  // (COLD3: `masked` is the tile's mask flag as a scalar sign bit and nothing leaves here -- a tile off the diagonal crosses one scalar
+  // compare and branch between its score MFMAs and its exponentials)
   auto hot_group = [&](auto bufc, auto k0c, auto nktc, const int kv0, vec8 (&pf)[NKP][2], unsigned &bits, float (&ls)[2],
-                       const bool leave) __attribute__((always_inline)) -> bool {
+                       const bool leave, const int masked) __attribute__((always_inline)) -> bool {
     constexpr int NKT = decltype(nktc)::value;
     f32x4 s[NKT][2];
     score_group(bufc, k0c, s, negm[0], negm[1]);
-    if constexpr (LAZY_TEST) {
-      if (__builtin_expect(leave, 0)) return true;
+    if constexpr (COLD3) {
+      if (masked < 0) apply_mask(k0c, s, kv0);
+    } else {
+      if constexpr (LAZY_TEST && FA16_COLD != 2) {
+        if (__builtin_expect(leave, 0)) return true;
+      }
+      if (needs_mask(kv0)) apply_mask(k0c, s, kv0);
     }
-    if (needs_mask(kv0)) apply_mask(k0c, s, kv0);
 #if FA16_PRIO
     if constexpr (decltype(k0c)::value + NKT == KT) __builtin_amdgcn_s_setprio(0);
 #endif
@@ -360,13 +384,13 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
     return false;
   };
   // the row maxima of the raw scores of NKT key tiles, into mx[qt] (this lane's keys)
-  auto max_group = [&](auto bufc, auto k0c, auto nktc, const int kv0, float (&mx)[2]) __attribute__((always_inline)) {
+  auto max_group = [&](auto bufc, auto k0c, auto nktc, const int kv0, float (&mx)[2], const int masked) __attribute__((always_inline)) {
     constexpr int NKT = decltype(nktc)::value;
     f32x4 s[NKT][2], zero;
 #pragma unroll
     for (int i = 0; i < 4; ++i) zero[i] = 0.0f;
     score_group(bufc, k0c, s, zero, zero);
-    if (needs_mask(kv0)) apply_mask(k0c, s, kv0);
+    if (COLD3 ? masked < 0 : needs_mask(kv0)) apply_mask(k0c, s, kv0);
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
@@ -409,29 +433,33 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
   constexpr unsigned LAZY_THR_BITS = __builtin_bit_cast(unsigned, (float)FA16_LAZY_THR);
   constexpr unsigned LAZY_POISON_BITS = __builtin_bit_cast(unsigned, (float)FA16_LAZY_POISON);
   static_assert(LAZY_THR_BITS < LAZY_POISON_BITS && LAZY_POISON_BITS < 0x7f800000u, "2^-BIAS << THR < POISON < inf");
-  auto lazy_renormalise = [&]() __attribute__((always_inline)) {
+  // lazy_look: the wave's ballot of "a sum of mine is large" (two VALU; the verdict is scalar). lazy_repair: what a non-zero ballot leads
+  // to, from the sums as they stand THEN -- with the look inside the PV product (LOOK_PV) that is one tile more than the look saw: sums
+  // only grow, so a row the look found large is large or untrusted now, and a row that meanwhile left the trusted range is poisoned, not scaled.
+  auto lazy_look = [&]() __attribute__((always_inline)) -> unsigned long long {
     const unsigned b0 = __builtin_bit_cast(unsigned, lacc[0][0]), b1 = __builtin_bit_cast(unsigned, lacc[1][0]);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(max(b0, b1) >= LAZY_THR_BITS) != 0, 0)) {
+    return __builtin_amdgcn_ballot_w64(max(b0, b1) >= LAZY_THR_BITS);
+  };
+  auto lazy_repair = [&]() __attribute__((always_inline)) {
 #pragma unroll
-      for (int qt = 0; qt < 2; ++qt) {
-        const unsigned a = __builtin_bit_cast(unsigned, lacc[qt][0]) & 0x7fffffffu;
-        const bool bad = a >= LAZY_POISON_BITS;
-        const bool big = !bad && a >= LAZY_THR_BITS;
-        const int e = (int)(a >> 23) - 127;
-        const float sc = big ? __builtin_bit_cast(float, (unsigned)(127 - e) << 23) : 1.0f;
-        const float kf = big ? (float)e : 0.0f;
+    for (int qt = 0; qt < 2; ++qt) {
+      const unsigned a = __builtin_bit_cast(unsigned, lacc[qt][0]) & 0x7fffffffu;
+      const bool bad = a >= LAZY_POISON_BITS;
+      const bool big = !bad && a >= LAZY_THR_BITS;
+      const int e = (int)(a >> 23) - 127;
+      const float sc = big ? __builtin_bit_cast(float, (unsigned)(127 - e) << 23) : 1.0f;
+      const float kf = big ? (float)e : 0.0f;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          lacc[qt][i] *= sc;
-          negm[qt][i] -= kf;
-        }
-        asm volatile("" : "+v"(negm[qt]));
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) oacc[dt][qt][i] *= sc;
-        if (bad) lds_write_b32(poison_flag, 1u);  // (the flag is read behind the tile loop's last barrier)
+      for (int i = 0; i < 4; ++i) {
+        lacc[qt][i] *= sc;
+        negm[qt][i] -= kf;
       }
+      asm volatile("" : "+v"(negm[qt]));
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) oacc[dt][qt][i] *= sc;
+      if (bad) lds_write_b32(poison_flag, 1u);  // (the flag is read behind the tile loop's last barrier)
     }
   };
   constexpr int G = (FA16_HALVES != 0) ? 2 : 1;  // key-tile groups of the hot pass: 1 = all 16 score MFMAs, then the softmax; 2 = per 32-key half
@@ -479,18 +507,39 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
       // over has its largest P' at 2^-3, a sum of 2^-3 at least: the kept first tile is never the weaker of the two.) Ordinary rows
       // (scores around 0) sum to about 8 over 64 keys and never start over; the first rows under the causal mask (fewer than 8
       // visible keys) do, one wave per head.
-      // LAZY (bf16): the hot pass has no test. What the previous tiles summed to is looked at here, once, in front of the tile (common
-      // case: one v_max_u32, one compare, one branch); the pass below runs scores -> mask -> exp2 -> pack -> PV + ones straight through,
-      // and nothing between the score MFMAs and the PV MFMAs waits for a verdict. The way back is left for the first tile (the floor)
-      // and for slow mode (the second run of a poisoned block), which takes it on EVERY tile, on a scalar flag: true maxima first, so
-      // every P' <= 2^-BIAS. (Backward for the reason given above: as a forward `if (slow)` in front of the pass it cost 32-40 B of scratch.)
-      if constexpr (LAZY_TEST && !FIRST) lazy_renormalise();
-      bool redo = FIRST && !ONES;
+      // LAZY (bf16): the hot pass has no test, and nothing between the barrier and the first score MFMA touches a vector register. What
+      // the tiles BEFORE this one summed to is looked at inside this tile's PV product (LOOK_PV: v_max_u32 + v_cmp into an SGPR pair, in
+      // the gap behind the product's first MFMA -- the sums' last writers retired sixteen MFMAs earlier, their next ones follow later in
+      // the product); the repair, if any, runs behind the product's last MFMA, from the sums as they stand then. So a rise in tile t is
+      // answered behind tile t + 1: the answer is exact whenever it comes (sums only grow, a power of two is a power of two), the lag
+      // only decides when a row counts as untrusted -- a sum that goes from below THR past POISON within two tiles (about 44 log2
+      // units) instead of one -- and that costs the workgroup its second run, never a wrong result. (Round 11 looked in front of the
+      // tile: a VALU read of the youngest matrix results and a branch on it directly behind the barrier; profiles/r20.)
+      // The pass below runs scores -> mask -> exp2 -> pack -> PV + ones straight through; between the score MFMAs and the exponentials
+      // it crosses ONE scalar compare and branch (the mask's, COLD3). The way back is left for the first tile (the floor) and for slow
+      // mode (the second run of a poisoned block), which sets the redo flag at the head of EVERY tile: true maxima first, so every
+      // P' <= 2^-BIAS. (In round 11's structure a forward `if (slow)` in front of the pass cost 32-40 B of scratch and slow mode left the
+      // pass behind its score MFMAs instead, a second branch on the common path; with the mask flag scalar and the look out of the
+      // tile's head, entering through the redo flag costs no scratch and no register: tools/resusage.sh, profiles/r20.)
+      if constexpr (LOOK_FRONT && !FIRST) {
+        if (__builtin_expect(lazy_look() != 0, 0)) lazy_repair();
+      }
+      // the tile's mask flag (needs_mask) as a SIGN BIT, scalar end to end: integer arithmetic, pinned -- as the OR of two compares (or
+      // as a 0 / 1 value: hipcc turns the shift back into a select) it is formed in the lane-mask domain and goes through a VGPR
+      // (v_cndmask + v_cmp) in the header of the redo loop
+      int masked = 0;
+      if constexpr (COLD3) {
+        const int to_diagonal = CAUSAL ? (qw0 + coff) - (kv0 + BNK - 1) : 0, to_end = p.Nk - (kv0 + BNK);  // negative: the tile crosses it
+        masked = to_diagonal | to_end;
+        asm volatile("" : "+s"(masked));
+      }
+      unsigned long long look = 0;  // LOOK_PV: the ballot of the look, an SGPR pair across the PV product
+      bool redo = (FIRST && !ONES) || (COLD3 && slow != 0);
       for (;;) {
         if (__builtin_expect(redo, 0)) {
           float mx[2] = {-INFINITY, -INFINITY};
-          max_group(bufc, K0A{}, std::integral_constant<int, KT / 2>{}, kv0, mx);
-          max_group(bufc, K0B{}, std::integral_constant<int, KT / 2>{}, kv0, mx);
+          max_group(bufc, K0A{}, std::integral_constant<int, KT / 2>{}, kv0, mx, masked);
+          max_group(bufc, K0B{}, std::integral_constant<int, KT / 2>{}, kv0, mx, masked);
           new_reference(firstc, mx);
         }
 #if FA16_PRIO
@@ -498,14 +547,14 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
 #endif
         unsigned bits = 0;
         if constexpr (LAZY_TEST) {
-          if (hot_group(bufc, K0A{}, KTG{}, kv0, pf, bits, ls, slow != 0 && !redo)) {
+          if (hot_group(bufc, K0A{}, KTG{}, kv0, pf, bits, ls, !COLD3 && slow != 0 && !redo, masked)) {
             redo = true;
             continue;
           }
         } else {
-          hot_group(bufc, K0A{}, KTG{}, kv0, pf, bits, ls, false);
+          hot_group(bufc, K0A{}, KTG{}, kv0, pf, bits, ls, false, 0);
         }
-        if constexpr (G == 2) hot_group(bufc, K0B{}, KTG{}, kv0, pf, bits, ls, false);
+        if constexpr (G == 2) hot_group(bufc, K0B{}, KTG{}, kv0, pf, bits, ls, false, 0);
         bool stale;
         if constexpr (LAZY) stale = false;  // (the test that is not there; written so that the f16 kernels keep their instructions)
         else if constexpr (ONES) stale = __builtin_amdgcn_ballot_w64((bits & 0x40004000u) != 0) != 0;
@@ -545,12 +594,24 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
                 for (int qt = 0; qt < 2; ++qt) lacc[qt] = M::mfma(ones, pf[j / DT][qt], lacc[qt]);
               }
             }
+            if constexpr (LOOK_PV && !FIRST) {
+              // the look at the row sums, in the gap behind the product's first MFMAs: the sums hold every tile before this one and have
+              // no writer pending (this tile's ones MFMAs come later, the previous tile's retired sixteen MFMAs ago)
+              if (j == 0) {
+                look = lazy_look();
+                asm volatile("" : "+s"(look));
+              }
+            }
             __builtin_amdgcn_sched_barrier(0);
           }
         }
 #if FA16_PRIO
         __builtin_amdgcn_s_setprio(0);
 #endif
+        if constexpr (LOOK_PV && !FIRST) {
+          // ... and what it leads to, behind the product's last MFMA (never between the MFMAs of one product): one scalar branch
+          if (__builtin_expect(look != 0, 0)) lazy_repair();
+        }
         if constexpr (FIRST && ONES) {
           // the assumed reference was too HIGH for some row (its first-tile sum is below FIRST_SUM_FLOOR): start the tile over with
           // the true maxima (O and the row sums hold nothing of weight: cleared)
@@ -572,6 +633,12 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
       }
     }
   };
+  // LAZY: the last tile's sums have no tile behind them to be looked at: they are tested in front of the block's last barrier, on which the
+  // workgroup's OR of the poison flags rides (a word of LDS, written by poisoned waves only)
+  auto tail_test = [&]() __attribute__((always_inline)) {
+    const unsigned a0 = __builtin_bit_cast(unsigned, lacc[0][0]) & 0x7fffffffu, a1 = __builtin_bit_cast(unsigned, lacc[1][0]) & 0x7fffffffu;
+    if (max(a0, a1) >= LAZY_POISON_BITS) lds_write_b32(poison_flag, 1u);
+  };
   // one staged unit (SUB tiles from tile t0 on, in the slots of buffer `buf`): the next unit's tiles go into the other buffer first, in
   // flight under this unit's MFMAs; one wait + barrier at its end
   auto unit = [&](auto bufc, auto firstc, const int t0) {
@@ -583,16 +650,21 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
     if constexpr (SUB == 2) {
       if (t0 + 1 < nT) tile(std::integral_constant<int, buf * SUB + 1>{}, std::false_type{}, t0 + 1);
     }
-    if (t0 + SUB < nT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the pieces issued at the top of this unit have landed
-    if constexpr (LAZY_TEST) {
-      // the last tile's sums have no tile behind them to be looked at: in front of the block's last barrier, on which the workgroup's OR
-      // of the poison flags rides (a word of LDS, written by poisoned waves only)
-      if (t0 + SUB >= nT && slow == 0) {
-        const unsigned a0 = __builtin_bit_cast(unsigned, lacc[0][0]) & 0x7fffffffu, a1 = __builtin_bit_cast(unsigned, lacc[1][0]) & 0x7fffffffu;
-        if (max(a0, a1) >= LAZY_POISON_BITS) lds_write_b32(poison_flag, 1u);
+    if constexpr (TAIL_OUT) {
+      // the block's LAST barrier, and the test in front of it, stand behind the tile loop (below): a tile's tail is one scalar condition
+      // around its wait and its barrier (with the test in here, on `last unit && !slow`, hipcc laid three scalar branches into the tail of
+      // EVERY tile, in front of the barrier all waves meet at: +0.5 % on configs 3 / non-causal / N = 16384, profiles/r20/ab_tail.log)
+      if (t0 + SUB < nT) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
       }
+    } else {
+      if (t0 + SUB < nT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the pieces issued at the top of this unit have landed
+      if constexpr (LAZY_TEST) {
+        if (t0 + SUB >= nT && slow == 0) tail_test();
+      }
+      __syncthreads();
     }
-    __syncthreads();
   };
   // LAZY: a poisoned block (the workgroup's flag word, read behind the last barrier; nothing has been stored yet) runs once more, in
   // slow mode, through the same loops; every other block leaves through the `break`. (The loop ends in front of the epilogue: around
@@ -603,6 +675,10 @@ __device__ __forceinline__ void fwd_mfma16_body(const Params &p) {
     for (int t = SUB; t < nT; t += 2 * SUB) {
       unit(std::integral_constant<int, 1>{}, std::false_type{}, t);
       if (t + SUB < nT) unit(std::integral_constant<int, 0>{}, std::false_type{}, t + SUB);
+    }
+    if constexpr (TAIL_OUT) {  // the last unit left its barrier to us
+      if (slow == 0) tail_test();
+      __syncthreads();
     }
     if constexpr (LAZY_TEST) {
       if (slow == 0) {

@@ -125,7 +125,13 @@ enum fa_status {
  * first 64 keys, until a score rises 4 log2 units above them), with one bit less per factor of 2 below that, and drops it below 2^-22
  * (2^-25): n such keys move lse by at most n * 2^-22 (n * 2^-25), all roundings in one direction. Where the scores sit does not
  * matter: the first tile is started over from its true row maxima whenever its probabilities against the assumed maximum of 0 add up
- * to less than 1. Every other kernel / dtype (FA_VARIANT_MFMA_EXACT, the split-KV and paired-block kernels, fp8 inputs):
+ * to less than 1. With bf16 inputs at D = 64 (and the smaller head dims that run padded on that kernel) FA_VARIANT_MFMA16 renews a
+ * row's reference LAZILY: probabilities keep their 8 bits at any scale, the row sums are looked at while the NEXT 64-key tile is
+ * multiplied, and a row whose sum has reached 2^20 then takes an exact power of two out of O, its sum and its reference behind that tile --
+ * a rise is answered two tiles after it began, and nothing is rounded on the way. The bounds above hold for any scores; what the
+ * lag costs is time only: a row that rises more than about 44 log2 units (e^30) within TWO consecutive tiles (its sum going from below
+ * 2^20 past 2^64 before the answer) sends its workgroup of 128 or 256 query rows through a second pass on true row maxima. inf / NaN
+ * inputs give inf / NaN rows, as everywhere. Every other kernel / dtype (FA_VARIANT_MFMA_EXACT, the split-KV and paired-block kernels, fp8 inputs):
  * |lse - exact| <= 1e-4 for |lse| <= ~10.
  *
  * fp8 probabilities. FA_VARIANT_MFMA_FP8PV (e4m3 inputs, D = 64 or 128; FA_VARIANT_AUTO's choice for grids that fill the chip) runs BOTH

@@ -4,7 +4,7 @@
     hipcc <the Makefile's flags> --cuda-device-only -S csrc/fa_mfma16_kernel.hip -o k.s
     python tools/isa_hot_tile.py k.s <mangled kernel name>
 
-Prints, per block, the MFMA, v_exp and v_cvt_pk counts and the other VALU by opcode: the hot tile of the 16x16x32 forward is the
+Prints, per basic block (labelled, or a fall-through block `%bb.N`), the MFMA, v_exp and v_cvt_pk counts and the other VALU by opcode: the hot tile of the 16x16x32 forward is the
 block with 32 v_exp (DESIGN 6.3d, row "hot tile")."""
 import re,sys
 def blocks(path,name):
@@ -13,8 +13,8 @@ def blocks(path,name):
     out=[]; cur=['entry',[]]
     for l in t[st:en].splitlines()[1:]:
         c=l.split(';')[0].strip()
-        if l.startswith('.LBB'):
-            out.append(cur); cur=[l.split(':')[0],[]]
+        if l.startswith('.LBB') or l.startswith('; %bb.'):  # (a fall-through block has no label of its own, only the comment)
+            out.append(cur); cur=[l.split(':')[0].lstrip('; '),[]]
         elif c and not c.startswith('.') : cur[1].append(c)
     out.append(cur); return out
 def summarize(path,name):
