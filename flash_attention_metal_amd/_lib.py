@@ -34,6 +34,10 @@ SYMBOLS = {
     "fa_fwd_varlen_paged_sink": (c_int, [c_void_p] * 8 + [c_int] * 9 + [c_float] + [c_longlong] * 6 + [c_int, c_int, c_void_p, c_int, c_void_p]),
     "fa_fwd_decode_paged_sink": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_float] + [c_longlong] * 6 + [c_int, c_int, c_void_p, c_int, c_int]
                                  + [c_void_p, c_longlong, c_void_p]),
+    "fa_fwd_varlen_softcap": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_float, c_int, c_void_p]),
+    "fa_fwd_varlen_paged_softcap": (c_int, [c_void_p] * 8 + [c_int] * 9 + [c_float] + [c_longlong] * 6 + [c_int, c_int, c_float, c_int, c_void_p]),
+    "fa_fwd_decode_paged_softcap": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_float] + [c_longlong] * 6 + [c_int, c_int, c_float, c_int, c_int]
+                                    + [c_void_p, c_longlong, c_void_p]),
     "fa_fwd_varlen_paged_kv8": (c_int, [c_void_p] * 8 + [c_int] * 9 + [c_float] + [c_longlong] * 6 + [c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "fa_fwd_varlen_paged_kv8_supported": (c_int, [c_int] * 4),
     "fa_kv_append_paged_quant": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_longlong] * 6 + [c_int, c_float, c_float, c_void_p]),
@@ -47,6 +51,7 @@ SYMBOLS = {
     "fa_bwd_varlen": (c_int, [c_void_p] * 12 + [c_int] * 8 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_void_p]),
     "fa_bwd_varlen_window": (c_int, [c_void_p] * 12 + [c_int] * 8 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_int, c_void_p]),
     "fa_bwd_varlen_sink": (c_int, [c_void_p] * 12 + [c_int] * 8 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "fa_bwd_varlen_softcap": (c_int, [c_void_p] * 12 + [c_int] * 8 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_float, c_int, c_void_p]),
     "fa_window_query_range": (c_int, [c_int] * 6 + [c_void_p, c_void_p]),
     "fa_bwd_varlen_workspace_bytes": (c_longlong, [c_int, c_int]),
     "fa_bwd_varlen_supported": (c_int, [c_int, c_int]),

@@ -37,6 +37,7 @@ int fail(int code, const char *fmt, ...) {
 //    fa_kv_append_paged: varlen_strides_ok for the new rows, page_pool_ok, and a grid of B * ceil(max_seqlen_new / 16) x Hkv;
 //  - fa_fwd_varlen_paged_kv8: varlen_paged_impl with the pools' own type (strides of 16 elements, a page counted in bytes of 1), its own
 //    support table, sinks optional; fa_kv_append_paged_quant: kv_append_impl with e4m3 pools, plus the two multipliers;
+//  - the four *_softcap entry points: the impl function, and with it every rule, of their *_window call, plus softcap_ok;
 //  - the four *_sink entry points: the impl function, and with it every rule, of their *_window call, plus sinks_ok (and dsinks' alignment);
 //  - a missing device: FA_ERR_NO_DEVICE from fa_fwd, FA_ERR_LAUNCH from every other entry point.
 #define TRY(check) do { if (const int st_ = (check)) return st_; } while (0)
@@ -138,6 +139,10 @@ int window_clamp(int w, int never) { return w < 0 || w > never ? never : w; }
 int sinks_ok(const char *fn, const float *sinks) {
   if (!sinks) return fail(FA_ERR_INVALID_ARG, "%s: null pointer", fn);
   return (uintptr_t)sinks & 3 ? fail(FA_ERR_INVALID_ARG, "%s: sinks must be fp32-aligned", fn) : FA_OK;
+}
+// the *_softcap entry points: the cap is a host scalar, finite and greater than 0
+int softcap_ok(const char *fn, float softcap) {
+  return (std::isfinite(softcap) && softcap > 0.0f) ? FA_OK : fail(FA_ERR_INVALID_ARG, "%s: softcap must be finite and > 0", fn);
 }
 int launched(const char *fn, hipError_t e) {
   return e == hipSuccess ? FA_OK : fail(FA_ERR_LAUNCH, "%s: launch failed: %s", fn, hipGetErrorString(e));
@@ -414,10 +419,13 @@ int fa_fwd_varlen_supported(int dtype, int D) { return fa::mfma_varlen_supported
 static int varlen_impl(const char *fn, const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q,
                        const int *cu_seqlens_k, int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D,
                        float scale, long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
-                       int window_left, int window_right, int dtype, void *hip_stream, const float *const *sinks = nullptr) {
+                       int window_left, int window_right, int dtype, void *hip_stream, const float *const *sinks = nullptr,
+                       const float *softcap = nullptr) {
+  // softcap (fa_fwd_varlen_softcap): like sinks, always the windowed kernels, in their softcap mode
   g_err[0] = 0;
   TRY(nonnull(fn, {q, k, v, o, cu_seqlens_q, cu_seqlens_k}));
   if (sinks) TRY(sinks_ok(fn, *sinks));
+  if (softcap) TRY(softcap_ok(fn, *softcap));
   TRY(positive(fn, {B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
@@ -436,7 +444,7 @@ static int varlen_impl(const char *fn, const void *q, const void *k, const void 
   TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
   TRY(head_fits(fn, (double)(max_seqlen_k + 128) * (double)kv_row_stride * 2, 4, " (one sequence of max_seqlen_k rows)"));
   TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));
-  const int route = sinks ? WIN_KERNEL : window_route(window_left, window_right);
+  const int route = (sinks || softcap) ? WIN_KERNEL : window_route(window_left, window_right);
   fa::VarlenSinkParams p;
   p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
   p.B = B; p.H = Hq; p.Hkv = Hkv; p.N = max_seqlen_q; p.Nk = max_seqlen_k; p.D = D; p.scale = scale;
@@ -448,6 +456,12 @@ static int varlen_impl(const char *fn, const void *q, const void *k, const void 
   if (route != WIN_KERNEL) return launched(fn, fa::launch_mfma_varlen(p, dtype, (hipStream_t)hip_stream));
   p.wl = window_clamp(window_left, max_seqlen_k);
   p.wr = window_clamp(window_right, max_seqlen_q);
+  if (softcap) {
+    fa::VarlenSoftcapParams pc;
+    static_cast<fa::VarlenWindowParams &>(pc) = p;
+    pc.softcap = *softcap;
+    return launched(fn, fa::launch_mfma_varlen_softcap(pc, dtype, (hipStream_t)hip_stream));
+  }
   if (!sinks) return launched(fn, fa::launch_mfma_varlen_window(p, dtype, (hipStream_t)hip_stream));
   p.sinks = *sinks;
   return launched(fn, fa::launch_mfma_varlen_sink(p, dtype, (hipStream_t)hip_stream));
@@ -474,6 +488,14 @@ int fa_fwd_varlen_sink(const void *q, const void *k, const void *v, void *o, flo
   return varlen_impl("fa_fwd_varlen_sink", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q, total_k, max_seqlen_q,
                      max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride, window_left, window_right, dtype,
                      hip_stream, &sinks);
+}
+int fa_fwd_varlen_softcap(const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q, const int *cu_seqlens_k,
+                          int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
+                          long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
+                          int window_left, int window_right, float softcap, int dtype, void *hip_stream) {
+  return varlen_impl("fa_fwd_varlen_softcap", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q, total_k, max_seqlen_q,
+                     max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride, window_left, window_right, dtype,
+                     hip_stream, nullptr, &softcap);
 }
 int fa_window_key_range(int Lq, int Lk, int window_left, int window_right, int row_first, int row_last, int *key_lo, int *key_hi) {
   g_err[0] = 0;
@@ -556,10 +578,11 @@ static int decode_paged_impl(const char *fn, const void *q, const void *k_pages,
                              int max_pages_per_seq, float scale, long long q_batch_stride, long long q_head_stride, long long kv_page_stride,
                              long long kv_head_stride, long long kv_row_stride, long long block_table_stride, int window_left,
                              int window_right, int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes, void *hip_stream,
-                             const float *const *sinks = nullptr) {
+                             const float *const *sinks = nullptr, const float *softcap = nullptr) {
   g_err[0] = 0;
   TRY(nonnull(fn, {q, k_pages, v_pages, o, block_table, seqlens_k, workspace}));
   if (sinks) TRY(sinks_ok(fn, *sinks));
+  if (softcap) TRY(softcap_ok(fn, *softcap));
   TRY(positive(fn, {B, Hq, Hkv, Nq, D, page_size, num_pages, max_pages_per_seq}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
@@ -575,7 +598,7 @@ static int decode_paged_impl(const char *fn, const void *q, const void *k_pages,
   TRY(page_tables_ok(fn, page_size, max_pages_per_seq, block_table, seqlens_k));
   const int cap = page_size * max_pages_per_seq;
   TRY(workspace_fits(fn, workspace_bytes, fa::decode_workspace_bytes(B, Hq, Hkv, Nq, cap, D), "fa_fwd_decode_paged_workspace_bytes"));
-  const int route = sinks ? WIN_KERNEL : window_route(window_left, window_right);
+  const int route = (sinks || softcap) ? WIN_KERNEL : window_route(window_left, window_right);
   fa::DecodeWindowParams p;
   // Nk = the capacity, hence the dense decode's split rule there: bit-identical to it on full caches
   TRY(decode_params(fn, p, q, k_pages, v_pages, o, lse, workspace, B, Hq, Hkv, Nq, cap, D, scale, q_batch_stride, q_head_stride, route != WIN_FULL, kv8));
@@ -587,6 +610,12 @@ static int decode_paged_impl(const char *fn, const void *q, const void *k_pages,
   if (route != WIN_KERNEL) return launched(fn, fa::launch_decode_paged(p, D, q_dtype, kv8, (hipStream_t)hip_stream));
   p.wl = window_clamp(window_left, cap);
   p.wr = window_clamp(window_right, Nq);
+  if (softcap) {
+    fa::DecodeSoftcapParams pc;
+    static_cast<fa::DecodePagedParams &>(pc) = p;
+    pc.wl = p.wl; pc.wr = p.wr; pc.softcap = *softcap;
+    return launched(fn, fa::launch_decode_paged_softcap(pc, D, q_dtype, kv8, (hipStream_t)hip_stream));
+  }
   if (!sinks) return launched(fn, fa::launch_decode_paged_window(p, D, q_dtype, kv8, (hipStream_t)hip_stream));
   return launched(fn, fa::launch_decode_paged_sink(p, *sinks, D, q_dtype, kv8, (hipStream_t)hip_stream));
 }
@@ -618,6 +647,17 @@ int fa_fwd_decode_paged_sink(const void *q, const void *k_pages, const void *v_p
                            num_pages, max_pages_per_seq, scale, q_batch_stride, q_head_stride, kv_page_stride, kv_head_stride, kv_row_stride,
                            block_table_stride, window_left, window_right, q_dtype, kv_dtype, workspace, workspace_bytes, hip_stream, &sinks);
 }
+int fa_fwd_decode_paged_softcap(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *block_table,
+                                const int *seqlens_k, int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages,
+                                int max_pages_per_seq, float scale, long long q_batch_stride, long long q_head_stride,
+                                long long kv_page_stride, long long kv_head_stride, long long kv_row_stride, long long block_table_stride,
+                                int window_left, int window_right, float softcap, int q_dtype, int kv_dtype, void *workspace,
+                                long long workspace_bytes, void *hip_stream) {
+  return decode_paged_impl("fa_fwd_decode_paged_softcap", q, k_pages, v_pages, o, lse, block_table, seqlens_k, B, Hq, Hkv, Nq, D, page_size,
+                           num_pages, max_pages_per_seq, scale, q_batch_stride, q_head_stride, kv_page_stride, kv_head_stride, kv_row_stride,
+                           block_table_stride, window_left, window_right, q_dtype, kv_dtype, workspace, workspace_bytes, hip_stream, nullptr,
+                           &softcap);
+}
 
 int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size) { return fa::mfma_varlen_paged_supported(dtype, D, page_size); }
 static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
@@ -625,13 +665,14 @@ static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages,
                              int max_seqlen_q, int D, int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride,
                              long long q_head_stride, long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
                              long long block_table_stride, int window_left, int window_right, int dtype, void *hip_stream,
-                             const float *const *sinks = nullptr, const int *kv8_dtype = nullptr) {
+                             const float *const *sinks = nullptr, const int *kv8_dtype = nullptr, const float *softcap = nullptr) {
   // kv8_dtype (fa_fwd_varlen_paged_kv8): `dtype` is q's and *kv8_dtype the pools'. Every rule below is the one path of both families;
   // what differs is the support table with its text, the pools' stride multiple and bytes per element (page_pool_ok under the pools'
   // type), and the routing: that call always runs its own kernel family, with or without sinks.
   g_err[0] = 0;
   TRY(nonnull(fn, {q, k_pages, v_pages, o, cu_seqlens_q, block_table, seqlens_k}));
   if (sinks) TRY(sinks_ok(fn, *sinks));
+  if (softcap) TRY(softcap_ok(fn, *softcap));
   TRY(positive(fn, {B, Hq, Hkv, total_q, max_seqlen_q, D, page_size, num_pages, max_pages_per_seq}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
@@ -651,7 +692,7 @@ static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages,
   if ((uintptr_t)cu_seqlens_q & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q must be int32-aligned", fn);
   TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
   TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));
-  const int route = (sinks || kv8_dtype) ? WIN_KERNEL : window_route(window_left, window_right);
+  const int route = (sinks || kv8_dtype || softcap) ? WIN_KERNEL : window_route(window_left, window_right);
   fa::VarlenPagedSinkParams p;
   p.q = q; p.k = k_pages; p.v = v_pages; p.o = o; p.lse = lse;
   p.B = B; p.H = Hq; p.Hkv = Hkv; p.N = max_seqlen_q; p.Nk = page_size * max_pages_per_seq; p.D = D; p.scale = scale;
@@ -668,6 +709,12 @@ static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages,
   p.wl = window_clamp(window_left, p.Nk);
   p.wr = window_clamp(window_right, max_seqlen_q);
   p.sinks = sinks ? *sinks : nullptr;
+  if (softcap) {
+    fa::VarlenPagedSoftcapParams pc;
+    static_cast<fa::VarlenPagedWindowParams &>(pc) = p;
+    pc.softcap = *softcap;
+    return launched(fn, fa::launch_mfma_varlen_paged_softcap(pc, dtype, (hipStream_t)hip_stream));
+  }
   if (kv8_dtype) return launched(fn, fa::launch_mfma_varlen_paged_kv8(p, sinks != nullptr, (hipStream_t)hip_stream));
   if (!sinks) return launched(fn, fa::launch_mfma_varlen_paged_window(p, dtype, (hipStream_t)hip_stream));
   return launched(fn, fa::launch_mfma_varlen_paged_sink(p, dtype, (hipStream_t)hip_stream));
@@ -699,6 +746,17 @@ int fa_fwd_varlen_paged_sink(const void *q, const void *k_pages, const void *v_p
   return varlen_paged_impl("fa_fwd_varlen_paged_sink", q, k_pages, v_pages, o, lse, cu_seqlens_q, block_table, seqlens_k, B, Hq, Hkv, total_q,
                            max_seqlen_q, D, page_size, num_pages, max_pages_per_seq, scale, q_row_stride, q_head_stride, kv_page_stride,
                            kv_head_stride, kv_row_stride, block_table_stride, window_left, window_right, dtype, hip_stream, &sinks);
+}
+int fa_fwd_varlen_paged_softcap(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *cu_seqlens_q,
+                                const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                                int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride,
+                                long long q_head_stride, long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                                long long block_table_stride, int window_left, int window_right, float softcap, int dtype,
+                                void *hip_stream) {
+  return varlen_paged_impl("fa_fwd_varlen_paged_softcap", q, k_pages, v_pages, o, lse, cu_seqlens_q, block_table, seqlens_k, B, Hq, Hkv,
+                           total_q, max_seqlen_q, D, page_size, num_pages, max_pages_per_seq, scale, q_row_stride, q_head_stride,
+                           kv_page_stride, kv_head_stride, kv_row_stride, block_table_stride, window_left, window_right, dtype, hip_stream,
+                           nullptr, nullptr, &softcap);
 }
 int fa_fwd_varlen_paged_kv8_supported(int q_dtype, int kv_dtype, int D, int page_size) {
   return fa::mfma_varlen_paged_kv8_supported(q_dtype, kv_dtype, D, page_size);
@@ -862,13 +920,16 @@ static int bwd_varlen_impl(const char *fn, const void *q, const void *k, const v
                            float *dq, float *dk, float *dv, void *workspace, const int *cu_seqlens_q, const int *cu_seqlens_k, int B, int Hq,
                            int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale, long long q_row_stride,
                            long long q_head_stride, long long kv_row_stride, long long kv_head_stride, int window_left, int window_right,
-                           int dtype, void *hip_stream, const float *const *sinks = nullptr, float *dsinks = nullptr) {
+                           int dtype, void *hip_stream, const float *const *sinks = nullptr, float *dsinks = nullptr,
+                           const float *softcap = nullptr) {
+  // softcap (fa_bwd_varlen_softcap): always the windowed kernels, in their softcap mode
   g_err[0] = 0;
   TRY(nonnull(fn, {q, k, v, o, d_o, lse, dq, dk, dv, workspace, cu_seqlens_q, cu_seqlens_k}));
   if (sinks) {
     TRY(sinks_ok(fn, *sinks));
     if ((uintptr_t)dsinks & 3) return fail(FA_ERR_INVALID_ARG, "%s: dsinks must be fp32-aligned", fn);
   }
+  if (softcap) TRY(softcap_ok(fn, *softcap));
   TRY(positive(fn, {B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D}));
   TRY(grouped(fn, Hq, Hkv));
   TRY(scale_ok(fn, scale));
@@ -889,7 +950,12 @@ static int bwd_varlen_impl(const char *fn, const void *q, const void *k, const v
   TRY(grid_fits(fn, (long long)B * Hkv, max_seqlen_k));  // the dK/dV kernel's
   const int route = window_route(window_left, window_right);
   hipError_t e;
-  if (route != WIN_KERNEL)
+  if (softcap)
+    e = fa::launch_bwd_varlen_softcap(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q,
+                                      total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride,
+                                      kv_head_stride, window_clamp(window_left, max_seqlen_k), window_clamp(window_right, max_seqlen_q),
+                                      *softcap, dtype, (hipStream_t)hip_stream);
+  else if (route != WIN_KERNEL)
     e = fa::launch_bwd_varlen(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q, total_k,
                               max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride,
                               route == WIN_CAUSAL ? 1 : 0, dtype, (hipStream_t)hip_stream);
@@ -927,6 +993,15 @@ int fa_bwd_varlen_sink(const void *q, const void *k, const void *v, const void *
   return bwd_varlen_impl("fa_bwd_varlen_sink", q, k, v, o, d_o, lse, dq, dk, dv, workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q,
                          total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride,
                          window_left, window_right, dtype, hip_stream, &sinks, dsinks);
+}
+int fa_bwd_varlen_softcap(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq, float *dk,
+                          float *dv, void *workspace, const int *cu_seqlens_q, const int *cu_seqlens_k, int B, int Hq, int Hkv, int total_q,
+                          int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale, long long q_row_stride,
+                          long long q_head_stride, long long kv_row_stride, long long kv_head_stride, int window_left, int window_right,
+                          float softcap, int dtype, void *hip_stream) {
+  return bwd_varlen_impl("fa_bwd_varlen_softcap", q, k, v, o, d_o, lse, dq, dk, dv, workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q,
+                         total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride,
+                         window_left, window_right, dtype, hip_stream, nullptr, nullptr, &softcap);
 }
 int fa_window_query_range(int Lq, int Lk, int window_left, int window_right, int key_first, int key_last, int *row_lo, int *row_hi) {
   g_err[0] = 0;

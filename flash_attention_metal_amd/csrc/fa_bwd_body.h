@@ -1,6 +1,7 @@
 // fa_bwd_body.h -- what the translation units of the backward share: fa_bwd_kernels.hip (dense: fa_bwd / fa_bwd_ex),
 // fa_bwd_varlen_kernels.hip (packed variable-length sequences: fa_bwd_varlen) and fa_bwd_window_kernels.hip (the same under a sliding
-// window: fa_bwd_varlen_window, FA_BWD_WINDOW = 1 on top of FA_BWD_VARLEN = 1). The algorithm and its history are described at the top of
+// window: fa_bwd_varlen_window, FA_BWD_WINDOW = 1 on top of FA_BWD_VARLEN = 1; fa_bwd_softcap_kernels.hip adds FA_BWD_SOFTCAP = 1 on top of
+// that: fa_bwd_varlen_softcap). The algorithm and its history are described at the top of
 // fa_bwd_kernels.hip. Here: the parameter blocks and the per-head-dim constants; the two kernel bodies themselves are the texts
 // fa_bwd_dq_body.inc and fa_bwd_dkdv_body.inc, which each __global__ function of either file includes as its body with FA_BWD_VARLEN
 // set to 0 or 1. Text, not a function: behind a forced-inline function the compiler copies the parameter block before it inlines, which
@@ -41,10 +42,21 @@ struct BwdWindowParams : BwdVarlenParams {
   int wl, wr;
 };
 
+// one fa_bwd_varlen_softcap call (the softcap mode of the bodies, FA_BWD_SOFTCAP = 1 on top of the window mode;
+// fa_bwd_softcap_kernels.hip): the windowed call's parameters plus the cap, a finite positive host scalar
+struct BwdSoftcapParams : BwdWindowParams {
+  float softcap;
+  float cap_log2;  // softcap * log2(e), the capped scores' factor to log2 units
+};
+
 constexpr float LOG2E = 1.4426950408889634f;
 
 #ifndef FA_BWD_WINDOW
 #define FA_BWD_WINDOW 0  // the bodies' window mode: 1 only around the kernels of fa_bwd_window_kernels.hip
+#endif
+
+#ifndef FA_BWD_SOFTCAP
+#define FA_BWD_SOFTCAP 0  // the bodies' softcap mode (on top of the window mode): 1 only around the kernels of fa_bwd_softcap_kernels.hip
 #endif
 
 #ifndef FA_BWD_DMA

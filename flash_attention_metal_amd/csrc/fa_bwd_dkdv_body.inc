@@ -1,7 +1,8 @@
 // fa_bwd_dkdv_body.inc -- the body of the dK/dV kernels (fa_bwd_body.h says how it is used): included inside
 //   template <typename Tag, int D, bool CAUSAL, bool PAD> __global__ void kernel(BwdParams or BwdVarlenParams p)
 // with FA_BWD_VARLEN defined to 0 or 1, and FA_BWD_WINDOW (varlen only) to 0 or 1: the window mode, whose parameter block is
-// BwdWindowParams. Its arms are chosen in the preprocessor, so that the text the other kernels compile is the text they had.
+// BwdWindowParams; FA_BWD_SOFTCAP (window only) to 0 or 1: the softcap mode, BwdSoftcapParams. Their arms are chosen in the preprocessor,
+// so that the text the other kernels compile is the text they had.
 // dK, dV: workgroup = 128 keys, wave = 32 keys (key on the lane, queries in the registers)
 #if FA_BWD_VARLEN
 #define FA_VP p
@@ -13,6 +14,7 @@
   constexpr bool VARLEN = FA_BWD_VARLEN != 0;
   static_assert(!VARLEN || (!PAD && (D == 64 || D == 128) && FA_BWD_DMA != 0), "varlen mode: head_dim 64 / 128, LDS-DMA staging");
   static_assert(FA_BWD_WINDOW == 0 || (VARLEN && CAUSAL), "window mode: on top of the varlen mode");
+  static_assert(FA_BWD_SOFTCAP == 0 || FA_BWD_WINDOW != 0, "softcap mode: on top of the window mode");
   FA_BWD_CONSTS(D, bwd_sub_kv(D));
   FA_BWD_PAD(PAD);
   using M = MT<Tag>;
@@ -82,7 +84,14 @@
     kf[ks] = __builtin_bit_cast(vec8, __builtin_amdgcn_raw_buffer_load_b128(rk, (VARLEN ? (unsigned)krow * kvrb : (unsigned)krow * GRB) + gcol(2 * ks + h), 0, 0));
     vf[ks] = __builtin_bit_cast(vec8, __builtin_amdgcn_raw_buffer_load_b128(rv, (VARLEN ? (unsigned)krow * kvrb : (unsigned)krow * GRB) + gcol(2 * ks + h), 0, 0));
   }
+#if FA_BWD_SOFTCAP
+  // softcap (see the dQ body): K~ carries 2 log2(e) scale / softcap; the score chain starts from zero and the row's -lse.log2e is applied
+  // behind tanh, from the LDS rows that hold it already
+  const float c2 = 2.0f * LOG2E * p.scale / p.softcap;
+  const float capc = p.cap_log2;  // (softcap . log2(e) from the host: a kernel argument stays in a scalar register, a product formed here in a vector one)
+#else
   const float c2 = p.scale * LOG2E;
+#endif
 
   const int kx = u_swz(r);
   const unsigned qu0 = (unsigned)(__UINTPTR_TYPE__)QU;
@@ -285,6 +294,15 @@
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int ql = 32 * qb + 8 * g;  // (+ 4h: in rowoff)
+#if FA_BWD_SOFTCAP
+          const u32x4 d4 = lds_read_b128(at(rows + BT * 4 + ql * 4));  // (-lse.log2e is applied behind tanh: the score chain starts from zero)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const unsigned dw = d4[e];
+            sq[4 * g + e] = 0.0f;
+            dpq[4 * g + e] = __builtin_bit_cast(float, dw);
+          }
+#else
           const u32x4 l4 = lds_read_b128(at(rows + ql * 4));
           const u32x4 d4 = lds_read_b128(at(rows + BT * 4 + ql * 4));
 #pragma unroll
@@ -295,6 +313,7 @@
             sq[4 * g + e] = __builtin_bit_cast(float, lw);
             dpq[4 * g + e] = __builtin_bit_cast(float, dw);
           }
+#endif
         }
         {
           constexpr int NF = 2 * BKS, LA = BD >= 128 ? FA_BWD_KV128_LA : FA_BWD_LA;
@@ -314,6 +333,44 @@
             __builtin_amdgcn_sched_barrier(0);
           });
         }
+#if FA_BWD_SOFTCAP
+        // the cap, in front of the mask: sq becomes the exponent t . C - lse.log2e (the row's value from LDS; -inf for a dead row or one
+        // past the end) and dpq takes the factor 1 - t^2 (a masked element's exponent is set to -inf below; its dpq stays finite)
+        // (a few rows at a time and the steps kept apart: left to itself hipcc holds all sixteen t and row values at once and spills around
+        // the tile loop. head_dim 64: four rows, the next four's values read one step ahead; head_dim 128: two rows and no step ahead)
+        if constexpr (BD >= 128) {
+#pragma unroll
+          for (int c = 0; c < 8; ++c) {  // registers 2c, 2c + 1 = rows 8 (c / 2) + 2 (c % 2) + 0..1 (+ 4h: in rowoff)
+            const u32x2 l2 = *reinterpret_cast<const __attribute__((address_space(3))) u32x2 *>(at(rows + (32 * qb + 8 * (c / 2) + 2 * (c % 2)) * 4));
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              const unsigned lw = l2[e];
+              const float tq = tanh_from_exp2_arg(sq[2 * c + e]);
+              dpq[2 * c + e] *= __builtin_fmaf(-tq, tq, 1.0f);
+              asm volatile("" : "+v"(dpq[2 * c + e]));  // (formed here: hipcc otherwise sinks the multiply below the mask and keeps every t)
+              sq[2 * c + e] = __builtin_fmaf(tq, capc, __builtin_bit_cast(float, lw));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        } else {
+          u32x4 l4 = lds_read_b128(at(rows + (32 * qb) * 4));
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            u32x4 l4n = l4;
+            if (g < 3) l4n = lds_read_b128(at(rows + (32 * qb + 8 * (g + 1)) * 4));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const unsigned lw = l4[e];
+              const float tq = tanh_from_exp2_arg(sq[4 * g + e]);
+              dpq[4 * g + e] *= __builtin_fmaf(-tq, tq, 1.0f);
+              asm volatile("" : "+v"(dpq[4 * g + e]));  // (as above)
+              sq[4 * g + e] = __builtin_fmaf(tq, capc, __builtin_bit_cast(float, lw));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            l4 = l4n;
+          }
+        }
+#endif
         // dV / dK fragments of this half (step j = (st, db, which): which 0 = dO^T fragment -> dV, 1 = Q^T fragment -> dK) are
         // read LA2 steps ahead of their MFMA, the first ones before the P / dS arithmetic (they do not depend on it)
         constexpr int NJ = 4 * BDB, LA2 = BD >= 128 ? FA_BWD_KV128_LA2 : FA_BWD_LA2, TV = BD == 64 ? 4 : 2;
@@ -324,7 +381,12 @@
           tlo[j] = lds_read_tr16(at(voff[(R0 >> 3) % TV][db] + src + R0 * BRB));
           thi[j] = lds_read_tr16(at(voff[((R0 >> 3) + 1) % TV][db] + src + (R0 + 8) * BRB));
         };
+#if FA_BWD_SOFTCAP
+        // (head_dim 128: the first transposed reads wait until P and dS are packed -- their four registers are what the cap's arithmetic needs)
+        if constexpr (BD < 128) static_for<0, LA2>([&](auto jc) { tread(jc); });
+#else
         static_for<0, LA2>([&](auto jc) { tread(jc); });
+#endif
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(0);
         if (need_mask) {  // key > query (kernels.metal:748): S' = -inf there. A wave-uniform BRANCH: written as a per-element
@@ -365,6 +427,12 @@
             df[st][j] = (elem)dpq[8 * st + j];
           }
         // dV^T += dO^T.P ; dK^T += Q^T.dS   (reduction over this half's 32 query rows)
+#if FA_BWD_SOFTCAP
+        if constexpr (BD >= 128) {
+          __builtin_amdgcn_sched_barrier(0);
+          static_for<0, LA2>([&](auto jc) { tread(jc); });
+        }
+#endif
         __builtin_amdgcn_s_setprio(1);
         static_for<0, NJ>([&](auto jc) {
           constexpr int j = decltype(jc)::value, jj = j / 2, st = jj / BDB, db = jj % BDB;

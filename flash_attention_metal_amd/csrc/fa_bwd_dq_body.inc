@@ -1,7 +1,8 @@
 // fa_bwd_dq_body.inc -- the body of the dQ kernels (fa_bwd_body.h says how it is used): included inside
 //   template <typename Tag, int D, bool CAUSAL, bool PAD> __global__ void kernel(BwdParams or BwdVarlenParams p)
 // with FA_BWD_VARLEN defined to 0 or 1, and FA_BWD_WINDOW (varlen only) to 0 or 1: the window mode, whose parameter block is
-// BwdWindowParams. Its arms are chosen in the preprocessor, so that the text the other kernels compile is the text they had.
+// BwdWindowParams; FA_BWD_SOFTCAP (window only) to 0 or 1: the softcap mode, BwdSoftcapParams. Their arms are chosen in the preprocessor,
+// so that the text the other kernels compile is the text they had.
 // dQ: workgroup = 128 query rows, wave = 32 rows (query on the lane, keys in the registers)
 #if FA_BWD_VARLEN
 #define FA_VP p
@@ -13,6 +14,7 @@
   constexpr bool VARLEN = FA_BWD_VARLEN != 0;
   static_assert(!VARLEN || (!PAD && (D == 64 || D == 128) && FA_BWD_DMA != 0), "varlen mode: head_dim 64 / 128, LDS-DMA staging");
   static_assert(FA_BWD_WINDOW == 0 || (VARLEN && CAUSAL), "window mode: on top of the varlen mode, in the masked kernels' block order");
+  static_assert(FA_BWD_SOFTCAP == 0 || FA_BWD_WINDOW != 0, "softcap mode: on top of the window mode");
   FA_BWD_CONSTS(D, bwd_sub_dq(D));
   FA_BWD_PAD(PAD);
   using M = MT<Tag>;
@@ -108,7 +110,15 @@
   const bool qlive = (VARLEN && CAUSAL) ? (qvalid && qrow + coff >= 0) : qvalid;
 #endif
   const float lse2 = qlive ? p.lse[(VARLEN ? row_base : (long long)bh * p.N) + qrow] * LOG2E : INFINITY;
+#if FA_BWD_SOFTCAP
+  // softcap: the capped score softcap . tanh(x), x = scale . s / softcap, takes the raw score's place. Q~ carries 2 log2(e) scale /
+  // softcap, so the matrix core delivers y with 2^y = e^(2x); the score chain starts from zero and the row's -lse.log2e is applied behind
+  // tanh: P = exp2(fma(t, C, -lse2)), C = softcap . log2(e). dS gets the factor 1 - t^2 = d(softcap tanh(x)) / d(scale s).
+  const float c2 = 2.0f * LOG2E * p.scale / p.softcap;
+  const float capc = p.cap_log2;  // (softcap . log2(e) from the host: a kernel argument stays in a scalar register, a product formed here in a vector one)
+#else
   const float c2 = p.scale * LOG2E;
+#endif
   // delta_i = rowsum(dO o O) (kernels.metal:983-990): this lane holds half of row i's dO (columns 16ks + 8h ..), loads the
   // same half of O, and the two halves of the row meet through one permlane swap; written once for the dK/dV kernel
   float dlt = 0.0f;
@@ -127,8 +137,13 @@
   }
   f32x16 nlse, ndlt;  // the row constants, one per lane, in all 16 registers of a tuple: C operands of the chains' first MFMAs
 #pragma unroll
+#if FA_BWD_SOFTCAP
+  for (int i = 0; i < 16; ++i) { nlse[i] = 0.0f; ndlt[i] = -dlt; }  // (the score chain starts from a constant zero tuple: no registers)
+  asm volatile("" : "+v"(ndlt));
+#else
   for (int i = 0; i < 16; ++i) { nlse[i] = -lse2; ndlt[i] = -dlt; }
   asm volatile("" : "+v"(nlse), "+v"(ndlt));  // opaque: else hipcc re-materialises the splats in front of every MFMA
+#endif
 
   const int kx = u_swz(r);
   // ABSOLUTE LDS addresses in the current K buffer (the V image is 2 STILE further), flipped in place once per tile: with the
@@ -303,6 +318,16 @@
         for (int j = 0; j < LA2; ++j) tread(j);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(0);
+#if FA_BWD_SOFTCAP
+        // the cap, in front of the mask: sk becomes the exponent t . C - lse2 and dpk takes the factor 1 - t^2 (a masked element's
+        // exponent is set to -inf below; its dpk stays finite, so its dS is exactly 0)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const float tq = tanh_from_exp2_arg(sk[i]);
+          dpk[i] *= __builtin_fmaf(-tq, tq, 1.0f);
+          sk[i] = __builtin_fmaf(tq, capc, -lse2);
+        }
+#endif
         if (need_mask) {  // key > query -> masked (kernels.metal:748); a wave-uniform branch
           int lim = FA_NK - 1 - kv0 - 32 * kb - 4 * h;
 #if FA_BWD_WINDOW

@@ -121,6 +121,22 @@ struct VarlenPagedSinkParams : VarlenPagedWindowParams {
 struct VarlenPagedKv8Params : VarlenPagedWindowParams {};
 struct VarlenPagedKv8SinkParams : VarlenPagedSinkParams {};
 
+// the softcap modes of the windowed modes (fa_fwd_varlen_softcap, fa_fwd_varlen_paged_softcap; include/fa_mi355.h, "Logit soft-capping"):
+// the windowed call's parameters plus the cap, a finite positive host scalar. Every score becomes softcap * tanh(scale * s / softcap)
+// before the mask; the kernels pre-scale the query operand by 2 log2(e) scale / softcap instead of scale log2(e).
+struct VarlenSoftcapParams : VarlenWindowParams {
+  float softcap;
+};
+struct VarlenPagedSoftcapParams : VarlenPagedWindowParams {
+  float softcap;
+};
+
+// tanh as the softcap kernels of all three families evaluate it, from y = 2 x log2(e) (what the matrix core delivers under the pre-scaled
+// operand): 1 - 2 / (1 + 2^y), one v_exp_f32 and one v_rcp_f32. Finite at both ends: 2^y = inf gives 1, 2^y = 0 gives -1.
+__device__ __forceinline__ float tanh_from_exp2_arg(float y) {
+  return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y)), 1.0f);
+}
+
 // one fa_fwd_decode call (csrc/fa_decode_kernel.hip)
 struct DecodeParams {
   const void *q, *k, *v;
@@ -156,6 +172,13 @@ struct CombineSinkParams : DecodeParams {
   const float *sinks;
 };
 
+// one fa_fwd_decode_paged_softcap call: the windowed paged decode's parameters plus the cap (see VarlenSoftcapParams). The combine kernels
+// run unchanged: they see only (acc, m, l).
+struct DecodeSoftcapParams : DecodePagedParams {
+  int wl, wr;
+  float softcap;
+};
+
 // dtype tags
 struct F32 {};
 struct F16 {};
@@ -177,6 +200,8 @@ hipError_t launch_mfma_varlen_window(const VarlenWindowParams &p, int dtype, hip
 hipError_t launch_mfma_varlen_paged_window(const VarlenPagedWindowParams &p, int dtype, hipStream_t s);
 hipError_t launch_mfma_varlen_sink(const VarlenSinkParams &p, int dtype, hipStream_t s);
 hipError_t launch_mfma_varlen_paged_sink(const VarlenPagedSinkParams &p, int dtype, hipStream_t s);
+hipError_t launch_mfma_varlen_softcap(const VarlenSoftcapParams &p, int dtype, hipStream_t s);
+hipError_t launch_mfma_varlen_paged_softcap(const VarlenPagedSoftcapParams &p, int dtype, hipStream_t s);
 // fa_fwd_varlen_paged_kv8: bf16 queries on e4m3 pools, always the KV8 window-mode kernels (with_sink: p.sinks is read, their sink mode)
 hipError_t launch_mfma_varlen_paged_kv8(const VarlenPagedSinkParams &p, bool with_sink, hipStream_t s);
 bool mfma_varlen_paged_kv8_supported(int q_dtype, int kv_dtype, int D, int page_size);
@@ -214,6 +239,8 @@ hipError_t launch_decode_paged(const DecodePagedParams &p, int D, int dtype, int
 hipError_t launch_decode_paged_window(const DecodeWindowParams &p, int D, int dtype, int kv8, hipStream_t s);
 // fa_fwd_decode_paged_sink: the windowed partial kernels, then the combine kernel that folds sinks[hq] into every row
 hipError_t launch_decode_paged_sink(const DecodeWindowParams &p, const float *sinks, int D, int dtype, int kv8, hipStream_t s);
+// fa_fwd_decode_paged_softcap: the windowed partial kernels in their softcap mode, then the unchanged paged combine
+hipError_t launch_decode_paged_softcap(const DecodeSoftcapParams &p, int D, int dtype, int kv8, hipStream_t s);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);
@@ -236,6 +263,11 @@ hipError_t launch_bwd_varlen_window(const void *q, const void *k, const void *v,
                                     float *dk, float *dv, float *ws, const int *cu_q, const int *cu_k, int B, int H, int Hkv, int total_q,
                                     int total_k, int max_q, int max_k, int D, float scale, long long q_rs, long long q_hs, long long kv_rs,
                                     long long kv_hs, int wl, int wr, int dtype, hipStream_t s);
+// fa_bwd_varlen_softcap (csrc/fa_bwd_softcap_kernels.hip): fa_bwd_varlen_window under a logit cap (finite, > 0)
+hipError_t launch_bwd_varlen_softcap(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq,
+                                     float *dk, float *dv, float *ws, const int *cu_q, const int *cu_k, int B, int H, int Hkv, int total_q,
+                                     int total_k, int max_q, int max_k, int D, float scale, long long q_rs, long long q_hs, long long kv_rs,
+                                     long long kv_hs, int wl, int wr, float softcap, int dtype, hipStream_t s);
 // the sinks' gradient of fa_bwd_varlen_sink (csrc/fa_sink_kernels.hip): dsinks[h] = -sum_i exp(sinks[h] - lse[h, i]) * delta[h, i] over the
 // query tokens a sequence owns, one workgroup per head, launched behind the dQ kernel that wrote delta
 hipError_t launch_dsink(const float *sinks, const float *lse, const float *delta, float *dsinks, const int *cu_q, int B, int H, int total_q,

@@ -82,7 +82,11 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(PRM p) {
   // WINDOW (PRM = DecodeWindowParams, fa_fwd_decode_paged_window; instantiated with CAUSAL): key j is visible to row iq iff
   // iq + cl <= j <= iq + cu, cl = coff - wl, cu = coff + wr (non-negative bounds from the host). The item's tiles are a share of
   // [t_lo, nT), the tiles that hold the keys rows 0 .. Nq - 1 see together, instead of [0, nT).
-  constexpr bool WINDOW = std::is_same<PRM, DecodeWindowParams>::value;
+  // SOFTCAP (PRM = DecodeSoftcapParams, fa_fwd_decode_paged_softcap): window mode over capped scores softcap . tanh(scale . s / softcap).
+  // Q~ carries 2 log2(e) scale / softcap, so the matrix core delivers the argument of tanh's one exponential; t . softcap . log2(e) takes
+  // the score's place in front of the mask (tanh(-inf) is -1, not -inf), and everything from the mask onwards is the window mode's.
+  constexpr bool SOFTCAP = std::is_same<PRM, DecodeSoftcapParams>::value;
+  constexpr bool WINDOW = std::is_same<PRM, DecodeWindowParams>::value || SOFTCAP;
   static_assert(!WINDOW || CAUSAL, "window mode: the upper bound is the causal one with its own offset");
   using M = MD16<Tag>;
   using vec8 = typename M::vec8;
@@ -128,7 +132,12 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(PRM p) {
   const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.v + base_kv * EB), 0, kv_bytes, 0x00020000);
 
   // ---- Q fragments: lane (c, g) holds row r = 16qt + c of the packed block, elements 32ks + 8g .. +7; pre-scaled Q~ = round(c.Q)
-  const float c2 = p.scale * 1.4426950408889634f;
+  float c2 = p.scale * 1.4426950408889634f;
+  float capc = 0.0f;  // softcap mode: softcap . log2(e)
+  if constexpr (SOFTCAP) {
+    capc = p.softcap * 1.4426950408889634f;
+    c2 = 2.0f * c2 / p.softcap;
+  }
   vec8 qf[QT][KS];
   int rlim[QT];  // last visible key of the lane's rows (causal; Nk - 1 otherwise and for padding rows)
   int rlo[QT];   // window mode: their first visible key (0 for padding rows)
@@ -347,6 +356,17 @@ __global__ __launch_bounds__(64) void decode_partial_kernel(PRM p) {
           const vec8 kf = __builtin_bit_cast(vec8, lds_read_b128(kptr[ks] + bo + kt * 16 * RB));
 #pragma unroll
           for (int qt = 0; qt < QT; ++qt) sc[kt][qt] = M::mfma(kf, qf[qt][ks], sc[kt][qt]);
+        }
+      }
+      if constexpr (SOFTCAP) {  // the capped scores, log2 units
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+#pragma unroll
+          for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sc[kt][qt][i] = tanh_from_exp2_arg(sc[kt][qt][i]) * capc;
+          // (32 packed rows at head_dim 128: one 16-key tile's temporaries at a time, or the kernel no longer fits two waves per SIMD)
+          if (D == 128 && QT == 2) __builtin_amdgcn_sched_barrier(0);
         }
       }
       // ---- mask: key > the row's limit (causal, bottom-right aligned) or key >= Nk
@@ -645,7 +665,8 @@ static hipError_t launch_decode_sink_q(const DecodeWindowParams &p, const float 
 
 template <typename Tag, int D, int QT, bool KV8, typename PRM>
 static hipError_t launch_decode_q(const PRM &p, hipStream_t s) {
-  constexpr bool PAGED = std::is_base_of<DecodePagedParams, PRM>::value, WINDOW = std::is_same<PRM, DecodeWindowParams>::value;
+  constexpr bool PAGED = std::is_base_of<DecodePagedParams, PRM>::value;
+  constexpr bool WINDOW = std::is_same<PRM, DecodeWindowParams>::value || std::is_same<PRM, DecodeSoftcapParams>::value;
   auto combine = decode_combine_kernel<Tag, D, QT, PAGED>;
   if constexpr (!WINDOW) {
     if (!p.is_causal) return launch_decode_pair(decode_partial_kernel<Tag, D, QT, false, KV8, PRM>, combine, decode_lds_bytes<D, KV8>(), p, s);
@@ -672,6 +693,7 @@ static hipError_t dispatch_decode(const PRM &p0, int D, int dtype, int kv8, hipS
 hipError_t launch_decode(const DecodeParams &p, int D, int dtype, int kv8, hipStream_t s) { return dispatch_decode(p, D, dtype, kv8, s); }
 hipError_t launch_decode_paged(const DecodePagedParams &p, int D, int dtype, int kv8, hipStream_t s) { return dispatch_decode(p, D, dtype, kv8, s); }
 hipError_t launch_decode_paged_window(const DecodeWindowParams &p, int D, int dtype, int kv8, hipStream_t s) { return dispatch_decode(p, D, dtype, kv8, s); }
+hipError_t launch_decode_paged_softcap(const DecodeSoftcapParams &p, int D, int dtype, int kv8, hipStream_t s) { return dispatch_decode(p, D, dtype, kv8, s); }
 hipError_t launch_decode_paged_sink(const DecodeWindowParams &p0, const float *sinks, int D, int dtype, int kv8, hipStream_t s) {
   DecodeWindowParams p = p0;
   p.q8 = (dtype == FA_DTYPE_FP8_E4M3);

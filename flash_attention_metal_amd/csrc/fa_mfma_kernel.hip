@@ -97,6 +97,12 @@ __device__ __forceinline__ int seqlen_paged(const VarlenPagedParams &p, int b) {
 __device__ __forceinline__ int seqlen_paged(const Params &, int) { return 0; }
 __device__ __forceinline__ int paged_capacity(const VarlenPagedParams &p) { return p.max_pages << p.lp; }
 __device__ __forceinline__ int paged_capacity(const Params &) { return 0; }
+__device__ __forceinline__ float softcap_of(const VarlenSoftcapParams &p) { return p.softcap; }
+__device__ __forceinline__ float softcap_of(const VarlenPagedSoftcapParams &p) { return p.softcap; }
+__device__ __forceinline__ float softcap_of(const Params &) { return 0.0f; }
+// C = softcap . log2(e): a capped score t . softcap in log2 units is t . C (wave-uniform: it lives in a scalar register)
+template <typename PT>
+__device__ __forceinline__ float softcap_log2(const PT &p) { return softcap_of(p) * 1.4426950408889634f; }
 // Dynamic LDS of a workgroup of the body below, the figure every launcher passes: per split the K and V double buffers (K rows of D
 // bytes for e4m3 inputs, head_dim 96 rows in 256-byte slots); the epilogue's O tiles sit inside them, and the split merge buffer --
 // (16 D/32 + 2) floats per lane of the publishing waves -- behind the O tiles.
@@ -117,6 +123,12 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   // and the lower limit is new -- the tile loop starts at the tile of the block's first row's bound, a wave skips tiles wholly below
   // ITS first row's bound, and its first ACTIVE tile takes the exact path.
   constexpr bool WINDOW = std::is_base_of<VarlenWindowParams, PT>::value || std::is_base_of<VarlenPagedWindowParams, PT>::value;
+  // SOFTCAP (PT = VarlenSoftcapParams / VarlenPagedSoftcapParams; fa_fwd_varlen_softcap, fa_fwd_varlen_paged_softcap): window mode over
+  // capped scores softcap . tanh(scale . s / softcap). The query operand is pre-scaled by 2 log2(e) scale / softcap, so the matrix core
+  // delivers y with 2^y = e^(2x), the one exponential tanh needs; the score chains start from zero, not from -m. Per score: t = 1 - 2 /
+  // (1 + 2^y), THEN the mask (tanh(-inf) is -1: a key masked before the cap would weigh exp(-softcap)), then P = exp2(fma(t, C, -m)) with
+  // C = softcap . log2(e); m stays in log2 units of the capped scores, so everything from P onwards is the window mode's.
+  constexpr bool SOFTCAP = std::is_same<PT, VarlenSoftcapParams>::value || std::is_same<PT, VarlenPagedSoftcapParams>::value;
   // SINK (PT = VarlenSinkParams / VarlenPagedSinkParams; fa_fwd_varlen_sink, fa_fwd_varlen_paged_sink): window mode with one more term in
   // every row's denominator, exp(sinks[head]), which carries no value. The tile loop does not know of it: the logit is one wave-uniform
   // scalar load per block, turned to log2 units, and the epilogue folds it into (m, l) by the larger of the row's reference and the sink.
@@ -498,7 +510,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   f32x16 negm;
 #pragma unroll
   for (int i = 0; i < 16; ++i) negm[i] = 0.0f;
-  if constexpr (PRE) asm volatile("" : "+v"(negm));  // opaque: else hipcc re-materialises the splat in front of every MFMA
+  if constexpr (PRE && !SOFTCAP) asm volatile("" : "+v"(negm));  // opaque: else hipcc re-materialises the splat in front of every MFMA
 
   if constexpr (DMA) {
     if constexpr (PAGEDV) fetch_pages(tb);
@@ -522,7 +534,10 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) qf[ks][j] = (elem)((float)qf[ks][j] * c2);
+        for (int j = 0; j < 8; ++j) {
+          if constexpr (SOFTCAP) qf[ks][j] = (elem)((float)qf[ks][j] * (2.0f * c2 / softcap_of(p)));  // (softcap mode: 2 log2(e) scale / softcap)
+          else qf[ks][j] = (elem)((float)qf[ks][j] * c2);
+        }
     }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
@@ -553,6 +568,12 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
           s[kb] = M::mfma(kf, qf[ks], s[kb]);
         }
       }
+    }
+    if constexpr (SOFTCAP) {  // the cap, in front of the mask as in the tile
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[kb][i] = tanh_from_exp2_arg(s[kb][i]);
     }
     if (need_mask) {
 #pragma unroll
@@ -612,7 +633,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
           for (int i = 0; i < 16; ++i) s[kb][i] = 0.0f;
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
-            s[kb] = M::mfma(kf[kb][ks], qf[ks], (PRE && ks == 0) ? negm : s[kb]);
+            s[kb] = M::mfma(kf[kb][ks], qf[ks], (PRE && !SOFTCAP && ks == 0) ? negm : s[kb]);
             // the V blocks of all 64 keys (prefetching only keys 0..31 here and the rest under the PV MFMAs saved 16 registers
             // and was 0.5-0.9 % slower once LDS-DMA staging had freed them, profiles/r03/ab_knobs_final_build.log)
             constexpr int PER = (2 * 2 * DB) / (2 * KS);  // V block reads per QK MFMA (1 at D=64)
@@ -656,7 +677,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         for (int i = 0; i < 16; ++i) zero[i] = 0.0f;
 #pragma unroll
         for (int i = 0; i < NK; ++i) {
-          s[i / KS] = M::mfma(kf[i], qf[i % KS], (i % KS) == 0 ? (PRE ? negm : zero) : s[i / KS]);
+          s[i / KS] = M::mfma(kf[i], qf[i % KS], (i % KS) == 0 ? (PRE ? (SOFTCAP ? zero : negm) : zero) : s[i / KS]);
           if (i + LA < NK) kread(i + LA);
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -664,6 +685,12 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
       // ---- mask (only on tiles that cross the diagonal or the end of the sequence)
       // (window mode: or holds keys below the wave's last row's bound)
       const bool need_mask = (CAUSAL && (kv0 + BN - 1 > qw0 + cup)) || (kv0 + BN > FA_NK) || (WINDOW && (kv0 < qw0 + WM - 1 + cl));
+      if constexpr (SOFTCAP) {  // t = tanh(x) from y = 2 x log2(e); s holds t from here to the exponential
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) s[kb][i] = tanh_from_exp2_arg(s[kb][i]);
+      }
       if (need_mask) {
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
@@ -697,7 +724,10 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
       if (t != tfw) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          if constexpr (PRE) {  // the matrix core has already subtracted m
+          if constexpr (SOFTCAP) {  // capped score t . C against the reference (a masked t is -inf: P = 0)
+            s[0][i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[0][i], softcap_log2(p), -m));
+            s[1][i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[1][i], softcap_log2(p), -m));
+          } else if constexpr (PRE) {  // the matrix core has already subtracted m
             s[0][i] = __builtin_amdgcn_exp2f(s[0][i]);
             s[1][i] = __builtin_amdgcn_exp2f(s[1][i]);
           } else {
@@ -719,6 +749,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
           half_pair(mx, lo, hi);
           mx = fmaxf(lo, hi);
         }
+        if constexpr (SOFTCAP) mx *= softcap_log2(p);  // the largest t -> log2 units of the capped scores (C > 0; -inf stays -inf)
         // varlen, causal with Lk < Lq: a row that sees no key at all has every score masked. A finite floor keeps its reference
         // finite (-inf - -inf would be a NaN in alpha and in P): its P and l stay exactly 0 and the epilogue writes O = 0, LSE = -inf.
         // Any row with a visible key has a finite max already, so nothing changes for it.
@@ -735,7 +766,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
 #pragma unroll
           for (int i = 0; i < 16; ++i) oacc[db][i] *= alpha;
         m = m_new;
-        if constexpr (PRE) {
+        if constexpr (PRE && !SOFTCAP) {
 #pragma unroll
           for (int i = 0; i < 16; ++i) negm[i] = -m_new;
           asm volatile("" : "+v"(negm));
@@ -745,8 +776,13 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         ls1 = 0.0f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
+          if constexpr (SOFTCAP) {  // (s holds t)
+            s[0][i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[0][i], softcap_log2(p), -mc));
+            s[1][i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[1][i], softcap_log2(p), -mc));
+          } else {
           s[0][i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[0][i], cm, -mc));
           s[1][i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[1][i], cm, -mc));
+          }
           ls0 += s[0][i];
           ls1 += s[1][i];
         }
@@ -963,6 +999,16 @@ __global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_sink_pag
   fwd_mfma_body<Tag, D, true, 1, true, BM, VarlenPagedSinkParams>(p);
 }
 
+// fa_fwd_varlen_softcap / fa_fwd_varlen_paged_softcap: the two window kernels in softcap mode, at their occupancy
+template <typename Tag, int D>
+__global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_softcap_kernel(VarlenSoftcapParams p) {
+  fwd_mfma_body<Tag, D, true, 1, true, BM, VarlenSoftcapParams>(p);
+}
+template <typename Tag, int D>
+__global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_softcap_paged_kernel(VarlenPagedSoftcapParams p) {
+  fwd_mfma_body<Tag, D, true, 1, true, BM, VarlenPagedSoftcapParams>(p);
+}
+
 // fa_fwd_varlen_paged_kv8: the paged window / sink kernels in KV8 mode (bf16 queries, e4m3 pools), at their occupancy: the 8 / 16 staging
 // registers fit (168 / 222 VGPR, no scratch)
 template <int D>
@@ -1050,6 +1096,18 @@ hipError_t launch_mfma_varlen_sink(const VarlenSinkParams &p, int dtype, hipStre
 hipError_t launch_mfma_varlen_paged_sink(const VarlenPagedSinkParams &p, int dtype, hipStream_t s) {
   return with_tag(dtype, [&](auto tag) {
     return with_dim<64, 128>(p.D, [&](auto d) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_sink_paged_kernel<decltype(tag), d()>, p, s); });
+  });
+}
+
+hipError_t launch_mfma_varlen_softcap(const VarlenSoftcapParams &p, int dtype, hipStream_t s) {
+  return with_tag(dtype, [&](auto tag) {
+    return with_dim<64, 128>(p.D, [&](auto d) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_softcap_kernel<decltype(tag), d()>, p, s); });
+  });
+}
+
+hipError_t launch_mfma_varlen_paged_softcap(const VarlenPagedSoftcapParams &p, int dtype, hipStream_t s) {
+  return with_tag(dtype, [&](auto tag) {
+    return with_dim<64, 128>(p.D, [&](auto d) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_softcap_paged_kernel<decltype(tag), d()>, p, s); });
   });
 }
 

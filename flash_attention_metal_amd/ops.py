@@ -261,6 +261,16 @@ def _sink_window(window, is_causal: bool) -> Tuple[int, int]:
     return ((-1, 0) if is_causal else (-1, -1)) if window is None else _window(window, is_causal)
 
 
+def _softcap(softcap, sinks) -> Optional[float]:
+    """The cap of a *_softcap entry point (include/fa_mi355.h, "Logit soft-capping"): None or 0.0 is the call without a cap; otherwise a
+    finite positive host scalar (the library refuses anything else), which does not combine with sinks."""
+    if softcap is None or float(softcap) == 0.0:
+        return None
+    if sinks is not None:
+        raise ValueError("softcap together with sinks is not supported")
+    return float(softcap)
+
+
 def decode_paged_workspace_bytes(B: int, Hq: int, Hkv: int, Nq: int, D: int, page_size: int, max_pages_per_seq: int) -> int:
     return int(load_library().fa_fwd_decode_paged_workspace_bytes(B, Hq, Hkv, Nq, D, page_size, max_pages_per_seq))
 
@@ -281,6 +291,7 @@ def flash_attention_decode_paged(
     stream: Optional[int] = None,
     window: Optional[Tuple[int, int]] = None,
     sinks: Optional[torch.Tensor] = None,
+    softcap: Optional[float] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """A decode step against a paged KV cache (include/fa_mi355.h fa_fwd_decode_paged): q [B,Hq,Nq,D]; k_pages / v_pages one pool
     each, [num_pages, Hkv, P, D] (layout "HND") or [num_pages, P, Hkv, D] ("NHD"), P in {16, 32, 64, 128, 256}; block_table int32
@@ -291,8 +302,11 @@ def flash_attention_decode_paged(
     window=(left, right): a sliding window (fa_fwd_decode_paged_window: key j visible to query i iff i + L_b - Nq - left <= j <=
     i + L_b - Nq + right; negative = unbounded; with is_causal=True right must be 0 or negative). None: the call above, untouched.
     sinks: a [Hq] tensor of per-head sink logits (fa_fwd_decode_paged_sink: exp(sinks[h]) joins every softmax denominator of head h and
-    carries no value; a row with no visible key then gets O = 0 and LSE = sinks[h]). None: the calls above, untouched."""
+    carries no value; a row with no visible key then gets O = 0 and LSE = sinks[h]). None: the calls above, untouched.
+    softcap: a finite positive float (fa_fwd_decode_paged_softcap: every score becomes softcap * tanh(scale * s / softcap) before the mask
+    and the softmax; window=None is then (-1, 0) under is_causal, else (-1, -1); not together with sinks). None or 0.0: the calls above."""
     lib = load_library()
+    cap = _softcap(softcap, sinks)  # (first: a cap that cannot be served is refused whatever else is wrong)
     if q.dim() != 4 or k_pages.dim() != 4 or k_pages.shape != v_pages.shape:
         raise ValueError("q [B,Hq,Nq,D], k_pages / v_pages one [num_pages,Hkv,P,D] (HND) or [num_pages,P,Hkv,D] (NHD) shape")
     if layout not in ("HND", "NHD"):
@@ -325,6 +339,8 @@ def flash_attention_decode_paged(
     if sinks is not None:
         sinks = _sinks(sinks, Hq, q.device)
         entry, mask = "fa_fwd_decode_paged_sink", _sink_window(window, is_causal) + (sinks.data_ptr(),)
+    if cap is not None:
+        entry, mask = "fa_fwd_decode_paged_softcap", _sink_window(window, is_causal) + (cap,)
     _call(lib, entry,
           (q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(), _ptr(lse), block_table.data_ptr(), seqlens_k.data_ptr(),
            B, Hq, Hkv, Nq, D, P, num_pages, max_pages, _scale(scale, D), *qs, ps, hs, rs, block_table.stride(0), *mask,
@@ -352,6 +368,7 @@ def flash_attention_varlen(
     stream: Optional[int] = None,
     window: Optional[Tuple[int, int]] = None,
     sinks: Optional[torch.Tensor] = None,
+    softcap: Optional[float] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """The forward over packed variable-length sequences (include/fa_mi355.h fa_fwd_varlen): q [total_q, Hq, D], k / v
     [total_k, Hkv, D], f16 / bf16, D = 64 | 128. Strides are taken from the tensors: any view with unit element stride works ([H, total, D]
@@ -365,8 +382,12 @@ def flash_attention_varlen(
     None: the call above, untouched. sinks: a [Hq] tensor of per-head sink logits (fa_fwd_varlen_sink: exp(sinks[h]) joins every softmax
     denominator of head h and carries no value -- natural-log units, the scale is not applied to it; a row with no visible key then gets
     O = 0 and LSE = sinks[h]; window=None with sinks is (-1, 0) under is_causal, else (-1, -1)); None: the calls above, untouched.
+    softcap: a finite positive float (fa_fwd_varlen_softcap, "Logit soft-capping": every score becomes softcap * tanh(scale * s / softcap)
+    before the mask and the softmax, LSE is that of the capped scores; window=None is then (-1, 0) under is_causal, else (-1, -1); not
+    together with sinks); None or 0.0: the calls above, untouched.
     Returns (out, lse): out like q ([total_q, Hq, D], q's strides unless `out` is given), lse [Hq, total_q]."""
     lib = load_library()
+    cap = _softcap(softcap, sinks)  # (first: a cap that cannot be served is refused whatever else is wrong)
     if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape:
         raise ValueError(f"q [total_q,Hq,D] and k, v one [total_k,Hkv,D] shape, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
     total_q, Hq, D = q.shape
@@ -400,6 +421,8 @@ def flash_attention_varlen(
     if sinks is not None:
         sinks = _sinks(sinks, Hq, q.device)
         entry, mask = "fa_fwd_varlen_sink", _sink_window(window, is_causal) + (sinks.data_ptr(),)
+    if cap is not None:
+        entry, mask = "fa_fwd_varlen_softcap", _sink_window(window, is_causal) + (cap,)
     _call(lib, entry,
           (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
            B, Hq, Hkv, total_q, total_k, int(max_seqlen_q), int(max_seqlen_k), D, _scale(scale, D), q.stride(0), q.stride(1),
@@ -459,6 +482,7 @@ def flash_attention_varlen_paged(
     stream: Optional[int] = None,
     window: Optional[Tuple[int, int]] = None,
     sinks: Optional[torch.Tensor] = None,
+    softcap: Optional[float] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Packed queries against a paged KV cache (include/fa_mi355.h fa_fwd_varlen_paged): chunked prefill, prefix caching, verification of
     many speculated tokens. q [total_q, Hq, D] as in flash_attention_varlen (any view with a unit element stride), cu_seqlens_q int32
@@ -473,8 +497,10 @@ def flash_attention_varlen_paged(
     (fa_fwd_varlen_paged_sink); None: the calls above, untouched. bf16 q on float8_e4m3fn pools (fa_fwd_varlen_paged_kv8, "e4m3 pools in
     the prefill"): the pool of flash_attention_decode_paged, read as plain e4m3 values -- no scales: fold a K scale into `scale`, a V scale
     into what consumes `out`; window, is_causal and sinks mean what they mean with sinks, and the result is bit for bit the bf16 call on
-    the widened pool. Returns (out, lse): out like q, lse [Hq, total_q]."""
+    the widened pool. softcap: as in flash_attention_varlen (fa_fwd_varlen_paged_softcap; f16 / bf16 pools only: with sinks or with e4m3
+    pools it raises ValueError); None or 0.0: the calls above, untouched. Returns (out, lse): out like q, lse [Hq, total_q]."""
     lib = load_library()
+    cap = _softcap(softcap, sinks)  # (first: a cap that cannot be served is refused whatever else is wrong)
     entry = "flash_attention_varlen_paged"
     if q.dim() != 3:
         raise ValueError(f"q [total_q,Hq,D], got {tuple(q.shape)}")
@@ -483,6 +509,8 @@ def flash_attention_varlen_paged(
     if Dk != D or Hkv < 1 or Hq % Hkv:
         raise ValueError(f"incompatible q {tuple(q.shape)} and pools {tuple(k_pages.shape)} (same D, Hq % Hkv == 0)")
     kv8 = _FP8 is not None and q.dtype == torch.bfloat16 and k_pages.dtype == _FP8
+    if cap is not None and kv8:
+        raise ValueError("softcap on float8_e4m3fn pools is not supported in the prefill (fa_fwd_varlen_paged_kv8 has no cap)")
     if not kv8 and (q.dtype not in (torch.float16, torch.bfloat16) or k_pages.dtype != q.dtype):
         raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k_pages.dtype} {v_pages.dtype} (f16 or bf16, q and the pools alike; or bf16 q "
                          "on float8_e4m3fn pools)")
@@ -504,6 +532,8 @@ def flash_attention_varlen_paged(
     if sinks is not None:
         sinks = _sinks(sinks, Hq, q.device)
         entry, mask = "fa_fwd_varlen_paged_sink", _sink_window(window, is_causal) + (sinks.data_ptr(),)
+    if cap is not None:
+        entry, mask = "fa_fwd_varlen_paged_softcap", _sink_window(window, is_causal) + (cap,)
     dtypes = (_TORCH2FA[q.dtype],)
     if kv8:  # one entry point with or without sinks; the mask as the sink path maps it
         entry, mask = "fa_fwd_varlen_paged_kv8", _sink_window(window, is_causal) + (_ptr(sinks),)
@@ -590,6 +620,7 @@ def flash_attention_varlen_backward(
     window: Optional[Tuple[int, int]] = None,
     sinks: Optional[torch.Tensor] = None,
     dsinks: Optional[torch.Tensor] = None,
+    softcap: Optional[float] = None,
 ):
     """The backward over packed variable-length sequences (include/fa_mi355.h fa_bwd_varlen), the counterpart of
     flash_attention_varlen: q, o, d_o [total_q, Hq, D] under one set of strides, k, v [total_k, Hkv, D] under another, f16 / bf16,
@@ -604,8 +635,11 @@ def flash_attention_varlen_backward(
     query sees gets dK = dV = 0. None: the call above, untouched.
     sinks: the [Hq] sink logits of the forward that wrote o and lse (fa_bwd_varlen_sink). The call then returns (dq, dk, dv, dsinks):
     dsinks fp32 [Hq] (written, not accumulated; allocated unless given), dq / dk / dv bit for bit those of the call without sinks on the
-    same tensors. None: the calls above, untouched, three gradients."""
+    same tensors. None: the calls above, untouched, three gradients.
+    softcap: the cap of the forward that wrote o and lse (fa_bwd_varlen_softcap: dS = P (dP - delta) (1 - tanh^2); the cap itself gets no
+    gradient; not together with sinks). None or 0.0: the calls above, untouched."""
     lib = load_library()
+    cap = _softcap(softcap, sinks)  # (first: a cap that cannot be served is refused whatever else is wrong)
     if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or o.shape != q.shape or d_o.shape != q.shape:
         raise ValueError(f"q, o, d_o one [total_q,Hq,D] shape and k, v one [total_k,Hkv,D] shape, got {tuple(q.shape)} {tuple(o.shape)} "
                          f"{tuple(d_o.shape)} {tuple(k.shape)} {tuple(v.shape)}")
@@ -655,6 +689,8 @@ def flash_attention_varlen_backward(
         entry, mask = "fa_bwd_varlen_sink", _sink_window(window, is_causal) + (sinks.data_ptr(), dsinks.data_ptr())
     elif dsinks is not None:
         raise ValueError("dsinks without sinks")
+    if cap is not None:
+        entry, mask = "fa_bwd_varlen_softcap", _sink_window(window, is_causal) + (cap,)
     _call(lib, entry,
           (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
            dv.data_ptr(), ws.data_ptr(), cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), B, Hq, Hkv, total_q, total_k,

@@ -254,11 +254,75 @@ def _varlen_sink_backward(ctx, grad_o, grad_lse):
 torch.library.register_autograd("fa_mi355::attention_varlen_sink", _varlen_sink_backward, setup_context=_varlen_sink_setup_context, lib=_LIB)
 
 
+_LIB.define("attention_varlen_softcap(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor cu_seqlens_k, int max_seqlen_q, "
+            "int max_seqlen_k, int window_left, int window_right, float softcap, float scale=0.0) -> (Tensor, Tensor)")
+
+
+def _varlen_softcap_impl(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window_left, window_right, softcap, scale=0.0):
+    if not softcap > 0:  # (0.0 would quietly be the call without a cap in the wrapper)
+        raise ValueError("fa_mi355::attention_varlen_softcap: softcap must be finite and > 0")
+    out = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device).zero_()
+    lse = torch.full((q.shape[1], q.shape[0]), float("-inf"), dtype=torch.float32, device=q.device)
+    return flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale=(scale if scale > 0 else None),
+                                  out=out, lse=lse, window=(window_left, window_right), softcap=softcap)
+
+
+def _varlen_softcap_meta(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window_left, window_right, softcap, scale=0.0):
+    return torch.empty_like(q), q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32)
+
+
+_LIB.impl("attention_varlen_softcap", _varlen_softcap_impl, "CUDA")
+_LIB.impl("attention_varlen_softcap", _varlen_softcap_meta, "Meta")
+
+
+def _varlen_softcap_setup_context(ctx, inputs, output):
+    q, k, v, cu_q, cu_k, max_q, max_k, window_left, window_right, softcap, scale = inputs
+    o, lse = output
+    ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k)
+    ctx.max_q, ctx.max_k, ctx.window, ctx.scale = int(max_q), int(max_k), (int(window_left), int(window_right)), float(scale)
+    ctx.softcap = float(softcap)
+    ctx.set_materialize_grads(False)
+
+
+def _varlen_softcap_backward(ctx, grad_o, grad_lse):
+    q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
+    if grad_lse is not None:
+        raise NotImplementedError("fa_mi355::attention_varlen_softcap: no gradient through the LSE output")
+    none = (None,) * 11  # (the cap is a host scalar: no gradient)
+    if grad_o is None:
+        return none
+    if q.dtype not in _TORCH2FA or not load_library().fa_bwd_varlen_supported(_TORCH2FA[q.dtype], q.shape[2]):
+        raise FaError(-2, f"no varlen backward kernel for q {tuple(q.shape)} {q.dtype} (f16 / bf16, head_dim 64 or 128)", "fa_bwd_varlen_softcap")
+    go = grad_o.to(o.dtype)
+    if go.stride() != q.stride():  # d_o is addressed under q's strides
+        go = torch.empty_strided(q.shape, q.stride(), dtype=o.dtype, device=q.device).copy_(go)
+    if o.stride() != q.stride():
+        o = torch.empty_strided(q.shape, q.stride(), dtype=o.dtype, device=q.device).copy_(o)
+    # zero-initialised: tokens owned by no sequence are not written by the kernels and get a zero gradient
+    dq = torch.empty_strided(q.shape, q.stride(), dtype=torch.float32, device=q.device).zero_()
+    dk = torch.empty_strided(k.shape, k.stride(), dtype=torch.float32, device=q.device).zero_()
+    dv = torch.empty_strided(k.shape, k.stride(), dtype=torch.float32, device=q.device).zero_()
+    flash_attention_varlen_backward(q, k, v, o, go, lse, cu_q, cu_k, ctx.max_q, ctx.max_k, scale=(ctx.scale if ctx.scale > 0 else None),
+                                    dq=dq, dk=dk, dv=dv, window=ctx.window, softcap=ctx.softcap)
+    return (dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)) + none[3:]
+
+
+torch.library.register_autograd("fa_mi355::attention_varlen_softcap", _varlen_softcap_backward, setup_context=_varlen_softcap_setup_context,
+                                lib=_LIB)
+
+
 def attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_seqlen_k: int, is_causal: bool = False, scale: float = 0.0,
-                     window=None, sinks=None):
+                     window=None, sinks=None, softcap=None):
     """window=(left, right): fa_mi355::attention_varlen_window (differentiable through fa_bwd_varlen_window); None: the op above.
     sinks=[Hq] logits: fa_mi355::attention_varlen_sink (differentiable in q, k, v and sinks; window=None is (-1, 0) under is_causal, else
-    (-1, -1))."""
+    (-1, -1)). softcap=a positive float: fa_mi355::attention_varlen_softcap (differentiable in q, k, v through fa_bwd_varlen_softcap; the
+    window maps as with sinks; not together with sinks); None or 0.0: the ops above."""
+    if softcap is not None and float(softcap) != 0.0:
+        if sinks is not None:
+            raise ValueError("softcap together with sinks is not supported")
+        left, right = _sink_window(window, is_causal)
+        return torch.ops.fa_mi355.attention_varlen_softcap(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, left, right,
+                                                           float(softcap), scale)
     if sinks is not None:
         left, right = _sink_window(window, is_causal)
         return torch.ops.fa_mi355.attention_varlen_sink(q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, left, right, scale)

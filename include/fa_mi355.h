@@ -636,6 +636,76 @@ int fa_kv_append_paged_quant(const void *k_new, const void *v_new, void *k_pages
                              long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
                              long long block_table_stride, int new_dtype, float k_mul, float v_mul, void *hip_stream);
 
+/*
+ * Logit soft-capping: fa_fwd_varlen_softcap, fa_fwd_varlen_paged_softcap, fa_fwd_decode_paged_softcap and fa_bwd_varlen_softcap are the
+ * four *_window entry points with `float softcap` added directly behind window_right (where the sink calls take `sinks`), for models that
+ * cap their attention logits (Gemma-2: head_dim 128, grouped heads, a window of 4096 alternating with full causal layers, a cap of 50).
+ * With x_ij = scale * s_ij / softcap and t_ij = tanh(x_ij) the capped score
+ *     s'_ij = softcap * t_ij
+ * takes the place of scale * s_ij everywhere: P_ij = exp(s'_ij) / sum_{j' visible} exp(s'_ij'), O_i = sum_j P_ij v_j, and LSE is that of the
+ * capped scores. `softcap` is a HOST scalar and must be finite and greater than 0, else FA_ERR_INVALID_ARG ("softcap must be finite and
+ * > 0"). Visibility is the rule of "Sliding window", unchanged, and it is applied AFTER the cap: tanh(-inf) is -1, not -inf, so a key
+ * masked before the cap would enter the softmax with weight exp(-softcap). A row without a visible key (that section's integer test) gets
+ * O = 0 and LSE = -inf, as there.
+ * Each call goes through its *_window sibling's one validation and launch path: every shared rule keeps its status code and its error
+ * text; support tables, the decode workspace and the backward workspace are the siblings' (the decode takes all four dtype pairs of
+ * fa_fwd_decode_paged; the prefill calls and the backward take f16 / bf16 with D = 64 | 128).
+ * ROUTING follows the sink forwards: the softcap forwards ALWAYS run one kernel family, the window-mode kernels in a softcap mode (eight
+ * 128-row kernels, twelve decode partial kernels; the decode's combine kernels run unchanged, they see only (acc, m, l)), and the backward
+ * always runs its windowed kernels in their softcap mode (eight kernels). An unbounded or never-binding side is clamped on the host, so
+ * (-1, 0) is the capped causal layer and (4095, 0) the capped window layer. Not combined with sinks, and not offered on e4m3 pools in the
+ * prefill (fa_fwd_varlen_paged_kv8), on the dense fa_fwd / fa_fwd_ex / fa_fwd_decode / fa_bwd, or at head_dim 256.
+ * How the kernels form it: the operand held in registers (Q~; K~ in the dK/dV kernel) is pre-scaled once per block by
+ * 2 * log2(e) * scale / softcap instead of scale * log2(e), so the matrix core delivers y with 2^y = e^(2x), the argument of the one
+ * exponential tanh needs, and the score chain starts from zero instead of from the row's reference. Per score
+ *     t = 1 - 2 / (1 + 2^y)          (one v_exp_f32, one v_rcp_f32; finite at both ends: 2^y = inf gives 1, 2^y = 0 gives -1)
+ * then the mask, then P = exp2(fma(t, C, -m)) with C = softcap * log2(e) and m the row's reference in log2 units of the capped scores
+ * (backward: -lse * log2(e) in m's place). Everything from P onwards is the window mode's code. The paged prefill is BIT-IDENTICAL to the
+ * packed softcap call on every sequence with L_b >= Lq_b >= 1, as without a cap.
+ * Backward: with the forward's LSE, P = exp(softcap * t - lse) and delta = rowsum(dO o O) is unchanged; the gradient with respect to the raw
+ * score is dS_ij = P_ij * (dP_ij - delta_i) * (1 - t_ij^2), dQ = scale * dS K and dK = scale * dS^T Q are the existing final multiplies,
+ * dV = P^T dO. The cap gets no gradient. delta and the write rules are fa_bwd_varlen_window's: owned tokens only, a key no query sees gets
+ * dK = dV = 0, a dead row dQ = 0.
+ * Accuracy. |d(softcap * tanh(x)) / d(scale * s)| = 1 - t^2 <= 1: the one rounding of the pre-scaled operand moves a capped score by no more
+ * than it moved the raw one, so "LSE accuracy" (lse_tol, o_tol) and "Backward accuracy" stay valid upper bounds with their pre-scale terms
+ * as they are. New is the evaluation of tanh in four fp32 steps (the exponential, 1 + e, the reciprocal, the fma): with u = 2^-24 and the
+ * two hardware instructions within eps = 3 u (half an ulp plus the one ulp they may be off by),
+ *     tanh_err = eps / 2 + 2 eps + 3 u = 10.5 * 2^-24 = 6.3e-7          (correctly rounded steps: 5.5 * 2^-24; measured in numpy: 1.9e-7)
+ *     |LSE - exact| <= lse_tol + softcap * tanh_err          |O_d - exact| <= o_tol + |O_d| * softcap * tanh_err
+ * and in the backward the per-element bound E_ij of "Backward accuracy", formed on g_ij = P_ij (dP_ij - delta_i), becomes
+ *     E'_ij = E_ij * (1 - t_ij^2) + |g_ij| * (2 |t_ij| tanh_err + 2^-23)
+ * (the factor 1 - t^2 scales what was there; t off by tanh_err moves the factor by 2 |t| tanh_err, and forming and applying it rounds
+ * twice). tests/softcap.py spells every term out, tests/test_softcap_cases.py holds an fp32 model of the kernels' arithmetic to the bars
+ * and shows eight planted mistakes to break them, tests/test_gpu_softcap.py and test_gpu_softcap_bwd.py hold the kernels.
+ */
+int fa_fwd_varlen_softcap(const void *q, const void *k, const void *v, void *o, float *lse,
+                          const int *cu_seqlens_q, const int *cu_seqlens_k,
+                          int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k,
+                          int D, float scale, long long q_row_stride, long long q_head_stride,
+                          long long kv_row_stride, long long kv_head_stride,
+                          int window_left, int window_right, float softcap, int dtype, void *hip_stream);
+int fa_fwd_varlen_paged_softcap(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                                const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                                int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                                int page_size, int num_pages, int max_pages_per_seq, float scale,
+                                long long q_row_stride, long long q_head_stride,
+                                long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                                long long block_table_stride, int window_left, int window_right, float softcap, int dtype,
+                                void *hip_stream);
+int fa_fwd_decode_paged_softcap(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                                const int *block_table, const int *seqlens_k,
+                                int B, int Hq, int Hkv, int Nq, int D, int page_size, int num_pages, int max_pages_per_seq,
+                                float scale, long long q_batch_stride, long long q_head_stride,
+                                long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                                long long block_table_stride, int window_left, int window_right, float softcap,
+                                int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes, void *hip_stream);
+int fa_bwd_varlen_softcap(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse,
+                          float *dq, float *dk, float *dv, void *workspace,
+                          const int *cu_seqlens_q, const int *cu_seqlens_k,
+                          int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
+                          long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
+                          int window_left, int window_right, float softcap, int dtype, void *hip_stream);
+
 /* 1 if fa_fwd has a kernel for the combination, else 0 (no GPU needed). */
 int fa_supported(int dtype, int variant, int D);
 
