@@ -31,6 +31,8 @@ from .ops import (  # noqa: F401
     varlen_backward_supported,
     varlen_backward_workspace_bytes,
     varlen_paged_kv8_supported,
+    varlen_paged_num_splits,
+    varlen_paged_split_workspace_bytes,
     varlen_paged_supported,
     varlen_supported,
 )

@@ -40,6 +40,10 @@ SYMBOLS = {
                                     + [c_void_p, c_longlong, c_void_p]),
     "fa_fwd_varlen_paged_kv8": (c_int, [c_void_p] * 8 + [c_int] * 9 + [c_float] + [c_longlong] * 6 + [c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "fa_fwd_varlen_paged_kv8_supported": (c_int, [c_int] * 4),
+    "fa_fwd_varlen_paged_split": (c_int, [c_void_p] * 8 + [c_int] * 9 + [c_float] + [c_longlong] * 6
+                                  + [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p]),
+    "fa_fwd_varlen_paged_num_splits": (c_int, [c_int] * 6),
+    "fa_fwd_varlen_paged_split_workspace_bytes": (c_longlong, [c_int] * 8),
     "fa_kv_append_paged_quant": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_longlong] * 6 + [c_int, c_float, c_float, c_void_p]),
     "fa_window_key_range": (c_int, [c_int] * 6 + [c_void_p, c_void_p]),
     "fa_kv_append_paged": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_longlong] * 6 + [c_int, c_void_p]),

@@ -660,12 +660,40 @@ int fa_fwd_decode_paged_softcap(const void *q, const void *k_pages, const void *
 }
 
 int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size) { return fa::mfma_varlen_paged_supported(dtype, D, page_size); }
+// the key split's scalars: sizes >= 1, a head_dim and a page size the paged prefill has, a capacity of at most 2^30 keys
+static bool ksplit_scalars_ok(int B, int Hq, int max_seqlen_q, int D, int page_size, int max_pages_per_seq) {
+  return B >= 1 && Hq >= 1 && max_seqlen_q >= 1 && (D == 64 || D == 128) && fa::page_size_ok(page_size) && max_pages_per_seq >= 1 &&
+         (long long)page_size * max_pages_per_seq <= (1 << 30) && (long long)B * Hq <= 0x7fffffffLL / (((long long)max_seqlen_q + 127) / 128);  // (64-bit: any int is a legal argument)
+}
+int fa_fwd_varlen_paged_num_splits(int B, int Hq, int max_seqlen_q, int D, int page_size, int max_pages_per_seq) {
+  if (!ksplit_scalars_ok(B, Hq, max_seqlen_q, D, page_size, max_pages_per_seq)) return 0;
+  return fa::varlen_paged_ksplit_splits(B, Hq, max_seqlen_q, D, page_size, max_pages_per_seq);
+}
+long long fa_fwd_varlen_paged_split_workspace_bytes(int B, int Hq, int total_q, int max_seqlen_q, int D, int page_size, int max_pages_per_seq,
+                                                    int num_splits) {
+  if (!ksplit_scalars_ok(B, Hq, max_seqlen_q, D, page_size, max_pages_per_seq) || total_q < max_seqlen_q || num_splits < 0 ||
+      num_splits > FA_VARLEN_PAGED_MAX_SPLITS)
+    return 0;
+  const int S = num_splits ? num_splits : fa::varlen_paged_ksplit_splits(B, Hq, max_seqlen_q, D, page_size, max_pages_per_seq);
+  if (S < 2) return 0;
+  const long long rows = (long long)Hq * total_q, per_row = (long long)S * (D + 1) * 4;  // rows < 2^62, per_row <= 64 * 129 * 4
+  if (rows > (0x7fffffffffffffffLL - 15) / per_row) return 0;                             // no such size: invalid, like the other zeros
+  return (rows * per_row + 15) / 16 * 16;
+}
+struct KsplitArgs {
+  int num_splits;
+  void *workspace;
+  long long workspace_bytes;
+};
 static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
                              const int *cu_seqlens_q, const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q,
                              int max_seqlen_q, int D, int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride,
                              long long q_head_stride, long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
                              long long block_table_stride, int window_left, int window_right, int dtype, void *hip_stream,
-                             const float *const *sinks = nullptr, const int *kv8_dtype = nullptr, const float *softcap = nullptr) {
+                             const float *const *sinks = nullptr, const int *kv8_dtype = nullptr, const float *softcap = nullptr,
+                             const KsplitArgs *ksplit = nullptr) {
+  // ksplit (fa_fwd_varlen_paged_split): every rule below first, then the split count's range and -- where it resolves to two or more --
+  // the workspace. Routing is the sink calls': always the window family. One split launches that family's kernel and nothing else.
   // kv8_dtype (fa_fwd_varlen_paged_kv8): `dtype` is q's and *kv8_dtype the pools'. Every rule below is the one path of both families;
   // what differs is the support table with its text, the pools' stride multiple and bytes per element (page_pool_ok under the pools'
   // type), and the routing: that call always runs its own kernel family, with or without sinks.
@@ -691,8 +719,21 @@ static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages,
   TRY(aligned16(fn, "tensors", {q, k_pages, v_pages, o}));
   if ((uintptr_t)cu_seqlens_q & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q must be int32-aligned", fn);
   TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
+  int S = 1;
+  if (ksplit) {  // (in front of the grid rule, the last one: a call that is right up to there has been through these)
+    if (ksplit->num_splits < 0 || ksplit->num_splits > FA_VARLEN_PAGED_MAX_SPLITS)
+      return fail(FA_ERR_INVALID_ARG, "%s: num_splits=%d must be 0 (the heuristic) .. %d", fn, ksplit->num_splits, FA_VARLEN_PAGED_MAX_SPLITS);
+    S = ksplit->num_splits ? ksplit->num_splits : fa::varlen_paged_ksplit_splits(B, Hq, max_seqlen_q, D, page_size, max_pages_per_seq);
+    if (S >= 2) {
+      if (!ksplit->workspace) return fail(FA_ERR_INVALID_ARG, "%s: null pointer", fn);
+      TRY(aligned16(fn, "workspace", {ksplit->workspace}));
+      TRY(workspace_fits(fn, ksplit->workspace_bytes,
+                         fa_fwd_varlen_paged_split_workspace_bytes(B, Hq, total_q, max_seqlen_q, D, page_size, max_pages_per_seq, S),
+                         "fa_fwd_varlen_paged_split_workspace_bytes"));
+    }
+  }
   TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));
-  const int route = (sinks || kv8_dtype || softcap) ? WIN_KERNEL : window_route(window_left, window_right);
+  const int route = (sinks || kv8_dtype || softcap || ksplit) ? WIN_KERNEL : window_route(window_left, window_right);
   fa::VarlenPagedSinkParams p;
   p.q = q; p.k = k_pages; p.v = v_pages; p.o = o; p.lse = lse;
   p.B = B; p.H = Hq; p.Hkv = Hkv; p.N = max_seqlen_q; p.Nk = page_size * max_pages_per_seq; p.D = D; p.scale = scale;
@@ -716,6 +757,12 @@ static int varlen_paged_impl(const char *fn, const void *q, const void *k_pages,
     return launched(fn, fa::launch_mfma_varlen_paged_softcap(pc, dtype, (hipStream_t)hip_stream));
   }
   if (kv8_dtype) return launched(fn, fa::launch_mfma_varlen_paged_kv8(p, sinks != nullptr, (hipStream_t)hip_stream));
+  if (S >= 2) {
+    fa::VarlenPagedKsplitParams pk;
+    static_cast<fa::VarlenPagedWindowParams &>(pk) = p;
+    pk.sinks = p.sinks; pk.ws = (float *)ksplit->workspace; pk.S = S;
+    return launched(fn, fa::launch_mfma_varlen_paged_ksplit(pk, dtype, (hipStream_t)hip_stream));
+  }
   if (!sinks) return launched(fn, fa::launch_mfma_varlen_paged_window(p, dtype, (hipStream_t)hip_stream));
   return launched(fn, fa::launch_mfma_varlen_paged_sink(p, dtype, (hipStream_t)hip_stream));
 }
@@ -757,6 +804,19 @@ int fa_fwd_varlen_paged_softcap(const void *q, const void *k_pages, const void *
                            total_q, max_seqlen_q, D, page_size, num_pages, max_pages_per_seq, scale, q_row_stride, q_head_stride,
                            kv_page_stride, kv_head_stride, kv_row_stride, block_table_stride, window_left, window_right, dtype, hip_stream,
                            nullptr, nullptr, &softcap);
+}
+int fa_fwd_varlen_paged_split(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse, const int *cu_seqlens_q,
+                              const int *block_table, const int *seqlens_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                              int page_size, int num_pages, int max_pages_per_seq, float scale, long long q_row_stride,
+                              long long q_head_stride, long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                              long long block_table_stride, int window_left, int window_right, const float *sinks, int dtype,
+                              int num_splits, void *workspace, long long workspace_bytes, void *hip_stream) {
+  // sinks may be NULL, as in fa_fwd_varlen_paged_kv8
+  const KsplitArgs ks = {num_splits, workspace, workspace_bytes};
+  return varlen_paged_impl("fa_fwd_varlen_paged_split", q, k_pages, v_pages, o, lse, cu_seqlens_q, block_table, seqlens_k, B, Hq, Hkv, total_q,
+                           max_seqlen_q, D, page_size, num_pages, max_pages_per_seq, scale, q_row_stride, q_head_stride, kv_page_stride,
+                           kv_head_stride, kv_row_stride, block_table_stride, window_left, window_right, dtype, hip_stream,
+                           sinks ? &sinks : nullptr, nullptr, nullptr, &ks);
 }
 int fa_fwd_varlen_paged_kv8_supported(int q_dtype, int kv_dtype, int D, int page_size) {
   return fa::mfma_varlen_paged_kv8_supported(q_dtype, kv_dtype, D, page_size);

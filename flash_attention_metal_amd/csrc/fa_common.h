@@ -121,6 +121,23 @@ struct VarlenPagedSinkParams : VarlenPagedWindowParams {
 struct VarlenPagedKv8Params : VarlenPagedWindowParams {};
 struct VarlenPagedKv8SinkParams : VarlenPagedSinkParams {};
 
+// the key-split mode of the paged window mode (fa_fwd_varlen_paged_split; include/fa_mi355.h, "Key split in the paged prefill"): the
+// windowed call's parameters plus the split count S >= 2 and the caller's workspace. Split s (= blockIdx.y of the partial grid) of a
+// block walks the tiles ksplit_tiles gives it and leaves, per owned row, the normalised state (o_s = acc / l in fp32, lse2_s = m + log2 l)
+// in the workspace: [S][H * total_q][D] floats of o_s, then [S][H * total_q] floats of lse2_s, row index hq * total_q + token as in LSE.
+// The combine kernel takes the same parameters (o, lse, cu_q, sinks).
+struct VarlenPagedKsplitParams : VarlenPagedWindowParams {
+  const float *sinks;  // [H] or nullptr: read by the combine kernel only
+  float *ws;
+  int S;
+};
+// tiles [t0, t1) of split s of S over a block whose tile range is [tb, nT): the decode's rule per block, n = nT - tb <= 2^24, S <= 64
+__host__ __device__ inline void ksplit_tiles(int tb, int nT, int s, int S, int &t0, int &t1) {
+  const unsigned n = (unsigned)(nT - tb);
+  t0 = tb + (int)((unsigned)s * n / (unsigned)S);
+  t1 = tb + (int)((unsigned)(s + 1) * n / (unsigned)S);
+}
+
 // the softcap modes of the windowed modes (fa_fwd_varlen_softcap, fa_fwd_varlen_paged_softcap; include/fa_mi355.h, "Logit soft-capping"):
 // the windowed call's parameters plus the cap, a finite positive host scalar. Every score becomes softcap * tanh(scale * s / softcap)
 // before the mask; the kernels pre-scale the query operand by 2 log2(e) scale / softcap instead of scale log2(e).
@@ -205,6 +222,10 @@ hipError_t launch_mfma_varlen_paged_softcap(const VarlenPagedSoftcapParams &p, i
 // fa_fwd_varlen_paged_kv8: bf16 queries on e4m3 pools, always the KV8 window-mode kernels (with_sink: p.sinks is read, their sink mode)
 hipError_t launch_mfma_varlen_paged_kv8(const VarlenPagedSinkParams &p, bool with_sink, hipStream_t s);
 bool mfma_varlen_paged_kv8_supported(int q_dtype, int kv_dtype, int D, int page_size);
+// fa_fwd_varlen_paged_split with S >= 2: the key-split partial kernel on the block map times S, then the combine kernel on the block map
+hipError_t launch_mfma_varlen_paged_ksplit(const VarlenPagedKsplitParams &p, int dtype, hipStream_t s);
+// the split count fa_fwd_varlen_paged_num_splits answers (host scalars only; arguments already validated)
+int varlen_paged_ksplit_splits(int B, int Hq, int max_seqlen_q, int D, int page_size, int max_pages_per_seq);
 // fa_kv_append_paged (csrc/fa_decode_kernel.hip): a byte copy of new K / V rows into their slots of the page pools
 struct AppendPagedParams {
   const void *k_new, *v_new;

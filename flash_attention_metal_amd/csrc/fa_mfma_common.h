@@ -319,7 +319,8 @@ inline void set_block_divisors(Params &p, int nq, int head_group) {
 // lds_attr: the size set_dyn_lds_once declares, once per (kernel, device) -- the launch's own unless one instantiation is launched
 // with several sizes (0 = lds). The grid check is reachable by the 32-row split-KV grid only (fa_fwd has bounded the 128-row grid).
 template <typename K, typename PT>
-inline hipError_t launch_blocks(K kern, const PT &p, int rows, int threads, size_t lds, int head_group, hipStream_t s, size_t lds_attr = 0) {
+inline hipError_t launch_blocks(K kern, const PT &p, int rows, int threads, size_t lds, int head_group, hipStream_t s, size_t lds_attr = 0,
+                                int grid_y = 1) {  // grid_y: the key-split partial kernels run the block map once per split (blockIdx.y)
   const int nQ = (p.N + rows - 1) / rows;
   if (lds > 48 * 1024) {
     hipError_t e = set_dyn_lds_once((const void *)kern, (int)(lds_attr ? lds_attr : lds));
@@ -331,7 +332,7 @@ inline hipError_t launch_blocks(K kern, const PT &p, int rows, int threads, size
   pp.head_group = head_group;
   set_block_divisors(pp, nQ, head_group);
   (void)hipGetLastError();  // do not report an older sticky error as this launch's
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, s, pp);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)grid_y), dim3(threads), lds, s, pp);
   return hipGetLastError();
 }
 

@@ -100,6 +100,16 @@ __device__ __forceinline__ int paged_capacity(const Params &) { return 0; }
 __device__ __forceinline__ float softcap_of(const VarlenSoftcapParams &p) { return p.softcap; }
 __device__ __forceinline__ float softcap_of(const VarlenPagedSoftcapParams &p) { return p.softcap; }
 __device__ __forceinline__ float softcap_of(const Params &) { return 0.0f; }
+// key-split mode: the workspace's two parts, [S][rows][D] floats of o_s and [S][rows] floats of lse2_s with rows = H . total_q; these two
+// give split s's row `row` (= hq . total_q + token, the LSE's index)
+template <int D>
+__device__ __forceinline__ float *ksplit_o(const VarlenPagedKsplitParams &p, int s, long long row) {
+  return p.ws + ((long long)s * p.H * p.total_q + row) * D;
+}
+template <int D>
+__device__ __forceinline__ float *ksplit_lse2(const VarlenPagedKsplitParams &p, int s, long long row) {
+  return p.ws + (long long)p.S * p.H * p.total_q * D + (long long)s * p.H * p.total_q + row;
+}
 // C = softcap . log2(e): a capped score t . softcap in log2 units is t . C (wave-uniform: it lives in a scalar register)
 template <typename PT>
 __device__ __forceinline__ float softcap_log2(const PT &p) { return softcap_of(p) * 1.4426950408889634f; }
@@ -139,6 +149,15 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   // bf16 chunks it stands for in the SAME swizzled images. The two LDS buffers and everything from LDS onwards are the bf16 kernel's, so
   // the results are bit for bit those of the paged window / sink kernels on the widened pool.
   constexpr bool KV8 = std::is_same<PT, VarlenPagedKv8Params>::value || std::is_same<PT, VarlenPagedKv8SinkParams>::value;
+  // KSPLIT (PT = VarlenPagedKsplitParams; fa_fwd_varlen_paged_split with S >= 2): the paged window mode over ONE of S sub-ranges of the
+  // block's tiles. The grid is the block map times S with the split index in blockIdx.y, i.e. outside map_block: the heads of a group
+  // keep their places relative to one another inside every split (they share K / V in one XCD's L2), and the splits of a block, which
+  // share nothing, lie a whole block map apart. The tile loop runs tiles [t0, t1) of ksplit_tiles; a wave's first tile INSIDE the split
+  // takes the exact path. The epilogue writes the normalised state of the block's owned rows to the workspace instead of O / LSE:
+  // o_s = acc * (1 / l) in fp32, the existing epilogue's expression before its rounding, and lse2_s = m + log2 l. A row with no visible
+  // key in the split has l = 0 over a finite floor or m = -inf: lse2_s = -inf either way, and its o_s (0 * inf) is never read. An empty
+  // split and a block without a visible key write lse2_s = -inf alone. The sink is the combine kernel's.
+  constexpr bool KSPLIT = std::is_same<PT, VarlenPagedKsplitParams>::value;
   static_assert(!KV8 || std::is_same<Tag, BF16>::value, "KV8 mode: bf16 queries, e4m3 pools widened to bf16");
   static_assert(!WINDOW || CAUSAL, "window mode: the upper bound is the causal one with its own offset");
   static_assert(!VARLEN || (SPLIT == 1 && ROWS == BM && PRESC && !std::is_same<Tag, FP8>::value && (D == 64 || D == 128)),
@@ -244,6 +263,11 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
       if (k_lo >= kv_hi) kv_hi = 0;
     }
     if ((WINDOW ? kv_hi : CAUSAL ? min(LK, qb * ROWS + ROWS + LK - LQ) : LK) <= 0) {
+      if constexpr (KSPLIT) {  // every split says "no key" for the block's owned rows; the combine kernel writes O = 0 and the LSE
+        const int row = qb * ROWS + (int)threadIdx.x;
+        if ((int)threadIdx.x < ROWS && row < LQ) *ksplit_lse2<D>(p, (int)blockIdx.y, lse_base + row) = -INFINITY;
+        return;
+      }
       elem *Oz = (elem *)p.o + base;
       for (int idx = threadIdx.x; idx < ROWS * CPR; idx += NTHREADS) {
         const int row = qb * ROWS + idx / CPR, ch = idx % CPR;
@@ -350,9 +374,19 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   }
 
   const int kv_end = WINDOW ? kv_hi : CAUSAL ? min(FA_NK, q0 + ROWS + coff) : FA_NK;  // (varlen: >= 1 here)
-  const int tb = WINDOW ? t_lo : 0;                             // the block's first tile
-  const int tfw = WINDOW ? max(0, qw0 + cl) / BN : sp;          // this wave's first active tile (the exact path's "first tile")
-  const int nT = (kv_end + BN - 1) / BN;
+  int ks_t0 = 0, ks_t1 = 0;  // key-split mode: this split's tiles of the block's range [t_lo, ceil(kv_end / BN))
+  if constexpr (KSPLIT) {
+    ksplit_tiles(t_lo, (kv_end + BN - 1) / BN, (int)blockIdx.y, p.S, ks_t0, ks_t1);
+    if (ks_t0 >= ks_t1) {  // an empty split (n < S): "no key" for the block's owned rows, in front of every barrier
+      const int row = q0 + (int)threadIdx.x;
+      if ((int)threadIdx.x < ROWS && row < LQ) *ksplit_lse2<D>(p, (int)blockIdx.y, lse_base + row) = -INFINITY;
+      return;
+    }
+  }
+  const int tb = KSPLIT ? ks_t0 : WINDOW ? t_lo : 0;            // the block's first tile (key-split mode: the split's)
+  // this wave's first active tile (the exact path's "first tile"; key-split mode: not before the split's first)
+  const int tfw = KSPLIT ? max(ks_t0, max(0, qw0 + cl) / BN) : WINDOW ? max(0, qw0 + cl) / BN : sp;
+  const int nT = KSPLIT ? ks_t1 : (kv_end + BN - 1) / BN;
 
   // LDS-DMA staging (FA_MFMA_DMA): wave w of a split moves the 1-KiB pieces w, w + RW, ... of each tile; inside a piece the
   // LDS image is lane-linear, so the chunk swizzle sits on the SOURCE address (one per-lane offset for K, one for V)
@@ -879,6 +913,44 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
 
   // ---- epilogue: normalise, LSE, O tile -> LDS -> coalesced 16-byte stores (split2: waves 0-3 only; the others keep
   // the barrier company)
+  if constexpr (KSPLIT) {
+    // key-split mode: the normalised state of this wave's owned rows goes to the workspace, straight from the registers (lane (r, h) holds
+    // d columns 32 db + 8 g4 + 4 h + 0..3 of row r: 16-byte stores, a lane pair fills a 32-byte sector). o_s and lse2_s are the
+    // expressions of the epilogue below -- oacc . (1 / l), and m with the logarithm of l, here base 2 -- so a split that holds all the
+    // visible keys of a row hands the combine exactly what that epilogue rounds.
+    {
+      float lo, hi;
+      half_pair(l, lo, hi);
+      l = lo + hi;
+    }
+    const float inv_l = 1.0f / l;
+    // The f16 epilogue below rounds the EXACT product oacc . (1 / l) to f16 once (hipcc fuses the multiply into v_fma_mixlo_f16); the
+    // bf16 one rounds the fp32 product. o_s carries what that rounding sees: bf16, the fp32 product; f16, the product rounded to ODD in
+    // fp32 (the residual of the product by one fma; inexact: truncate, set the last bit), from which the combine's one rounding to f16
+    // gives the bits of rounding the exact product -- 24 bits are two more than f16 needs for that. One ulp of fp32 instead of a half.
+    auto o_of = [&](float a) __attribute__((always_inline)) {
+      float pr = a * inv_l;
+      if constexpr (std::is_same<Tag, F16>::value) {
+        const float res = __builtin_fmaf(a, inv_l, -pr);
+        unsigned u = __builtin_bit_cast(unsigned, pr);
+        if (res != 0.0f) u = (((res < 0.0f) != (pr < 0.0f)) ? u - 1u : u) | 1u;
+        pr = __builtin_bit_cast(float, u);
+      }
+      return pr;
+    };
+    if (qrow < LQ) {
+      typedef float f32x4 __attribute__((ext_vector_type(4)));
+      float *wo = ksplit_o<D>(p, (int)blockIdx.y, lse_base + qrow) + 4 * h;
+      if (h == 0) *ksplit_lse2<D>(p, (int)blockIdx.y, lse_base + qrow) = m + __builtin_log2f(l);
+#pragma unroll
+      for (int db = 0; db < DB; ++db)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4)
+          *reinterpret_cast<f32x4 *>(wo + 32 * db + 8 * g4) = f32x4{o_of(oacc[db][4 * g4 + 0]), o_of(oacc[db][4 * g4 + 1]),
+                                                                   o_of(oacc[db][4 * g4 + 2]), o_of(oacc[db][4 * g4 + 3])};
+    }
+    return;
+  }
   lds_char *Ot = (lds_char *)smem_generic + wave * (WM * RB);  // this wave's [32][D] tile (inside the K buffers)
   if (sp == 0) {
     {
@@ -1020,6 +1092,105 @@ __global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_kv8_sink
   fwd_mfma_body<BF16, D, true, 1, true, BM, VarlenPagedKv8SinkParams>(p);
 }
 
+// fa_fwd_varlen_paged_split (S >= 2): the paged window kernel in key-split mode, at its occupancy; grid = the block map x S
+template <typename Tag, int D>
+__global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_ksplit_paged_kernel(VarlenPagedKsplitParams p) {
+  fwd_mfma_body<Tag, D, true, 1, true, BM, VarlenPagedKsplitParams>(p);
+}
+
+// ... and its second launch, on the partial's own block map (one workgroup per (sequence, head, 128 rows), the same cu_seqlens_q lookup
+// and clamps: what the partials wrote is what is read, and only owned tokens of O / LSE are written). Thread t takes 8 d columns of rows
+// t / (D / 8), + 256 / (D / 8), ... of the block. Per row, over the splits in order (no atomics: bitwise reproducible):
+//   M = max_s lse2_s;  w_s = 2^(lse2_s - M);  W = sum_s w_s;  O = (sum_s w_s o_s) (1 / W);  LSE = (M + log2 W) ln 2.
+// A split with lse2_s = -inf is SKIPPED, its o_s never loaded (stale workspace, or the 0 . inf of a row without a key in the split). The
+// sums start from -0, the one value x + (-0) = x holds for bit for bit: a row whose keys all lie in one split has w = 1, W = 1 and comes
+// out as o_s rounded to the type once -- the un-split kernel's bits. M = -inf (no split saw a key): O = 0 exactly, LSE = -inf.
+// SINK (sinks != nullptr at launch): decode_combine_sink_kernel's merge behind the reduction: s2 = sink . log2(e), Mm = max(M, s2),
+// W' = W 2^(M - Mm) + 2^(s2 - Mm), O = acc 2^(M - Mm) / W', LSE = (Mm + log2 W') ln 2. Neither exponent is positive; a sink whose term
+// underflows leaves Mm = M, a factor of exactly 1 and W' = W + 0; a dead row gets LSE = sinks[h] bit for bit.
+template <typename Tag, int D, bool SINK>
+__global__ __launch_bounds__(NTHREADS) void ksplit_combine_kernel(VarlenPagedKsplitParams p) {
+  using elem = typename MT<Tag>::elem;
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  constexpr int CPR = D / 8, RPP = NTHREADS / CPR;  // 16-byte output chunks per row, rows per pass
+  int bh, qb;
+  map_block<true>(blockIdx.x, p, bh, qb);
+  const int b = (int)fdiv((unsigned)bh, p.fd_h), hq = bh - b * p.H;
+  const int sq = min(max(p.cu_q[b], 0), p.total_q), eq = min(max(p.cu_q[b + 1], 0), p.total_q);
+  const int LQ = min(max(eq - sq, 0), p.N);
+  const long long lse_base = (long long)hq * p.total_q + sq;
+  const long long rows = (long long)p.H * p.total_q;
+  const float *wl = ksplit_lse2<D>(p, 0, 0);
+  const float *wo = ksplit_o<D>(p, 0, 0);
+  const int S = p.S, ch = (int)threadIdx.x % CPR;
+  float sink = 0.0f;
+  if constexpr (SINK) sink = p.sinks[hq];
+  elem *Og = (elem *)p.o + (long long)sq * p.q_rs + (long long)hq * p.head_stride;
+  for (int row = qb * BM + (int)threadIdx.x / CPR; row < min(LQ, qb * BM + BM); row += RPP) {
+    const float *rl = wl + lse_base + row;
+    // eight splits' loads in flight at a time (one dependent read per split made the decode's combine cost more than its partial kernel)
+    float M = -INFINITY;
+    for (int s0 = 0; s0 < S; s0 += 8) {
+      float l2[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) l2[u] = s0 + u < S ? rl[(long long)(s0 + u) * rows] : -INFINITY;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) M = fmaxf(M, l2[u]);
+    }
+    float W = -0.0f, acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = -0.0f;
+    for (int s0 = 0; s0 < S; s0 += 8) {
+      float l2[8];
+      f32x4 x0[8], x1[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) l2[u] = s0 + u < S ? rl[(long long)(s0 + u) * rows] : -INFINITY;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        x0[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        x1[u] = x0[u];
+        if (l2[u] != -INFINITY) {  // a split without a key for this row is selected away: never loaded, never multiplied
+          const float *ro = wo + ((long long)(s0 + u) * rows + lse_base + row) * D + ch * 8;
+          x0[u] = *reinterpret_cast<const f32x4 *>(ro);
+          x1[u] = *reinterpret_cast<const f32x4 *>(ro + 4);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {  // in split order
+        if (l2[u] == -INFINITY) continue;
+        const float w = __builtin_amdgcn_exp2f(l2[u] - M);
+        W += w;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          acc[i] += w * x0[u][i];
+          acc[4 + i] += w * x1[u][i];
+        }
+      }
+    }
+    const bool dead = M == -INFINITY;
+    float inv, lse;
+    if constexpr (SINK) {
+      const float s2 = sink * 1.4426950408889634f;
+      const float Mm = dead ? s2 : fmaxf(M, s2);
+      const float ow = dead ? 0.0f : __builtin_amdgcn_exp2f(M - Mm);
+      const float Wt = (dead ? 0.0f : W * ow) + __builtin_amdgcn_exp2f(s2 - Mm);
+      inv = ow * (1.0f / Wt);
+      lse = dead ? sink : (Mm + __builtin_log2f(Wt)) * 0.6931471805599453f;
+    } else {
+      inv = dead ? 0.0f : 1.0f / W;
+      lse = dead ? -INFINITY : (M + __builtin_log2f(W)) * 0.6931471805599453f;
+    }
+    u32x4 out;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const elem e0 = dead ? (elem)0.0f : (elem)(acc[2 * i] * inv), e1 = dead ? (elem)0.0f : (elem)(acc[2 * i + 1] * inv);
+      out[i] = (unsigned)__builtin_bit_cast(unsigned short, e0) | ((unsigned)__builtin_bit_cast(unsigned short, e1) << 16);
+    }
+    *reinterpret_cast<u32x4 *>(Og + (long long)row * p.q_rs + ch * 8) = out;
+    if (p.lse != nullptr && ch == 0) p.lse[lse_base + row] = lse;
+  }
+}
+
 // ---------------------------------------------------------------------------
 bool mfma_supported(int dtype, int D) {
   if (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) return D == 32 || D == 64 || D == 96 || D == 128 || D == 256;
@@ -1128,6 +1299,46 @@ hipError_t launch_mfma_varlen_paged_kv8(const VarlenPagedSinkParams &p, bool wit
     VarlenPagedKv8Params pk;
     static_cast<VarlenPagedWindowParams &>(pk) = p;
     return launch_blocks(fwd_mfma_kv8_kernel<D>, pk, BM, NTHREADS, mfma_lds_bytes<BF16, D>(), hg, s);
+  });
+}
+
+// Splits per 128-row block of fa_fwd_varlen_paged_split: the smallest count with blocks * S >= FA_KSPLIT_SLOTS, but so that a split of a
+// block that spans the whole capacity keeps FA_KSPLIT_MIN_TILES 64-key tiles -- a split pays the block's prologue (Q fragments, pre-scale,
+// first tile's latency) and 128 (D + 1) floats of workspace traffic.
+// FA_KSPLIT_SLOTS = 256 CUs x 2 workgroups at BOTH head dims. The head_dim 64 kernels run three per CU, and 768 was the first value; measured
+// on the tool's whole head_dim 64 grid (profiles/r22/bench_varlen_paged_split_d64.log): with 512 blocks (16 x 8 heads x 4, 4 x 32 x 4,
+// 16 x 32 x 1) 768 asks for S = 2, i.e. 1024 half-length workgroups in two rounds where the un-split call needs one: 1.09 to 1.24 of its
+// time; and one sequence of 8 heads x 512 queries got S = 24 where 8 to 16 is best (1.5 at 8k keys, 1.11 at 32k). With 512 no shape of that
+// grid is slower than the un-split call and the worst distance to the best S measured is 1.17.
+// FA_KSPLIT_MIN_TILES = 4, the decode's: it binds at 8k keys and a chunk of 8 only (S = 32 where 16 is best, within 3 %); 8 gives the same
+// choices on that grid, 16 is worse (S = 8 at 8k keys: 1.25 of the best).
+#ifndef FA_KSPLIT_SLOTS
+#define FA_KSPLIT_SLOTS 512
+#endif
+#ifndef FA_KSPLIT_MIN_TILES
+#define FA_KSPLIT_MIN_TILES 4
+#endif
+int varlen_paged_ksplit_splits(int B, int Hq, int max_seqlen_q, int D, int page_size, int max_pages_per_seq) {
+  const long long blocks = (long long)B * Hq * (((long long)max_seqlen_q + BM - 1) / BM), slots = FA_KSPLIT_SLOTS;
+  (void)D;
+  const long long cap_tiles = ((long long)page_size * max_pages_per_seq + BN - 1) / BN;
+  long long S = (slots + blocks - 1) / blocks;
+  S = std::min<long long>(S, std::max<long long>(1, cap_tiles / FA_KSPLIT_MIN_TILES));
+  return (int)std::max<long long>(1, std::min<long long>(S, FA_VARLEN_PAGED_MAX_SPLITS));
+}
+
+// the pair of launches on one stream: partials on the block map x S (blockIdx.y = the split), then the combine on the block map
+hipError_t launch_mfma_varlen_paged_ksplit(const VarlenPagedKsplitParams &p, int dtype, hipStream_t s) {
+  return with_tag(dtype, [&](auto tag) {
+    return with_dim<64, 128>(p.D, [&](auto d) {
+      using Tag = decltype(tag);
+      constexpr int D = decltype(d)::value;
+      const int hg = causal_head_group(p, D, 2);
+      hipError_t e = launch_blocks(fwd_mfma_ksplit_paged_kernel<Tag, D>, p, BM, NTHREADS, mfma_lds_bytes<Tag, D>(), hg, s, 0, p.S);
+      if (e != hipSuccess) return e;
+      if (p.sinks != nullptr) return launch_blocks(ksplit_combine_kernel<Tag, D, true>, p, BM, NTHREADS, 0, hg, s);
+      return launch_blocks(ksplit_combine_kernel<Tag, D, false>, p, BM, NTHREADS, 0, hg, s);
+    });
   });
 }
 

@@ -438,6 +438,19 @@ def varlen_paged_kv8_supported(q_dtype: str, kv_dtype: str, D: int, page_size: i
     return bool(load_library().fa_fwd_varlen_paged_kv8_supported(DTYPES[q_dtype], DTYPES[kv_dtype], D, int(page_size)))
 
 
+def varlen_paged_num_splits(B: int, Hq: int, max_seqlen_q: int, D: int, page_size: int, max_pages_per_seq: int) -> int:
+    """What num_splits=0 resolves to in flash_attention_varlen_paged (fa_fwd_varlen_paged_num_splits; host scalars only; 0: invalid)."""
+    return int(load_library().fa_fwd_varlen_paged_num_splits(B, Hq, int(max_seqlen_q), D, int(page_size), int(max_pages_per_seq)))
+
+
+def varlen_paged_split_workspace_bytes(B: int, Hq: int, total_q: int, max_seqlen_q: int, D: int, page_size: int, max_pages_per_seq: int,
+                                       num_splits: int = 0) -> int:
+    """Bytes of workspace flash_attention_varlen_paged(num_splits=...) needs (fa_fwd_varlen_paged_split_workspace_bytes; 0 for one split
+    and for invalid sizes)."""
+    return int(load_library().fa_fwd_varlen_paged_split_workspace_bytes(B, Hq, total_q, int(max_seqlen_q), D, int(page_size),
+                                                                        int(max_pages_per_seq), int(num_splits)))
+
+
 def _pool(entry: str, k_pages: torch.Tensor, v_pages: torch.Tensor, layout: str):
     """(num_pages, Hkv, P, D, page stride, head stride, row stride) of a pool pair in layout HND / NHD."""
     if k_pages.dim() != 4 or k_pages.shape != v_pages.shape:
@@ -483,6 +496,8 @@ def flash_attention_varlen_paged(
     window: Optional[Tuple[int, int]] = None,
     sinks: Optional[torch.Tensor] = None,
     softcap: Optional[float] = None,
+    num_splits: Optional[int] = None,
+    workspace: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Packed queries against a paged KV cache (include/fa_mi355.h fa_fwd_varlen_paged): chunked prefill, prefix caching, verification of
     many speculated tokens. q [total_q, Hq, D] as in flash_attention_varlen (any view with a unit element stride), cu_seqlens_q int32
@@ -498,9 +513,19 @@ def flash_attention_varlen_paged(
     the prefill"): the pool of flash_attention_decode_paged, read as plain e4m3 values -- no scales: fold a K scale into `scale`, a V scale
     into what consumes `out`; window, is_causal and sinks mean what they mean with sinks, and the result is bit for bit the bf16 call on
     the widened pool. softcap: as in flash_attention_varlen (fa_fwd_varlen_paged_softcap; f16 / bf16 pools only: with sinks or with e4m3
-    pools it raises ValueError); None or 0.0: the calls above, untouched. Returns (out, lse): out like q, lse [Hq, total_q]."""
+    pools it raises ValueError); None or 0.0: the calls above, untouched. num_splits: an int >= 0 takes the key-split call
+    (fa_fwd_varlen_paged_split, "Key split in the paged prefill": the keys of every 128-row block are dealt to that many workgroups and
+    combined in a second launch -- for a chunk or a few speculated tokens on one or a few long sequences, where the blocks alone cannot fill
+    the chip); 0 asks varlen_paged_num_splits; window, is_causal and sinks mean what they mean with sinks; with softcap or with e4m3 pools it
+    raises ValueError. `workspace`: a uint8 device tensor of at least varlen_paged_split_workspace_bytes(...) bytes (allocated here if
+    None). None: the calls above, untouched. Returns (out, lse): out like q, lse [Hq, total_q]."""
     lib = load_library()
     cap = _softcap(softcap, sinks)  # (first: a cap that cannot be served is refused whatever else is wrong)
+    if num_splits is not None:
+        if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+            raise ValueError(f"num_splits must be None or an int >= 0 (0: the heuristic), got {num_splits!r}")
+        if cap is not None:
+            raise ValueError("num_splits together with softcap is not supported (fa_fwd_varlen_paged_split has no cap)")
     entry = "flash_attention_varlen_paged"
     if q.dim() != 3:
         raise ValueError(f"q [total_q,Hq,D], got {tuple(q.shape)}")
@@ -511,6 +536,8 @@ def flash_attention_varlen_paged(
     kv8 = _FP8 is not None and q.dtype == torch.bfloat16 and k_pages.dtype == _FP8
     if cap is not None and kv8:
         raise ValueError("softcap on float8_e4m3fn pools is not supported in the prefill (fa_fwd_varlen_paged_kv8 has no cap)")
+    if num_splits is not None and kv8:
+        raise ValueError("num_splits on float8_e4m3fn pools is not supported (fa_fwd_varlen_paged_split takes f16 / bf16 pools)")
     if not kv8 and (q.dtype not in (torch.float16, torch.bfloat16) or k_pages.dtype != q.dtype):
         raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k_pages.dtype} {v_pages.dtype} (f16 or bf16, q and the pools alike; or bf16 q "
                          "on float8_e4m3fn pools)")
@@ -538,6 +565,11 @@ def flash_attention_varlen_paged(
     if kv8:  # one entry point with or without sinks; the mask as the sink path maps it
         entry, mask = "fa_fwd_varlen_paged_kv8", _sink_window(window, is_causal) + (_ptr(sinks),)
         dtypes = (_TORCH2FA[q.dtype], _TORCH2FA[k_pages.dtype])
+    if num_splits is not None:  # the mask as the sink path maps it; sinks may be absent
+        need = varlen_paged_split_workspace_bytes(B, Hq, total_q, int(max_seqlen_q), D, P, block_table.shape[1], num_splits)
+        ws = _workspace(workspace, need, q.device)
+        entry, mask = "fa_fwd_varlen_paged_split", _sink_window(window, is_causal) + (_ptr(sinks),)
+        dtypes = (_TORCH2FA[q.dtype], num_splits, ws.data_ptr(), ws.numel())
     _call(lib, entry,
           (q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), block_table.data_ptr(),
            seqlens_k.data_ptr(), B, Hq, Hkv, total_q, int(max_seqlen_q), D, P, num_pages, block_table.shape[1], _scale(scale, D),

@@ -637,6 +637,60 @@ int fa_kv_append_paged_quant(const void *k_new, const void *v_new, void *k_pages
                              long long block_table_stride, int new_dtype, float k_mul, float v_mul, void *hip_stream);
 
 /*
+ * Key split in the paged prefill: fa_fwd_varlen_paged_split is fa_fwd_varlen_paged_sink with `int num_splits, void *workspace, long long
+ * workspace_bytes` added behind `int dtype`, for calls whose B * Hq * ceil(max_seqlen_q / 128) blocks of 128 rows cannot fill the chip: a
+ * chunk of a few hundred queries, or the verification of a few speculated tokens, on one or a few long sequences. The keys of every
+ * 128-row block are dealt to S workgroups, which leave per-row partial states in the caller's workspace, and a second launch on the same
+ * stream combines them. Semantics are fa_fwd_varlen_paged_sink's: layouts, strides, tables and their clamping, owned tokens, the window
+ * rule, dead rows, f16 / bf16 with q and the pools of one type, D = 64 | 128, P in {16 .. 256}; fa_fwd_varlen_paged_supported applies as
+ * it stands. `sinks` may be NULL, as in fa_fwd_varlen_paged_kv8: then there is no sink term and a dead row gets LSE = -inf. Validation is
+ * the one paged-prefill path: every rule the call shares with fa_fwd_varlen_paged_sink carries the same status and the same error text.
+ * num_splits: 0 .. FA_VARLEN_PAGED_MAX_SPLITS, else FA_ERR_INVALID_ARG; 0 stands for what fa_fwd_varlen_paged_num_splits answers for the
+ * call's scalars. With S >= 2 splits `workspace` must be non-NULL, 16-byte aligned device memory of at least
+ * fa_fwd_varlen_paged_split_workspace_bytes(..., S) bytes, else FA_ERR_INVALID_ARG; what it holds before and after the call is irrelevant.
+ * S = 1: the call launches the kernel of the window family it would have launched without the split (the paged window kernel, or the
+ * paged sink kernel when sinks != NULL; never-binding bounds clamped on the host as in the sink calls) and nothing else; the workspace may
+ * be NULL; the result is that call's, bit for bit.
+ * THE SPLIT RULE (per block, as fa_fwd_decode's is per call): a block's tile range is what the window kernel walks, tiles [tb, nT) of 64
+ * keys from fa_window_key_range of the block's rows, n = nT - tb. Split s of S takes tiles
+ *     tb + floor(s * n / S) .. tb + floor((s + 1) * n / S) - 1
+ * so every causal block balances its own length, the capacity plays no part, and a split is empty when n < S.
+ * What a split leaves per owned row, normalised: o_s = acc / l in fp32 (formed as the un-split epilogue forms it before rounding to the
+ * type: acc * (1 / l), the fp32 product for bf16; for f16, whose epilogue rounds the exact product to f16 once, that product rounded to
+ * odd in fp32, so that one rounding to f16 in the combine lands on the same bits) and lse2_s = m + log2 l in log2 units; -inf for an empty split and for a row without a visible key in the split. The combine
+ * runs on the partial kernel's own (sequence, head, 128-row block) map with the same cu_seqlens_q lookup and clamps, per row
+ *     M = max_s lse2_s;  w_s = 2^(lse2_s - M);  W = sum_s w_s;  O = (sum_s w_s o_s) / W;  LSE = (M + log2 W) ln 2
+ * over s in order: no atomics, bitwise reproducible. A split with lse2_s = -inf is skipped, never multiplied. M = -inf: O = 0 exactly and
+ * LSE = -inf. A sink is folded once, behind the reduction, with fa_fwd_decode_paged_sink's overflow-safe merge: a dead row gets LSE =
+ * sinks[h] bit for bit, a sink whose term underflows leaves the bits of the call with sinks == NULL.
+ * Without sinks, O of every row of a block with n = 1 is BIT-IDENTICAL to the S = 1 call under any S >= 2: the one non-empty split weighs
+ * exactly 1, W = 1, and O is rounded to the type once. (Its LSE is (m + log2 l) ln 2 where the un-split kernel forms m ln 2 + ln l: equal
+ * within the roundings below, not bit for bit.)
+ * Accuracy: the un-split call's bounds ("LSE accuracy"; with sinks lse_tol' / the O bound of "Attention sinks") plus the merge term of
+ * merged key splits, 2 (S + 3) 2^-24 sum_j P_ij |v_jd| on O -- and, because a split's state is ONE fp32 number
+ * lse2_s whose resolution is that of its magnitude, 6 2^-24 |LSE| sum_j P_ij |v_jd| more (nothing at |LSE| of a few units) --, and on LSE 2^-22 (2 |LSE| + S + 6) (the splits' own log2 and sum, the differences,
+ * the exponentials and W's S additions, log2 W, the sum and the product by ln 2). tests/ksplit.py spells both out.
+ * Graph capture: the host reads no device memory and both grids depend on host scalars only (the block map x S, then the block map).
+ * fa_fwd_varlen_paged_num_splits (host only): with blocks = B * Hq * ceil(max_seqlen_q / 128) and slots = 512 (256 CUs x 2, at both head dims: measured) the
+ * smallest S with blocks * S >= slots, capped so that a split of a block spanning the capacity max_pages_per_seq * page_size keeps at
+ * least 4 tiles, capped by FA_VARLEN_PAGED_MAX_SPLITS, at least 1; 0 for invalid arguments. The workspace holds S * Hq * total_q * (D + 1)
+ * floats, rounded up to 16 bytes; the size function resolves num_splits = 0 like the call and answers 0 for invalid sizes and for S = 1.
+ * Not offered with softcap, on e4m3 pools, or on the packed and dense calls.
+ */
+#define FA_VARLEN_PAGED_MAX_SPLITS 64
+int fa_fwd_varlen_paged_split(const void *q, const void *k_pages, const void *v_pages, void *o, float *lse,
+                              const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                              int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                              int page_size, int num_pages, int max_pages_per_seq, float scale,
+                              long long q_row_stride, long long q_head_stride,
+                              long long kv_page_stride, long long kv_head_stride, long long kv_row_stride,
+                              long long block_table_stride, int window_left, int window_right, const float *sinks, int dtype,
+                              int num_splits, void *workspace, long long workspace_bytes, void *hip_stream);
+int fa_fwd_varlen_paged_num_splits(int B, int Hq, int max_seqlen_q, int D, int page_size, int max_pages_per_seq);
+long long fa_fwd_varlen_paged_split_workspace_bytes(int B, int Hq, int total_q, int max_seqlen_q, int D,
+                                                    int page_size, int max_pages_per_seq, int num_splits);
+
+/*
  * Logit soft-capping: fa_fwd_varlen_softcap, fa_fwd_varlen_paged_softcap, fa_fwd_decode_paged_softcap and fa_bwd_varlen_softcap are the
  * four *_window entry points with `float softcap` added directly behind window_right (where the sink calls take `sinks`), for models that
  * cap their attention logits (Gemma-2: head_dim 128, grouped heads, a window of 4096 alternating with full causal layers, a cap of 50).
