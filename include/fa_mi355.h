@@ -186,7 +186,8 @@ int fa_fwd_exv(const void *q, const void *k, const void *v, void *o, float *lse,
  * [total, H, D] (strides H*D, D) and [H, total, D] (strides D, total*D) work, and so do three views of one packed [total, Hq + 2*Hkv, D]
  * QKV projection (row stride (Hq + 2*Hkv)*D, head stride D). Strides are multiples of 8 elements and at least D, bases 16-byte aligned,
  * the element stride is 1; lse is [Hq, total_q] fp32 contiguous, or NULL. The tensors may exceed 4 GiB: a sequence's base is a 64-bit
- * address, and only (max_seqlen + 128) * row_stride * 2 bytes must stay below 4 GiB, for q and for k / v.
+ * address, and only (max_seqlen + 128) * row_stride * 2 bytes must stay below 4 GiB, for q and for k / v (loads and stores above 4 GiB
+ * and in-sequence offsets of 2 - 4 GiB are run by tests/test_gpu_far_addresses.py, cases A and C).
  * cu_seqlens_q / cu_seqlens_k (int32, [B + 1]) are DEVICE memory read by the kernels -- the host never reads them and the launch
  * geometry depends on the host scalars alone (B * Hq * ceil(max_seqlen_q / 128) workgroups), so one captured graph serves any set of
  * lengths under the same B, total_* and max_seqlen_*. Sequence b owns query tokens cu_seqlens_q[b] .. cu_seqlens_q[b+1) and keys
@@ -278,7 +279,8 @@ int fa_fwd_decode_paged_supported(int q_dtype, int kv_dtype, int D, int Hq, int 
  * behave exactly as in fa_fwd_decode_paged: HND or NHD pools under one set of strides, L_b = seqlens_k[b] clamped to
  * [0, max_pages_per_seq * P], key j < L_b is slot j % P of page block_table[b][j / P]; a page index outside [0, num_pages) reads as
  * zeros and touches nothing; slots >= L_b of a last page and table entries past ceil(L_b / P) have no influence (NaN there is harmless).
- * The pool may exceed 4 GiB, one page of one head stays below 2 GiB, the capacity is at most 2^30 keys.
+ * The pool may exceed 4 GiB, one page of one head stays below 2 GiB, the capacity is at most 2^30 keys (pools whose used pages lie past
+ * ELEMENT offset 2^32, bf16 and e4m3, are run by tests/test_gpu_far_addresses.py, cases D - F).
  * Per sequence the operator is fa_fwd_ex: query head h reads key head h / (Hq / Hkv); causal is bottom-right aligned per sequence (key
  * j visible to query i iff j <= i + L_b - Lq_b), where L_b is the cache length WITH the chunk already appended (fa_kv_append_paged
  * below) -- that makes a causal call a chunked-prefill step. L_b < Lq_b and L_b = 0 are legal: a row with no visible key gets O = 0
@@ -449,7 +451,7 @@ double fa_bwd_algorithmic_flops(int B, int H, int N, int D, int is_causal);
  * fp32 gradient of three views of one packed [total, Hq + 2*Hkv, D] QKV projection is three views of one fp32 buffer of that shape.
  * lse is the forward's [Hq, total_q] fp32. Strides are multiples of 8 elements and at least D, bases 16-byte aligned. The tensors may
  * exceed 4 GiB (gradients are stored through 64-bit addresses); only (max_seqlen + 128) * row_stride * 2 bytes must stay below 4 GiB,
- * for q and for k / v. `workspace`: caller-owned device memory of fa_bwd_varlen_workspace_bytes(Hq, total_q) bytes (delta, [Hq, total_q]
+ * for q and for k / v (fp32 stores past byte 2^33 are run by tests/test_gpu_far_addresses.py, cases B and C). `workspace`: caller-owned device memory of fa_bwd_varlen_workspace_bytes(Hq, total_q) bytes (delta, [Hq, total_q]
  * fp32; 0 for invalid sizes), contents irrelevant before the call. The size cannot be seen from the pointer: the caller answers for it.
  * cu_seqlens_q / cu_seqlens_k (int32, [B + 1]) are DEVICE memory read by the kernels -- the host never reads them; the grids are
  * B * Hq * ceil(max_seqlen_q / 128) workgroups for dQ and B * Hkv * ceil(max_seqlen_k / 128) for dK / dV, so one captured graph serves
