@@ -22,11 +22,14 @@ from .ops import (  # noqa: F401
     flash_attention_decode,
     flash_attention_decode_paged,
     flash_attention_forward,
+    flash_attention_mla_decode_paged,
     flash_attention_varlen,
     flash_attention_varlen_backward,
     flash_attention_varlen_paged,
     forward_kernel_name,
     kv_append_paged,
+    mla_decode_paged_supported,
+    mla_decode_paged_workspace_bytes,
     supported,
     varlen_backward_supported,
     varlen_backward_workspace_bytes,

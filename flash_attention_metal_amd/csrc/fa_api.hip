@@ -659,6 +659,63 @@ int fa_fwd_decode_paged_softcap(const void *q, const void *k_pages, const void *
                            &softcap);
 }
 
+// ---- fa_fwd_mla_decode_paged: the paged decode's rules on one latent pool. q and o carry three strides each (a rule of this call's
+// own); everything else is the shared helpers, in fa_fwd_decode_paged's order, with its statuses and texts.
+int fa_fwd_mla_decode_paged_supported(int dtype, int Dqk, int Dv, int Hq, int Nq, int page_size) {
+  return fa::mla_decode_supported(dtype, Dqk, Dv) && Hq >= 1 && Nq >= 1 && (long long)Hq * Nq <= 32 && fa::page_size_ok(page_size);
+}
+long long fa_fwd_mla_decode_paged_workspace_bytes(int B, int Hq, int Nq, int Dv, int page_size, int max_pages_per_seq) {
+  if (B < 1 || Hq < 1 || Nq < 1 || (long long)Hq * Nq > 32 || Dv != 512 || !fa::page_size_ok(page_size) || max_pages_per_seq < 1 ||
+      (long long)page_size * max_pages_per_seq > (1 << 30))
+    return 0;
+  return fa::mla_decode_workspace_bytes(B, Hq, Nq, page_size * max_pages_per_seq);  // the split rule at the capacity: host scalars only
+}
+// one [B, Hq, Nq, D] operand under (batch, head, row) element strides, rows and heads interleaved either way
+static int mla_strides_ok(const char *fn, const char *what, int B, int D, long long bs, long long hs, long long rs) {
+  if (rs < D || hs < D || bs < 0 || (B > 1 && bs < D) || (bs % 8) || (hs % 8) || (rs % 8))
+    return fail(FA_ERR_INVALID_ARG, "%s: bad %sstrides (batch %lld, head %lld, row %lld): a row holds %d elements, strides are multiples of 8", fn,
+                what, bs, hs, rs, D);
+  return FA_OK;
+}
+int fa_fwd_mla_decode_paged(const void *q, const void *kv_pages, void *o, float *lse, const int *block_table, const int *seqlens_k, int B,
+                            int Hq, int Nq, int Dqk, int Dv, int page_size, int num_pages, int max_pages_per_seq, float scale,
+                            long long q_batch_stride, long long q_head_stride, long long q_row_stride, long long o_batch_stride,
+                            long long o_head_stride, long long o_row_stride, long long kv_page_stride, long long kv_row_stride,
+                            long long block_table_stride, int is_causal, int dtype, void *workspace, long long workspace_bytes,
+                            void *hip_stream) {
+  g_err[0] = 0;
+  const char *fn = "fa_fwd_mla_decode_paged";
+  TRY(nonnull(fn, {q, kv_pages, o, block_table, seqlens_k, workspace}));
+  TRY(positive(fn, {B, Hq, Nq, Dqk, Dv, page_size, num_pages, max_pages_per_seq}));
+  TRY(scale_ok(fn, scale));
+  if (!fa_fwd_mla_decode_paged_supported(dtype, Dqk, Dv, Hq, Nq, page_size))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 (q and the pool alike), (Dqk, Dv) = (576, 512), Hq * Nq <= 32 packed query rows and a "
+                "page size of 16, 32, 64, 128 or 256; got dtype=%s Dqk=%d Dv=%d Hq=%d Nq=%d page_size=%d", fn, fa_dtype_name(dtype), Dqk, Dv,
+                Hq, Nq, page_size);
+  TRY(table_stride_ok(fn, block_table_stride, max_pages_per_seq));
+  TRY(mla_strides_ok(fn, "", B, Dqk, q_batch_stride, q_head_stride, q_row_stride));
+  TRY(mla_strides_ok(fn, "output ", B, Dv, o_batch_stride, o_head_stride, o_row_stride));
+  TRY(page_strides_ok(fn, Dqk, page_size, kv_page_stride, kv_row_stride, kv_row_stride, block_table_stride, dtype));  // (one latent head: no head stride)
+  TRY(aligned16(fn, "tensors and workspace", {q, kv_pages, o, workspace}));
+  TRY(page_tables_ok(fn, page_size, max_pages_per_seq, block_table, seqlens_k));
+  const int cap = page_size * max_pages_per_seq;
+  TRY(workspace_fits(fn, workspace_bytes, fa::mla_decode_workspace_bytes(B, Hq, Nq, cap), "fa_fwd_mla_decode_paged_workspace_bytes"));
+  const int rblk = (Hq * Nq + 15) / 16;
+  if ((long long)B * Hq * Nq > 0x7fffffffLL || (long long)B * 256 * rblk > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  fa::MlaDecodeParams p;
+  p.q = q; p.kv = kv_pages; p.o = o; p.lse = lse; p.ws = (float *)workspace;
+  p.block_table = block_table; p.seqlens = seqlens_k;
+  p.B = B; p.Hq = Hq; p.Nq = Nq; p.RBLK = rblk; p.scale = scale;
+  p.S = fa::mla_decode_splits(B, rblk, cap);
+  p.q_bs = q_batch_stride; p.q_hs = q_head_stride; p.q_rs = q_row_stride;
+  p.o_bs = o_batch_stride; p.o_hs = o_head_stride; p.o_rs = o_row_stride;
+  p.page_stride = kv_page_stride; p.row_stride = kv_row_stride;
+  p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
+  p.lp = log2_of(page_size);
+  p.is_causal = is_causal ? 1 : 0;
+  return launched(fn, fa::launch_mla_decode_paged(p, dtype, (hipStream_t)hip_stream));
+}
+
 int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size) { return fa::mfma_varlen_paged_supported(dtype, D, page_size); }
 // the key split's scalars: sizes >= 1, a head_dim and a page size the paged prefill has, a capacity of at most 2^30 keys
 static bool ksplit_scalars_ok(int B, int Hq, int max_seqlen_q, int D, int page_size, int max_pages_per_seq) {

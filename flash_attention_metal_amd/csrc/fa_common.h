@@ -196,6 +196,24 @@ struct DecodeSoftcapParams : DecodePagedParams {
   float softcap;
 };
 
+// one fa_fwd_mla_decode_paged call (csrc/fa_mla_kernel.hip): kv is the one latent pool ([num_pages, P, 576]: no head stride), q and o
+// carry (batch, head, row) element strides of their own. Rows r = h * Nq + iq are packed into RBLK blocks of 16.
+struct MlaDecodeParams {
+  const void *q, *kv;
+  void *o;
+  float *lse;  // nullable
+  float *ws;   // workspace: per (b, split, row block) [16][512] partial O (unnormalised), then [16][2] (m, l)
+  const int *block_table, *seqlens;
+  int B, Hq, Nq;
+  int S;     // key splits per sequence
+  int RBLK;  // 16-row blocks: ceil(Hq * Nq / 16), 1 or 2
+  float scale;
+  long long q_bs, q_hs, q_rs, o_bs, o_hs, o_rs, page_stride, row_stride;  // elements
+  int bt_stride, num_pages, max_pages;
+  int lp;  // log2 of the page size (16 .. 256)
+  int is_causal;
+};
+
 // dtype tags
 struct F32 {};
 struct F16 {};
@@ -262,6 +280,11 @@ hipError_t launch_decode_paged_window(const DecodeWindowParams &p, int D, int dt
 hipError_t launch_decode_paged_sink(const DecodeWindowParams &p, const float *sinks, int D, int dtype, int kv8, hipStream_t s);
 // fa_fwd_decode_paged_softcap: the windowed partial kernels in their softcap mode, then the unchanged paged combine
 hipError_t launch_decode_paged_softcap(const DecodeSoftcapParams &p, int D, int dtype, int kv8, hipStream_t s);
+// fa_fwd_mla_decode_paged (csrc/fa_mla_kernel.hip): (Dqk, Dv) = (576, 512), f16 / bf16; the split rule at the capacity Nk
+hipError_t launch_mla_decode_paged(const MlaDecodeParams &p, int dtype, hipStream_t s);
+bool mla_decode_supported(int dtype, int Dqk, int Dv);
+int mla_decode_splits(int B, int rblk, int Nk);
+long long mla_decode_workspace_bytes(int B, int Hq, int Nq, int Nk);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);

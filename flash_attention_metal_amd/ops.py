@@ -348,6 +348,68 @@ def flash_attention_decode_paged(
     return out, lse
 
 
+def mla_decode_paged_supported(dtype: str, d_qk: int, d_v: int, Hq: int, Nq: int, page_size: int) -> bool:
+    return bool(load_library().fa_fwd_mla_decode_paged_supported(DTYPES[dtype], d_qk, d_v, Hq, Nq, page_size))
+
+
+def mla_decode_paged_workspace_bytes(B: int, Hq: int, Nq: int, d_v: int, page_size: int, max_pages_per_seq: int) -> int:
+    return int(load_library().fa_fwd_mla_decode_paged_workspace_bytes(B, Hq, Nq, d_v, page_size, max_pages_per_seq))
+
+
+def flash_attention_mla_decode_paged(
+    q: torch.Tensor,
+    kv_pages: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens_k: torch.Tensor,
+    scale: float,
+    d_v: int = 512,
+    is_causal: bool = False,
+    return_lse: bool = True,
+    out: Optional[torch.Tensor] = None,
+    lse: Optional[torch.Tensor] = None,
+    workspace: Optional[torch.Tensor] = None,
+    stream: Optional[int] = None,
+) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The absorbed MLA decode step over a paged latent cache (include/fa_mi355.h fa_fwd_mla_decode_paged): q [B,Hq,Nq,576] under any
+    strides with a unit last stride (head-major or a token-major view), Hq * Nq <= 32; kv_pages ONE pool [num_pages, P, 576] or
+    [num_pages, P, 1, 576], f16 / bf16 like q, P in {16, 32, 64, 128, 256}: all 576 columns of a row enter the score, the first d_v = 512
+    are the value. block_table int32 [B, max_pages_per_seq] and seqlens_k int32 [B] are contiguous device tensors read by the kernels only:
+    nothing here synchronises, the call can be captured in a graph. `scale` is required (the model's, e.g. (128 + 64) ** -0.5 * mscale ** 2:
+    the head dim of the model is not 576). Returns O [B,Hq,Nq,d_v] (allocated head-major if `out` is None; any strides with a unit last
+    stride otherwise) and LSE [B,Hq,Nq] fp32 or None. A row with no visible key gets O = 0 and LSE = -inf. `workspace`: a uint8 device
+    tensor of at least mla_decode_paged_workspace_bytes(...) bytes (allocated here if None)."""
+    lib = load_library()
+    if scale is None:
+        raise ValueError("flash_attention_mla_decode_paged needs the model's scale: there is no default (the head dim of the model is not 576)")
+    if q.dim() != 4 or kv_pages.dim() not in (3, 4) or (kv_pages.dim() == 4 and kv_pages.shape[2] != 1):
+        raise ValueError("q [B,Hq,Nq,576], kv_pages one [num_pages,P,576] or [num_pages,P,1,576] latent pool")
+    if not all(t.is_cuda and t.device == q.device for t in (q, kv_pages, block_table, seqlens_k)):
+        raise ValueError("flash_attention_mla_decode_paged needs q, the pool and both tables on one device: there is no CPU path")
+    B, Hq, Nq, Dqk = q.shape
+    num_pages, P, Dk = kv_pages.shape[0], kv_pages.shape[1], kv_pages.shape[-1]
+    ps, rs, es = kv_pages.stride(0), kv_pages.stride(1), kv_pages.stride(-1)
+    if Dk != Dqk or es != 1 or q.stride(3) != 1:
+        raise ValueError(f"incompatible q {tuple(q.shape)} and pool {tuple(kv_pages.shape)} (same last dim, unit element strides)")
+    if (block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or not block_table.is_contiguous()
+            or seqlens_k.dtype != torch.int32 or seqlens_k.shape != (B,) or not seqlens_k.is_contiguous()):
+        raise ValueError("block_table must be a contiguous int32 [B, max_pages_per_seq] tensor and seqlens_k a contiguous int32 [B] one")
+    if q.dtype not in (torch.float16, torch.bfloat16) or kv_pages.dtype != q.dtype:
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {kv_pages.dtype} (f16 or bf16, q and the pool alike)")
+    d_v = int(d_v)
+    if out is None:
+        out = torch.empty((B, Hq, Nq, d_v), dtype=q.dtype, device=q.device)
+    elif not out.is_cuda or out.device != q.device or out.dtype != q.dtype or out.shape != (B, Hq, Nq, d_v) or out.stride(3) != 1:
+        raise ValueError("out must be a [B,Hq,Nq,d_v] device tensor of q's dtype with a unit last stride")
+    lse = _lse(lse, return_lse, q)
+    max_pages = block_table.shape[1]
+    ws = _workspace(workspace, mla_decode_paged_workspace_bytes(B, Hq, Nq, d_v, P, max(max_pages, 1)), q.device)
+    _call(lib, "fa_fwd_mla_decode_paged",
+          (q.data_ptr(), kv_pages.data_ptr(), out.data_ptr(), _ptr(lse), block_table.data_ptr(), seqlens_k.data_ptr(), B, Hq, Nq, Dqk, d_v, P,
+           num_pages, max_pages, float(scale), q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2), ps, rs,
+           block_table.stride(0), int(bool(is_causal)), _TORCH2FA[q.dtype], ws.data_ptr(), ws.numel()), q.device, stream)
+    return out, lse
+
+
 def varlen_supported(dtype: str, D: int) -> bool:
     return bool(load_library().fa_fwd_varlen_supported(DTYPES[dtype], D))
 

@@ -762,6 +762,57 @@ int fa_bwd_varlen_softcap(const void *q, const void *k, const void *v, const voi
                           long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,
                           int window_left, int window_right, float softcap, int dtype, void *hip_stream);
 
+/*
+ * Multi-head latent attention (decode): fa_fwd_mla_decode_paged is the "absorbed" decode step of MLA (DeepSeek-V2 / V3 / R1, Kimi-K2)
+ * over a paged LATENT cache. Every query head reads ONE shared latent row per key, Dqk = 576 elements: 512 of compressed KV followed by 64
+ * of rotary key. All 576 take part in the score, the first Dv = 512 are the value. Per sequence b, with L_b = seqlens_k[b] clamped to
+ * [0, max_pages_per_seq * P]:
+ *     s_ij = q[b,h,i,0:Dqk] . kv_j[0:Dqk]      P = softmax_j(scale * s_ij) over visible keys      O[b,h,i,0:Dv] = sum_j P_ij * kv_j[0:Dv]
+ * LSE is in natural log, [B, Hq, Nq] fp32, or NULL. `scale` is the caller's: there is no default, the model's head dim is not 576.
+ * The pool: key j of sequence b is slot j % P of page block_table[b][j / P] of ONE pool (K and V are the same bytes); element d of slot r
+ * of page p sits at p * kv_page_stride + r * kv_row_stride + d. The natural layout is [num_pages, P, 576]: one latent head, no head
+ * stride (the layout of vLLM's and FlashMLA's latent cache). The pool may exceed 4 GiB; one page stays below 2 GiB, the capacity
+ * max_pages_per_seq * P is at most 2^30 keys.
+ * q and o: element (b, h, i, d) sits at b * q_batch_stride + h * q_head_stride + i * q_row_stride + d, and of o likewise under the o_*
+ * strides, so [B, Hq, Nq, D] and token-major [B, Nq, Hq, D] both work. Strides are multiples of 8 elements, each at least Dqk (Dv for
+ * o; the batch stride may be anything >= 0 when B = 1); bases are 16-byte aligned. O rows of 512 elements are written, never 576.
+ * Causal is bottom-right aligned per sequence, as in fa_fwd_decode_paged: key j is visible to query i iff j <= i + L_b - Nq.
+ * Supported: f16 / bf16 (q and the pool of one type), (Dqk, Dv) = (576, 512), Hq * Nq <= 32 packed rows r = h * Nq + i (16 heads under
+ * tensor parallelism of 8 with one or two tokens per step), P in {16, 32, 64, 128, 256}; anything else FA_ERR_UNSUPPORTED with a message
+ * that names what was given.
+ * As fa_fwd_decode_paged, in its words:
+ *  - block_table (int32, [B, block_table_stride], block_table_stride >= max_pages_per_seq) and seqlens_k (int32, [B]) are DEVICE memory
+ *    read by the kernels -- the host never reads them, and both grids depend on host scalars only, so one captured graph serves every step;
+ *  - a row with no visible key (L_b = 0, or causal with i + L_b < Nq) gets O = 0 exactly and LSE = -inf;
+ *  - results depend neither on slots >= L_b of a sequence's last page (NaN there is harmless: they read as zeros), nor on table entries
+ *    past ceil(L_b / P), nor on the workspace's prior contents, and are bitwise reproducible; a page index outside [0, num_pages) reads
+ *    as zeros and touches nothing outside the pool;
+ *  - `workspace` is caller-owned device memory of fa_fwd_mla_decode_paged_workspace_bytes() bytes, 16-byte aligned, contents irrelevant
+ *    before and after the call; the call is asynchronous and allocates nothing;
+ *  - bad pointers, sizes or strides, a short workspace or block_table_stride < max_pages_per_seq: FA_ERR_INVALID_ARG before any launch.
+ *    Every rule the two calls share carries the same status and the same text after the function name.
+ * How it runs (csrc/fa_mla_kernel.hip): the keys of a sequence are split over S one-wave items per 16-row block,
+ * S by fa_fwd_decode_paged's rule evaluated at the capacity; an item streams 64-key tiles (72 KiB: a [64][512] latent part and a [64][64]
+ * rotary part in one LDS image that serves both products) and writes its partial (O * l, m, l) to the workspace, B * S * rows16 *
+ * (Dv + 2) floats with rows16 = 16 * ceil(Hq * Nq / 16); a second launch combines them by their maxima. Rows 17..32 are a second
+ * 16-row item over the same keys. Pre-scaled query operand as FA_VARIANT_MFMA ("LSE accuracy" above): the tolerances are
+ * fa_fwd_decode's, formed on the 576-wide rows.
+ * The append needs no entry point of its own: fa_kv_append_paged with Hkv = 1, D = 576, k_new == v_new and k_pages == v_pages (a row is
+ * 72 whole 16-byte chunks; both copies write the same bytes).
+ * Not here: e4m3 latent pools, more than 32 packed rows, window / sink / softcap, the MLA prefill (192 / 128 head dims), a backward.
+ */
+int fa_fwd_mla_decode_paged(const void *q, const void *kv_pages, void *o, float *lse,
+                            const int *block_table, const int *seqlens_k,
+                            int B, int Hq, int Nq, int Dqk, int Dv,
+                            int page_size, int num_pages, int max_pages_per_seq, float scale,
+                            long long q_batch_stride, long long q_head_stride, long long q_row_stride,
+                            long long o_batch_stride, long long o_head_stride, long long o_row_stride,
+                            long long kv_page_stride, long long kv_row_stride, long long block_table_stride,
+                            int is_causal, int dtype, void *workspace, long long workspace_bytes, void *hip_stream);
+/* depends on host scalars only (the split rule at the capacity); 0 if a size is invalid or unsupported */
+long long fa_fwd_mla_decode_paged_workspace_bytes(int B, int Hq, int Nq, int Dv, int page_size, int max_pages_per_seq);
+int fa_fwd_mla_decode_paged_supported(int dtype, int Dqk, int Dv, int Hq, int Nq, int page_size);
+
 /* 1 if fa_fwd has a kernel for the combination, else 0 (no GPU needed). */
 int fa_supported(int dtype, int variant, int D);
 
