@@ -25,6 +25,7 @@ from .ops import (  # noqa: F401
     flash_attention_mla_decode_paged,
     flash_attention_varlen,
     flash_attention_varlen_backward,
+    flash_attention_varlen_mla,
     flash_attention_varlen_paged,
     forward_kernel_name,
     kv_append_paged,
@@ -33,6 +34,7 @@ from .ops import (  # noqa: F401
     supported,
     varlen_backward_supported,
     varlen_backward_workspace_bytes,
+    varlen_mla_supported,
     varlen_paged_kv8_supported,
     varlen_paged_num_splits,
     varlen_paged_split_workspace_bytes,

@@ -473,6 +473,46 @@ int fa_fwd_varlen(const void *q, const void *k, const void *v, void *o, float *l
   return varlen_impl("fa_fwd_varlen", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D,
                      scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride, -1, is_causal ? 0 : -1, dtype, hip_stream);
 }
+// fa_fwd_varlen_mla: fa_fwd_varlen's rules in its order, with the stride, alignment and 4 GiB rules once per tensor (q, k, v, o)
+int fa_fwd_varlen_mla_supported(int dtype, int Dqk, int Dv) { return fa::mfma_varlen_mla_supported(dtype, Dqk, Dv); }
+int fa_fwd_varlen_mla(const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q, const int *cu_seqlens_k,
+                      int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int Dqk, int Dv, float scale,
+                      long long q_row_stride, long long q_head_stride, long long k_row_stride, long long k_head_stride,
+                      long long v_row_stride, long long v_head_stride, long long o_row_stride, long long o_head_stride, int is_causal,
+                      int dtype, void *hip_stream) {
+  const char *fn = "fa_fwd_varlen_mla";
+  g_err[0] = 0;
+  TRY(nonnull(fn, {q, k, v, o, cu_seqlens_q, cu_seqlens_k}));
+  TRY(positive(fn, {B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, Dqk, Dv}));
+  TRY(grouped(fn, Hq, Hkv));
+  TRY(scale_ok(fn, scale));
+  if (!fa_fwd_varlen_mla_supported(dtype, Dqk, Dv))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 and (Dqk, Dv) = (192, 128), got dtype=%s Dqk=%d Dv=%d", fn, fa_dtype_name(dtype), Dqk, Dv);
+  if (max_seqlen_q > total_q || max_seqlen_k > total_k)
+    return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen (%d, %d) exceeds the token count (%d, %d)", fn, max_seqlen_q, max_seqlen_k, total_q, total_k);
+  TRY(varlen_strides_ok(fn, "", Dqk, q_row_stride, q_head_stride, stride_mult(dtype)));
+  TRY(varlen_strides_ok(fn, "key ", Dqk, k_row_stride, k_head_stride, stride_mult(dtype)));
+  TRY(varlen_strides_ok(fn, "value ", Dv, v_row_stride, v_head_stride, stride_mult(dtype)));
+  TRY(varlen_strides_ok(fn, "output ", Dv, o_row_stride, o_head_stride, stride_mult(dtype)));
+  TRY(aligned16(fn, "tensors", {q, k, v, o}));
+  if (((uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q / cu_seqlens_k must be int32-aligned", fn);
+  // 32-bit byte offsets inside ONE sequence of one head, per tensor (fa_fwd_varlen's rule)
+  TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
+  TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)o_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
+  TRY(head_fits(fn, (double)(max_seqlen_k + 128) * (double)k_row_stride * 2, 4, " (one sequence of max_seqlen_k rows)"));
+  TRY(head_fits(fn, (double)(max_seqlen_k + 128) * (double)v_row_stride * 2, 4, " (one sequence of max_seqlen_k rows)"));
+  TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));
+  fa::VarlenMlaParams p;
+  p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
+  p.B = B; p.H = Hq; p.Hkv = Hkv; p.N = max_seqlen_q; p.Nk = max_seqlen_k; p.D = Dqk; p.scale = scale;
+  p.batch_stride = 0; p.head_stride = q_head_stride; p.kv_batch_stride = 0; p.kv_head_stride = k_head_stride;
+  p.is_causal = is_causal != 0;
+  p.cu_q = cu_seqlens_q; p.cu_k = cu_seqlens_k;
+  p.total_q = total_q; p.total_k = total_k;
+  p.q_rs = q_row_stride; p.kv_rs = k_row_stride;
+  p.v_rs = v_row_stride; p.v_head_stride = v_head_stride; p.o_rs = o_row_stride; p.o_head_stride = o_head_stride;
+  return launched(fn, fa::launch_mfma_varlen_mla(p, dtype, (hipStream_t)hip_stream));
+}
 int fa_fwd_varlen_window(const void *q, const void *k, const void *v, void *o, float *lse, const int *cu_seqlens_q, const int *cu_seqlens_k,
                          int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D, float scale,
                          long long q_row_stride, long long q_head_stride, long long kv_row_stride, long long kv_head_stride,

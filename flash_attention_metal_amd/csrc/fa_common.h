@@ -56,6 +56,12 @@ struct VarlenParams : Params {
   long long q_rs, kv_rs;      // row strides, elements
 };
 
+// one fa_fwd_varlen_mla call (the MLA mode of the varlen mode, csrc/fa_mfma_kernel.hip): q / k rows of 192 elements, v / o rows of 128, and
+// a (row, head) stride pair per tensor -- q: q_rs / head_stride, k: kv_rs / kv_head_stride, v and o: the four below. D holds 192.
+struct VarlenMlaParams : VarlenParams {
+  long long v_rs, v_head_stride, o_rs, o_head_stride;  // elements
+};
+
 // one fa_fwd_varlen_paged call (the varlen paged mode of csrc/fa_mfma_kernel.hip): the query side of VarlenParams (cu_k / total_k unused);
 // k / v are the page pools, kv_head_stride their head stride, kv_rs their row stride, Nk the capacity max_pages * page size. Key j of
 // sequence b is slot j % P of page block_table[b * bt_stride + j / P]; both tables are device memory read by the kernels.
@@ -227,6 +233,9 @@ hipError_t launch_tiled_v2(const Params &p, int dtype, hipStream_t s);
 hipError_t launch_mfma(const Params &p, int dtype, hipStream_t s);
 hipError_t launch_mfma_varlen(const VarlenParams &p, int dtype, hipStream_t s);
 bool mfma_varlen_supported(int dtype, int D);
+// fa_fwd_varlen_mla: (Dqk, Dv) = (192, 128), f16 / bf16
+hipError_t launch_mfma_varlen_mla(const VarlenMlaParams &p, int dtype, hipStream_t s);
+bool mfma_varlen_mla_supported(int dtype, int Dqk, int Dv);
 hipError_t launch_mfma_varlen_paged(const VarlenPagedParams &p, int dtype, hipStream_t s);
 bool mfma_varlen_paged_supported(int dtype, int D, int page_size);
 // page sizes of the paged entry points: 16, 32, 64, 128 or 256 rows

@@ -116,15 +116,24 @@ __device__ __forceinline__ float softcap_log2(const PT &p) { return softcap_of(p
 // Dynamic LDS of a workgroup of the body below, the figure every launcher passes: per split the K and V double buffers (K rows of D
 // bytes for e4m3 inputs, head_dim 96 rows in 256-byte slots); the epilogue's O tiles sit inside them, and the split merge buffer --
 // (16 D/32 + 2) floats per lane of the publishing waves -- behind the O tiles.
-template <typename Tag, int D, int SPLIT = 1, int ROWS = BM>
+// (DV != D, the MLA prefill mode: K rows of D elements in a two-part image, V and O rows of DV)
+template <typename Tag, int D, int SPLIT = 1, int ROWS = BM, int DV = D>
 constexpr size_t mfma_lds_bytes() {
-  constexpr size_t RB = (D == 96) ? 256 : D * 2, KRB = std::is_same<Tag, FP8>::value ? D : RB;
+  constexpr size_t RB = (D == 96) ? 256 : DV * 2, KRB = std::is_same<Tag, FP8>::value ? D : (DV != D) ? D * 2 : RB;
   constexpr size_t otiles = (size_t)ROWS * RB, merge_end = otiles + (size_t)(ROWS / WM) * (16 * (D / 32) + 2) * 64 * 4;
   return std::max(SPLIT * (2 * BN * KRB + 2 * BN * RB), SPLIT == 2 ? merge_end : otiles);
 }
 
-template <typename Tag, int D, bool CAUSAL, int SPLIT, bool PRESC, int ROWS = BM, typename PT = Params>
+template <typename Tag, int D, bool CAUSAL, int SPLIT, bool PRESC, int ROWS = BM, typename PT = Params, int DV = D>
 __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
+  // MLA (PT = VarlenMlaParams, D = 192, DV = 128; fa_fwd_varlen_mla): the varlen mode with two head dims -- q and k rows of D elements
+  // (128 "nope" + 64 rotary), v and o rows of DV -- and a (row, head) stride pair per tensor. Everything from the scores onwards is the
+  // head_dim-128 varlen kernel's. The K tile is a two-part LDS image: the nope part [64][128] is the head_dim-128 K image (swizzle chunk ^
+  // (row & 15)), the rotary part [64][64] behind it the head_dim-64 K image (chunk ^ ((row >> 1) & 7)); both are staged by LDS-DMA from
+  // the same 384-byte key row. A score chain runs the eight nope k-steps in the head_dim-128 kernel's order, then the four rotary ones:
+  // with zero rotary columns the call returns fa_fwd_varlen's bits at D = 128.
+  constexpr bool MLA = DV != D;
+  constexpr int KS_NOPE = MLA ? DV / 16 : D / 16;  // k-steps whose K fragments come from the first part of the K image
   constexpr bool PAGEDV = std::is_base_of<VarlenPagedParams, PT>::value;
   constexpr bool VARLEN = std::is_base_of<VarlenParams, PT>::value;
   // WINDOW (PT = VarlenWindowParams / VarlenPagedWindowParams; fa_fwd_varlen_window, fa_fwd_varlen_paged_window): the varlen modes under
@@ -160,7 +169,8 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   constexpr bool KSPLIT = std::is_same<PT, VarlenPagedKsplitParams>::value;
   static_assert(!KV8 || std::is_same<Tag, BF16>::value, "KV8 mode: bf16 queries, e4m3 pools widened to bf16");
   static_assert(!WINDOW || CAUSAL, "window mode: the upper bound is the causal one with its own offset");
-  static_assert(!VARLEN || (SPLIT == 1 && ROWS == BM && PRESC && !std::is_same<Tag, FP8>::value && (D == 64 || D == 128)),
+  static_assert(!MLA || (D == 192 && DV == 128 && std::is_same<PT, VarlenMlaParams>::value), "MLA mode: (192, 128) over VarlenMlaParams");
+  static_assert(!VARLEN || (SPLIT == 1 && ROWS == BM && PRESC && !std::is_same<Tag, FP8>::value && (D == 64 || D == 128 || MLA)),
                 "varlen mode: the plain 128-row kernel, 16-bit inputs, LDS-DMA staging");
   constexpr int RW = ROWS / WM;   // row groups = waves per split
   constexpr int ST = 64 * RW;     // threads per split (the staging map's width)
@@ -168,11 +178,12 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   using vec8 = typename M::vec8;
   using elem = typename M::elem;
   constexpr int GRB16 = D * 2;              // row bytes of a 16-bit row in global memory
-  constexpr int RB = (D == 96) ? 256 : D * 2;  // LDS row pitch (bytes)
-  constexpr int CPR = D / 8;                // 16-byte chunks per row that hold data
+  constexpr int RB = (D == 96) ? 256 : DV * 2;  // LDS row pitch (bytes; MLA mode: of a V / O row, and of the K image's nope part)
+  constexpr int RBR = 128;                  // MLA mode: row pitch of the K image's rotary part
+  constexpr int CPR = DV / 8;               // 16-byte chunks per row that hold data
   constexpr int CPRL = RB / 16;             // 16-byte slots per LDS row (power of two)
   constexpr int KS = D / 16;                // k-steps of the QK^T product
-  constexpr int DB = D / 32;                // 32-wide d blocks of O^T
+  constexpr int DB = DV / 32;               // 32-wide d blocks of O^T
   constexpr int TILE = BN * RB;             // bytes of one K (or V) tile in LDS
   constexpr bool IS_FP8 = std::is_same<Tag, FP8>::value;  // Q,K,V are e4m3 in HBM, bf16 from LDS onwards
   constexpr int GB = IS_FP8 ? 1 : 2;        // bytes per element in HBM
@@ -190,12 +201,12 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   // and subtracts per score). Costs one rounding of c.q (2^-9 relative for bf16, 2^-12 for f16) per operand element:
   // the score error stays a fraction of the P rounding that follows; LSE error scales with the score magnitude
   // (include/fa_mi355.h states the bound).
-  constexpr bool PRE = PRESC && prescale_applies<Tag, D>();
+  constexpr bool PRE = PRESC && (MLA || prescale_applies<Tag, D>());
   // fp8 inputs: the score product runs on v_mfma_scale_f32_32x32x64_f8f6f4 (unit E8M0 scales: an exact e4m3 product
   // at twice the bf16 rate, K = 64 per instruction). K stays e4m3 in LDS (rows of D bytes) and Q stays e4m3 in
   // registers; V is widened to bf16 while it is staged, because P has to be bf16 for the PV product anyway.
   constexpr int KRB = IS_FP8 ? D : RB;      // K row pitch in LDS (bytes)
-  constexpr int KTILE = BN * KRB;           // bytes of one K tile in LDS
+  constexpr int KTILE = MLA ? BN * (RB + RBR) : BN * KRB;  // bytes of one K tile in LDS
   constexpr int NS8 = IS_FP8 ? D / 64 : 1;  // fp8: 64-wide k-steps of the score product
   typedef int i32x8 __attribute__((ext_vector_type(8)));
 
@@ -203,7 +214,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   const int wave_all = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int sp = (SPLIT == 1) ? 0 : (wave_all / RW);  // which KV split this wave works on
   constexpr int GROUP_LDS = 2 * KTILE + 2 * TILE;     // K and V double buffers of one split
-  constexpr size_t LDS = mfma_lds_bytes<Tag, D, SPLIT, ROWS>();
+  constexpr size_t LDS = mfma_lds_bytes<Tag, D, SPLIT, ROWS, DV>();
   static_assert(SPLIT * GROUP_LDS <= LDS && RW * WM * RB <= LDS, "the launchers' LDS size covers the K / V buffers and the epilogue's O tiles");
   static_assert(SPLIT == 1 || RW * WM * RB + RW * (16 * DB + 2) * 64 * 4 <= LDS, "... and the split merge buffer");
   lds_char *smem = (lds_char *)smem_generic + sp * GROUP_LDS;
@@ -225,6 +236,8 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   // compile to the code they had before the mode existed):
   int LQ = 0, LK = 0;          // queries and keys of this block's sequence
   unsigned qrb = 0, kvrb = 0;  // row pitch of Q / O and of K / V in global memory, bytes
+  long long base_v = 0, base_o = 0;  // MLA mode: V and O have bases and row pitches of their own
+  unsigned vrb = 0, orb = 0;
   long long lse_base = 0;      // first LSE element of this block's (head, sequence)
   const int *ptbl = nullptr;   // varlen paged: this sequence's row of the block table
   int cl = 0, cu = 0;          // window mode: key j is visible to row i iff i + cl <= j <= i + cu
@@ -251,6 +264,12 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
     if constexpr (SINK) sink = p.sinks[hq];
     qrb = (unsigned)p.q_rs * 2;
     kvrb = (unsigned)p.kv_rs * (KV8 ? 1 : 2);
+    if constexpr (MLA) {
+      base_v = (long long)sk * p.v_rs + (long long)fdiv((unsigned)hq, p.fd_gq) * p.v_head_stride;
+      base_o = (long long)sq * p.o_rs + (long long)hq * p.o_head_stride;
+      vrb = (unsigned)p.v_rs * 2;
+      orb = (unsigned)p.o_rs * 2;
+    }
     // no key is visible to any row of the block (no keys at all, or causal with Lk < Lq: key j is visible to query i iff
     // j <= i + Lk - Lq): O = 0, LSE = -inf, as the paged decode defines it
     // (window mode: the block's rows see keys [k_lo, kv_hi) together; none when the range is empty: kv_hi = 0 then)
@@ -268,10 +287,10 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         if ((int)threadIdx.x < ROWS && row < LQ) *ksplit_lse2<D>(p, (int)blockIdx.y, lse_base + row) = -INFINITY;
         return;
       }
-      elem *Oz = (elem *)p.o + base;
+      elem *Oz = (elem *)p.o + (MLA ? base_o : base);
       for (int idx = threadIdx.x; idx < ROWS * CPR; idx += NTHREADS) {
         const int row = qb * ROWS + idx / CPR, ch = idx % CPR;
-        if (row < LQ) *reinterpret_cast<u32x4 *>(Oz + (long long)row * p.q_rs + ch * 8) = u32x4{0u, 0u, 0u, 0u};
+        if (row < LQ) *reinterpret_cast<u32x4 *>(Oz + (long long)row * (MLA ? (long long)(orb / 2) : p.q_rs) + ch * 8) = u32x4{0u, 0u, 0u, 0u};
       }
       const int row = qb * ROWS + (int)threadIdx.x;
       if (p.lse != nullptr && (int)threadIdx.x < ROWS && row < LQ) p.lse[lse_base + row] = SINK ? sink : -INFINITY;  // (sink mode: the sink alone)
@@ -297,7 +316,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(
       (void *)((const char *)p.k + (PAGEDV ? 0 : base_kv) * GB), 0, kv_head_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)((const char *)p.v + (PAGEDV ? 0 : base_kv) * GB), 0, kv_head_bytes, 0x00020000);
+      (void *)((const char *)p.v + (PAGEDV ? 0 : MLA ? base_v : base_kv) * GB), 0, MLA ? (unsigned)(LK - 1) * vrb + DV * 2 : kv_head_bytes, 0x00020000);
 
   // ---- Q fragments (B operand of K.Q^T): lane (r,h) holds Q[qrow][16ks+8h .. +7].
   // Rows >= N read as zero through the descriptor's range check.
@@ -323,7 +342,12 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   const int kx = (D == 32) ? ((r >> 2) & 3) : (D == 64) ? ((r >> 1) & 7) : (r & 15);
   int koff[KS];
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) koff[ks] = r * RB + (((2 * ks + h) ^ kx) << 4);
+  for (int ks = 0; ks < KS; ++ks) {
+    if (MLA && ks >= KS_NOPE) koff[ks] = BN * RB + r * RBR + (((2 * (ks - KS_NOPE) + h) ^ ((r >> 1) & 7)) << 4);  // the rotary part
+    else koff[ks] = r * RB + (((2 * ks + h) ^ kx) << 4);
+  }
+  // bytes between rows r and 32 + r of the K image that k-step ks reads
+#define FA_K32(ks) ((MLA && (ks) >= KS_NOPE) ? 32 * RBR : 32 * RB)
   // fp8 K rows are D bytes: the row image equals a 16-bit row of head_dim D/2 (same swizzle family)
   const int kx8 = (D == 64) ? ((r >> 2) & 3) : (D == 128) ? ((r >> 1) & 7) : (r & 15);
   // V: transposed read; 16-lane group g covers d columns 16(g&1).. of block db,
@@ -390,17 +414,24 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
 
   // LDS-DMA staging (FA_MFMA_DMA): wave w of a split moves the 1-KiB pieces w, w + RW, ... of each tile; inside a piece the
   // LDS image is lane-linear, so the chunk swizzle sits on the SOURCE address (one per-lane offset for K, one for V)
-  constexpr bool DMA = (FA_MFMA_DMA != 0) && !IS_FP8 && !KV8 && (D == 32 || D == 64 || D == 128);
+  constexpr bool DMA = (FA_MFMA_DMA != 0) && !IS_FP8 && !KV8 && (D == 32 || D == 64 || D == 128 || MLA);
   constexpr int RPP = 1024 / RB;                 // rows per piece
   constexpr int NPW = (BN / RPP) / RW;           // pieces per wave, tile and operand
   unsigned dma_kvo = 0, dma_vvo = 0;
+  unsigned dma_kro = 0;  // MLA mode: the rotary part's pieces, 8 rows of 128 bytes from byte 256 of the key row
+  constexpr int RPPR = 1024 / RBR, NPWR = (BN / RPPR) / RW;
+  if constexpr (MLA) {
+    static_assert((RW * RPPR) % 16 == 0 && NPWR >= 1, "the piece stride must keep the swizzle");
+    const int row = wave * RPPR + lane / (RBR / 16), pc = lane % (RBR / 16);
+    dma_kro = row * kvrb + DV * 2 + ((pc ^ ((row >> 1) & 7)) << 4);
+  }
   if constexpr (DMA) {
     static_assert((RW * RPP) % 16 == 0 || D == 32, "the piece stride must keep the swizzle");
     const int row = wave * RPP + lane / CPRL, pc = lane % CPRL;
     const int skx = (D == 32) ? ((row >> 2) & 3) : (D == 64) ? ((row >> 1) & 7) : (row & 15);
     const int svx = (D == 32) ? 0 : (D == 64) ? (((row >> 1) & 1) << 2) : ((row & 3) << 2);
     dma_kvo = VARLEN ? row * kvrb + ((pc ^ skx) << 4) : (unsigned)(row * GRB + ((pc ^ skx) << 4));
-    dma_vvo = VARLEN ? row * kvrb + ((pc ^ svx) << 4) : (unsigned)(row * GRB + ((pc ^ svx) << 4));
+    dma_vvo = VARLEN ? row * (MLA ? vrb : kvrb) + ((pc ^ svx) << 4) : (unsigned)(row * GRB + ((pc ^ svx) << 4));
     if constexpr (PAGEDV) {  // the lane's row inside its piece only: the piece's own slot in its page is wave-uniform and added per piece
       dma_kvo = (lane / CPRL) * kvrb + ((pc ^ skx) << 4);
       dma_vvo = (lane / CPRL) * kvrb + ((pc ^ svx) << 4);
@@ -448,6 +479,10 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         const unsigned vk = dma_kvo + so, vv = dma_vvo + so;
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lk), "v"(vk), "s"(rkp) : "memory");
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lv), "v"(vv), "s"(rvp) : "memory");
+      } else if constexpr (MLA) {  // the varlen arm below with V at its own pitch
+        const unsigned vk = dma_kvo + soff, vv = dma_vvo + ((unsigned)t * BN + j * (RW * RPP)) * vrb;
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lk), "v"(vk), "s"(rk) : "memory");
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lv), "v"(vv), "s"(rv) : "memory");
       } else if constexpr (VARLEN) {
         // the whole offset in voffset, i.e. inside the descriptor's range check: what follows a sequence's last key is another sequence
         // or the end of the tensor, and both must read as zeros (the dense kernel's heads end where its descriptors end)
@@ -457,6 +492,14 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
       } else {
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lk), "v"(dma_kvo), "s"(rk), "s"(soff) : "memory");
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lv), "v"(dma_vvo), "s"(rv), "s"(soff) : "memory");
+      }
+    }
+    if constexpr (MLA) {  // the rotary part, behind the nope part in the K buffer: the same key rows through the same descriptor
+#pragma unroll
+      for (int j = 0; j < NPWR; ++j) {
+        const unsigned lr = (unsigned)(__UINTPTR_TYPE__)Kbuf + buf * KTILE + BN * RB + (wave + RW * j) * 1024;
+        const unsigned vr = dma_kro + ((unsigned)t * BN + j * (RW * RPPR)) * kvrb;
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lr), "v"(vr), "s"(rk) : "memory");
       }
     }
     if constexpr (PAGEDV) fetch_pages(t + 1);
@@ -598,7 +641,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
       } else {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          const vec8 kf = __builtin_bit_cast(vec8, lds_read_b128(kptr[ks] + buf * KTILE + kb * 32 * RB));
+          const vec8 kf = __builtin_bit_cast(vec8, lds_read_b128(kptr[ks] + buf * KTILE + kb * FA_K32(ks)));
           s[kb] = M::mfma(kf, qf[ks], s[kb]);
         }
       }
@@ -700,9 +743,9 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
       } else {
         // head_dim 128: 16 K fragments would cost 64 VGPRs if held live; read each one LA MFMAs ahead of
         // its use instead (profile before: 9 % of wave time stalled on LDS issue, 14 % MFMA/VALU co-execution)
-        constexpr int NK = 2 * KS, LA = FA_LAK;
+        constexpr int NK = 2 * KS, LA = MLA ? 4 : FA_LAK;  // (MLA mode: the head_dim-128 kernel's look-ahead)
         vec8 kf[NK];
-        auto kread = [&](int i) { kf[i] = __builtin_bit_cast(vec8, lds_read_b128(kptr[i % KS] + buf * KTILE + (i / KS) * 32 * RB)); };
+        auto kread = [&](int i) { kf[i] = __builtin_bit_cast(vec8, lds_read_b128(kptr[i % KS] + buf * KTILE + (i / KS) * FA_K32(i % KS))); };
 #pragma unroll
         for (int i = 0; i < LA; ++i) kread(i);
         __builtin_amdgcn_sched_barrier(0);
@@ -841,7 +884,7 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
         }
       } else {
         // V^T fragments just in time, LA MFMAs ahead (step j = (kb, st, db))
-        constexpr int NV = 2 * 2 * DB, LA = FA_LAV;
+        constexpr int NV = 2 * 2 * DB, LA = MLA ? 4 : FA_LAV;
         s16x4 wlo[NV], whi[NV];
         auto vread = [&](int j) {
           const lds_char *vb = vptr[j % DB] + buf * TILE + (32 * (j / (2 * DB)) + 16 * ((j / DB) % 2)) * RB;
@@ -1004,20 +1047,21 @@ __device__ __forceinline__ void fwd_mfma_body(const PT &p) {
   }
   __syncthreads();
   if (sp == 0) {
-    elem *Og = (elem *)p.o + base;
+    elem *Og = (elem *)p.o + (MLA ? base_o : base);
 #pragma unroll
     for (int it = 0; it < WM * CPR / 64; ++it) {
       const int idx = it * 64 + lane;
       const int row = idx / CPR, ch = idx % CPR;
       const u32x4 vv = lds_read_b128(Ot + row * RB + ((ch ^ (row & (CPRL - 1))) << 4));
       if (qw0 + row < FA_NQ)
-        *reinterpret_cast<u32x4 *>(Og + (VARLEN ? (long long)(qw0 + row) * (long long)(qrb / 2) : (long long)(qw0 + row) * D) + ch * 8) = vv;
+        *reinterpret_cast<u32x4 *>(Og + (VARLEN ? (long long)(qw0 + row) * (long long)((MLA ? orb : qrb) / 2) : (long long)(qw0 + row) * D) + ch * 8) = vv;
     }
   }
 }
 
 #undef FA_NQ
 #undef FA_NK
+#undef FA_K32
 
 template <typename Tag, int D, bool CAUSAL, bool PRESC>
 __global__ __launch_bounds__(NTHREADS, (main_kernel_occ4<Tag, D, PRESC>() ? 4 : D <= 64 ? 3 : D <= 128 ? 2 : 1)) void fwd_mfma_kernel(Params p) {
@@ -1096,6 +1140,13 @@ __global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_kv8_sink
 template <typename Tag, int D>
 __global__ __launch_bounds__(NTHREADS, (D <= 64 ? 3 : 2)) void fwd_mfma_ksplit_paged_kernel(VarlenPagedKsplitParams p) {
   fwd_mfma_body<Tag, D, true, 1, true, BM, VarlenPagedKsplitParams>(p);
+}
+
+// fa_fwd_varlen_mla: the varlen kernel in MLA mode, (192, 128). 80 KiB of LDS: two workgroups fill a CU's 160 KiB, and the registers
+// are declared for two.
+template <typename Tag, bool CAUSAL>
+__global__ __launch_bounds__(NTHREADS, 2) void fwd_mfma_mla_kernel(VarlenMlaParams p) {
+  fwd_mfma_body<Tag, 192, CAUSAL, 1, true, BM, VarlenMlaParams, 128>(p);
 }
 
 // ... and its second launch, on the partial's own block map (one workgroup per (sequence, head, 128 rows), the same cu_seqlens_q lookup
@@ -1235,6 +1286,19 @@ bool mfma_varlen_supported(int dtype, int D) { return (dtype == FA_DTYPE_F16 || 
 hipError_t launch_mfma_varlen(const VarlenParams &p, int dtype, hipStream_t s) {
   return with_tag(dtype, [&](auto tag) {
     return with_dim_causal<64, 128>(p.D, p.is_causal, [&](auto d, auto c) { return launch_varlen_one<decltype(tag), d()>(fwd_mfma_varlen_kernel<decltype(tag), d(), c()>, p, s); });
+  });
+}
+
+bool mfma_varlen_mla_supported(int dtype, int Dqk, int Dv) { return (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) && Dqk == 192 && Dv == 128; }
+
+// (causal_head_group sized by the mean of the K and V row: the issue order only, never the results)
+hipError_t launch_mfma_varlen_mla(const VarlenMlaParams &p, int dtype, hipStream_t s) {
+  return with_tag(dtype, [&](auto tag) {
+    using Tag = decltype(tag);
+    constexpr size_t lds = mfma_lds_bytes<Tag, 192, 1, BM, 128>();
+    const int hg = causal_head_group(p, 160, 2);
+    if (p.is_causal) return launch_blocks(fwd_mfma_mla_kernel<Tag, true>, p, BM, NTHREADS, lds, hg, s);
+    return launch_blocks(fwd_mfma_mla_kernel<Tag, false>, p, BM, NTHREADS, lds, hg, s);
   });
 }
 

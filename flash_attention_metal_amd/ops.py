@@ -492,6 +492,72 @@ def flash_attention_varlen(
     return out, lse
 
 
+def varlen_mla_supported(dtype: str, d_qk: int, d_v: int) -> bool:
+    return bool(load_library().fa_fwd_varlen_mla_supported(DTYPES[dtype], int(d_qk), int(d_v)))
+
+
+def flash_attention_varlen_mla(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    cu_seqlens_k: torch.Tensor,
+    max_seqlen_q: int,
+    max_seqlen_k: int,
+    is_causal: bool = False,
+    scale: Optional[float] = None,
+    return_lse: bool = True,
+    out: Optional[torch.Tensor] = None,
+    lse: Optional[torch.Tensor] = None,
+    stream: Optional[int] = None,
+) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The MLA prefill forward over packed variable-length sequences (include/fa_mi355.h fa_fwd_varlen_mla): the non-absorbed form of
+    a latent-attention layer, q [total_q, Hq, 192], k [total_k, Hkv, 192] (128 "nope" + 64 rotary columns), v [total_k, Hkv, 128],
+    f16 / bf16. Strides are taken from EACH tensor, the element stride must be 1: q may be a slice of a wider projection, v the upper
+    half of the [total_k, Hkv, 256] output of the kv up-projection. cu_seqlens_* and everything they imply are flash_attention_varlen's:
+    int32 [B + 1] on q's device, read by the kernel only, so the call can be captured and replayed after the tables change in place;
+    causal is bottom-right aligned per sequence; a row with no visible key gets O = 0 and LSE = -inf; unowned tokens are not written.
+    scale=None means 192 ** -0.5 (nothing is derived from the value head dim). out: [total_q, Hq, 128], contiguous by default; any
+    strided tensor of that shape with unit element stride is written in place (a slice of a wider buffer). An inference path: no
+    backward. The chunked-context recipe (an un-masked call per cached chunk, a causal call on the new tokens, the LSE merge) is in
+    INTEGRATION.md, "Latent-attention layers: prefill".
+    Returns (out, lse): out [total_q, Hq, 128], lse [Hq, total_q]."""
+    lib = load_library()
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise ValueError(f"q [total_q,Hq,192], k [total_k,Hkv,192] and v [total_k,Hkv,128], got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
+    total_q, Hq, Dqk = q.shape
+    total_k, Hkv, Dk = k.shape
+    Dv = v.shape[2]
+    if Dk != Dqk or tuple(v.shape[:2]) != (total_k, Hkv) or Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"incompatible shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}")
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k.dtype} {v.dtype} (f16 or bf16)")
+    if q.stride(2) != 1 or k.stride(2) != 1 or v.stride(2) != 1:
+        raise ValueError("q, k, v need a unit element stride (a head of a token is contiguous elements)")
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if cu.dtype != torch.int32 or cu.dim() != 1 or cu.shape[0] < 2 or not cu.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 [B + 1] tensor")
+    if cu_seqlens_k.shape != cu_seqlens_q.shape:
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must both be [B + 1]")
+    B = cu_seqlens_q.shape[0] - 1
+    if not all(t.is_cuda and t.device == q.device for t in (q, k, v, cu_seqlens_q, cu_seqlens_k)):
+        raise RuntimeError("flash_attention_varlen_mla needs q, k, v and both cu_seqlens on one device: there is no CPU path")
+    if out is None:
+        out = torch.empty((total_q, Hq, Dv), dtype=q.dtype, device=q.device)
+    elif (not out.is_cuda or out.device != q.device or out.dtype != q.dtype or tuple(out.shape) != (total_q, Hq, Dv) or out.stride(2) != 1):
+        raise ValueError("out must be a device tensor of q's dtype and shape [total_q, Hq, d_v] with a unit element stride")
+    if lse is None:
+        lse = torch.empty((Hq, total_q), dtype=torch.float32, device=q.device) if return_lse else None
+    elif not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.shape != (Hq, total_q):
+        raise ValueError("lse must be contiguous fp32 [Hq, total_q] on q's device")
+    _call(lib, "fa_fwd_varlen_mla",
+          (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
+           B, Hq, Hkv, total_q, total_k, int(max_seqlen_q), int(max_seqlen_k), Dqk, Dv, _scale(scale, Dqk), q.stride(0), q.stride(1),
+           k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1), int(bool(is_causal)), _TORCH2FA[q.dtype]),
+          q.device, stream)
+    return out, lse
+
+
 def varlen_paged_supported(dtype: str, D: int, page_size: int) -> bool:
     return bool(load_library().fa_fwd_varlen_paged_supported(DTYPES[dtype], D, int(page_size)))
 

@@ -799,7 +799,7 @@ int fa_bwd_varlen_softcap(const void *q, const void *k, const void *v, const voi
  * fa_fwd_decode's, formed on the 576-wide rows.
  * The append needs no entry point of its own: fa_kv_append_paged with Hkv = 1, D = 576, k_new == v_new and k_pages == v_pages (a row is
  * 72 whole 16-byte chunks; both copies write the same bytes).
- * Not here: e4m3 latent pools, more than 32 packed rows, window / sink / softcap, the MLA prefill (192 / 128 head dims), a backward.
+ * Not here: e4m3 latent pools, more than 32 packed rows, window / sink / softcap, the MLA prefill (192 / 128 head dims: fa_fwd_varlen_mla, below), a backward.
  */
 int fa_fwd_mla_decode_paged(const void *q, const void *kv_pages, void *o, float *lse,
                             const int *block_table, const int *seqlens_k,
@@ -812,6 +812,53 @@ int fa_fwd_mla_decode_paged(const void *q, const void *kv_pages, void *o, float 
 /* depends on host scalars only (the split rule at the capacity); 0 if a size is invalid or unsupported */
 long long fa_fwd_mla_decode_paged_workspace_bytes(int B, int Hq, int Nq, int Dv, int page_size, int max_pages_per_seq);
 int fa_fwd_mla_decode_paged_supported(int dtype, int Dqk, int Dv, int Hq, int Nq, int page_size);
+
+/*
+ * Multi-head latent attention (prefill): fa_fwd_varlen_mla is the NON-absorbed form of the same layer, as serving engines run its
+ * prefill: the latent rows are up-projected to per-head keys and values, and ordinary multi-head attention runs over packed sequences
+ * with a query / key head dim of Dqk = 192 (128 "nope" + 64 rotary) and a value head dim of Dv = 128. Per sequence the operator is
+ * fa_fwd_varlen's with two head dims:
+ *     s_ij = q_i[0:192] . k_j[0:192]      P = softmax_j(scale * s_ij) over visible keys      O_i[0:128] = sum_j P_ij * v_j[0:128]
+ * LSE is in natural log, [Hq, total_q] fp32 contiguous, or NULL. `scale` is the caller's (DeepSeek: 192^-0.5 times its mscale); nothing
+ * is derived from Dv.
+ * Everything fa_fwd_varlen promises holds, in its words: cu_seqlens_q / cu_seqlens_k (int32, [B + 1]) are DEVICE memory read by the
+ * kernels -- the host never reads them and the launch geometry depends on the host scalars alone (B * Hq * ceil(max_seqlen_q / 128)
+ * workgroups), so one captured graph serves any set of lengths under the same B, total_* and max_seqlen_*. Every table entry is clamped
+ * to [0, total], a non-increasing pair gives length 0, and the lengths Lq_b / Lk_b are clamped to max_seqlen_q / max_seqlen_k: rows of a
+ * sequence beyond that clamp and tokens at or past cu_seqlens_q[B] are not written, neither are bytes between heads or rows under wide
+ * strides, and a corrupt table touches nothing outside tokens [0, total) of any tensor. Lk_b < Lq_b and Lk_b = 0 are legal: a row with
+ * no visible key gets O = 0 exactly and LSE = -inf. Causal is bottom-right aligned PER SEQUENCE (key j visible to query i iff
+ * j <= i + Lk_b - Lq_b); query head h reads key/value head h / (Hq / Hkv). Results are bitwise reproducible, nothing is allocated, the
+ * call is asynchronous on hip_stream.
+ * What differs: q, k, v and o EACH have their own (row, head) element strides -- token t, head h, element d of tensor x sits at
+ * t * x_row_stride + h * x_head_stride + d -- multiples of 8, at least 192 / 192 / 128 / 128, bases 16-byte aligned, element stride 1;
+ * (max_seqlen + 128) * row_stride * 2 bytes stay below 4 GiB for each of the four (max_seqlen_q for q and o, max_seqlen_k for k and v).
+ * So v may be a view of the [total_k, H, 256] output of the kv up-projection (head stride 256, offset 128: k's nope part is the other
+ * half), and o a slice of a wider buffer. O rows of 128 elements are written, never 192.
+ * f16 / bf16, (Dqk, Dv) = (192, 128): anything else FA_ERR_UNSUPPORTED with a message that names what was given. Null pointers (lse may
+ * be NULL), sizes < 1, Hq % Hkv != 0, scale <= 0, bad strides or alignment, max_seqlen_* > total_*, a sequence above the 4 GiB bound or
+ * a grid that does not fit an int: FA_ERR_INVALID_ARG before any launch; every rule shared with fa_fwd_varlen carries its status and
+ * its text after the function name.
+ * How it runs (csrc/fa_mfma_kernel.hip, MLA mode): the head_dim-128 varlen kernel from the scores onwards
+ * (pre-scaled query operand: tolerances are FA_VARIANT_MFMA's formed on the 192-wide rows, "LSE accuracy" above), over a two-part K
+ * image in LDS -- the head_dim-128 image of the nope columns, behind it the head_dim-64 image of the rotary columns. A score chain runs
+ * the eight nope k-steps, then the four rotary ones: with columns 128..191 of q and k zero, O and LSE are BIT-IDENTICAL to
+ * fa_fwd_varlen at D = 128 on the first 128 columns under the same scale.
+ * Chunked context ("Latent-attention layers: prefill"): one un-masked call per chunk of cached context, one causal
+ * call on the new tokens, merged by the caller through the LSEs.
+ * Not here: the rotary key as a separate broadcast tensor, a paged or e4m3 key side, window / sink / softcap, a key split, a backward,
+ * other head-dim pairs, an in-library merge.
+ */
+int fa_fwd_varlen_mla(const void *q, const void *k, const void *v, void *o, float *lse,
+                      const int *cu_seqlens_q, const int *cu_seqlens_k,
+                      int B, int Hq, int Hkv, int total_q, int total_k,
+                      int max_seqlen_q, int max_seqlen_k, int Dqk, int Dv, float scale,
+                      long long q_row_stride, long long q_head_stride,
+                      long long k_row_stride, long long k_head_stride,
+                      long long v_row_stride, long long v_head_stride,
+                      long long o_row_stride, long long o_head_stride,
+                      int is_causal, int dtype, void *hip_stream);
+int fa_fwd_varlen_mla_supported(int dtype, int Dqk, int Dv);   /* f16 | bf16, (192, 128) */
 
 /* 1 if fa_fwd has a kernel for the combination, else 0 (no GPU needed). */
 int fa_supported(int dtype, int variant, int D);
