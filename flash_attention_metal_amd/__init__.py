@@ -30,6 +30,8 @@ from .ops import (  # noqa: F401
     forward_kernel_name,
     kv_append_paged,
     mla_decode_paged_supported,
+    mla_decode_paged_wide_supported,
+    mla_decode_paged_wide_workspace_bytes,
     mla_decode_paged_workspace_bytes,
     supported,
     varlen_backward_supported,

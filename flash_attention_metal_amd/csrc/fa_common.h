@@ -212,7 +212,7 @@ struct MlaDecodeParams {
   const int *block_table, *seqlens;
   int B, Hq, Nq;
   int S;     // key splits per sequence
-  int RBLK;  // 16-row blocks: ceil(Hq * Nq / 16), 1 or 2
+  int RBLK;  // 16-row blocks: ceil(Hq * Nq / 16), 1 or 2 (fa_fwd_mla_decode_paged_wide: up to 8)
   float scale;
   long long q_bs, q_hs, q_rs, o_bs, o_hs, o_rs, page_stride, row_stride;  // elements
   int bt_stride, num_pages, max_pages;
@@ -294,6 +294,13 @@ hipError_t launch_mla_decode_paged(const MlaDecodeParams &p, int dtype, hipStrea
 bool mla_decode_supported(int dtype, int Dqk, int Dv);
 int mla_decode_splits(int B, int rblk, int Nk);
 long long mla_decode_workspace_bytes(int B, int Hq, int Nq, int Nk);
+// fa_fwd_mla_decode_paged_wide (csrc/fa_mla_wide_kernel.hip): up to 128 packed rows in workgroups of NW waves x 16 rows over one shared
+// tile image; the split rule is fed the ceil(rows / (16 NW)) workgroup row blocks; the workspace format and the combine kernel are the
+// one-wave call's
+inline int mla_wide_waves(int rows) { return rows <= 32 ? 2 : 4; }
+hipError_t launch_mla_decode_paged_wide(const MlaDecodeParams &p, int dtype, hipStream_t s);
+hipError_t launch_mla_combine(const MlaDecodeParams &p, int dtype, hipStream_t s);
+long long mla_decode_wide_workspace_bytes(int B, int Hq, int Nq, int Nk);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);

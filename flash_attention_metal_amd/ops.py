@@ -356,6 +356,14 @@ def mla_decode_paged_workspace_bytes(B: int, Hq: int, Nq: int, d_v: int, page_si
     return int(load_library().fa_fwd_mla_decode_paged_workspace_bytes(B, Hq, Nq, d_v, page_size, max_pages_per_seq))
 
 
+def mla_decode_paged_wide_supported(dtype: str, d_qk: int, d_v: int, Hq: int, Nq: int, page_size: int) -> bool:
+    return bool(load_library().fa_fwd_mla_decode_paged_wide_supported(DTYPES[dtype], d_qk, d_v, Hq, Nq, page_size))
+
+
+def mla_decode_paged_wide_workspace_bytes(B: int, Hq: int, Nq: int, d_v: int, page_size: int, max_pages_per_seq: int) -> int:
+    return int(load_library().fa_fwd_mla_decode_paged_wide_workspace_bytes(B, Hq, Nq, d_v, page_size, max_pages_per_seq))
+
+
 def flash_attention_mla_decode_paged(
     q: torch.Tensor,
     kv_pages: torch.Tensor,
@@ -369,15 +377,20 @@ def flash_attention_mla_decode_paged(
     lse: Optional[torch.Tensor] = None,
     workspace: Optional[torch.Tensor] = None,
     stream: Optional[int] = None,
+    wide: Optional[bool] = None,
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """The absorbed MLA decode step over a paged latent cache (include/fa_mi355.h fa_fwd_mla_decode_paged): q [B,Hq,Nq,576] under any
-    strides with a unit last stride (head-major or a token-major view), Hq * Nq <= 32; kv_pages ONE pool [num_pages, P, 576] or
+    """The absorbed MLA decode step over a paged latent cache (include/fa_mi355.h fa_fwd_mla_decode_paged and
+    fa_fwd_mla_decode_paged_wide): q [B,Hq,Nq,576] under any strides with a unit last stride (head-major or a token-major view), up to 128
+    rows Hq * Nq; kv_pages ONE pool [num_pages, P, 576] or
     [num_pages, P, 1, 576], f16 / bf16 like q, P in {16, 32, 64, 128, 256}: all 576 columns of a row enter the score, the first d_v = 512
     are the value. block_table int32 [B, max_pages_per_seq] and seqlens_k int32 [B] are contiguous device tensors read by the kernels only:
     nothing here synchronises, the call can be captured in a graph. `scale` is required (the model's, e.g. (128 + 64) ** -0.5 * mscale ** 2:
     the head dim of the model is not 576). Returns O [B,Hq,Nq,d_v] (allocated head-major if `out` is None; any strides with a unit last
     stride otherwise) and LSE [B,Hq,Nq] fp32 or None. A row with no visible key gets O = 0 and LSE = -inf. `workspace`: a uint8 device
-    tensor of at least mla_decode_paged_workspace_bytes(...) bytes (allocated here if None)."""
+    tensor of at least mla_decode_paged_workspace_bytes(...) bytes (allocated here if None). `wide` chooses the entry point: None sends
+    Hq * Nq <= 32 to fa_fwd_mla_decode_paged (one-wave items) and more rows to fa_fwd_mla_decode_paged_wide (workgroups of two or four waves
+    over a shared tile); True forces the wide call for any row count it supports, False the other. The wide call's workspace is sized by
+    mla_decode_paged_wide_workspace_bytes(...)."""
     lib = load_library()
     if scale is None:
         raise ValueError("flash_attention_mla_decode_paged needs the model's scale: there is no default (the head dim of the model is not 576)")
@@ -402,8 +415,10 @@ def flash_attention_mla_decode_paged(
         raise ValueError("out must be a [B,Hq,Nq,d_v] device tensor of q's dtype with a unit last stride")
     lse = _lse(lse, return_lse, q)
     max_pages = block_table.shape[1]
-    ws = _workspace(workspace, mla_decode_paged_workspace_bytes(B, Hq, Nq, d_v, P, max(max_pages, 1)), q.device)
-    _call(lib, "fa_fwd_mla_decode_paged",
+    wide = Hq * Nq > 32 if wide is None else bool(wide)
+    need = (mla_decode_paged_wide_workspace_bytes if wide else mla_decode_paged_workspace_bytes)(B, Hq, Nq, d_v, P, max(max_pages, 1))
+    ws = _workspace(workspace, need, q.device)
+    _call(lib, "fa_fwd_mla_decode_paged_wide" if wide else "fa_fwd_mla_decode_paged",
           (q.data_ptr(), kv_pages.data_ptr(), out.data_ptr(), _ptr(lse), block_table.data_ptr(), seqlens_k.data_ptr(), B, Hq, Nq, Dqk, d_v, P,
            num_pages, max_pages, float(scale), q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2), ps, rs,
            block_table.stride(0), int(bool(is_causal)), _TORCH2FA[q.dtype], ws.data_ptr(), ws.numel()), q.device, stream)

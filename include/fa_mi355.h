@@ -799,7 +799,8 @@ int fa_bwd_varlen_softcap(const void *q, const void *k, const void *v, const voi
  * fa_fwd_decode's, formed on the 576-wide rows.
  * The append needs no entry point of its own: fa_kv_append_paged with Hkv = 1, D = 576, k_new == v_new and k_pages == v_pages (a row is
  * 72 whole 16-byte chunks; both copies write the same bytes).
- * Not here: e4m3 latent pools, more than 32 packed rows, window / sink / softcap, the MLA prefill (192 / 128 head dims: fa_fwd_varlen_mla, below), a backward.
+ * Not here: e4m3 latent pools, more than 32 packed rows (fa_fwd_mla_decode_paged_wide, below: up to 128), window / sink / softcap, the MLA prefill
+ * (192 / 128 head dims: fa_fwd_varlen_mla, below), a backward.
  */
 int fa_fwd_mla_decode_paged(const void *q, const void *kv_pages, void *o, float *lse,
                             const int *block_table, const int *seqlens_k,
@@ -812,6 +813,39 @@ int fa_fwd_mla_decode_paged(const void *q, const void *kv_pages, void *o, float 
 /* depends on host scalars only (the split rule at the capacity); 0 if a size is invalid or unsupported */
 long long fa_fwd_mla_decode_paged_workspace_bytes(int B, int Hq, int Nq, int Dv, int page_size, int max_pages_per_seq);
 int fa_fwd_mla_decode_paged_supported(int dtype, int Dqk, int Dv, int Hq, int Nq, int page_size);
+
+/*
+ * Multi-head latent attention (decode, wide): fa_fwd_mla_decode_paged_wide is fa_fwd_mla_decode_paged for up to 128 packed query rows:
+ * all 128 heads on one GPU under data-parallel attention, or k-token verification at 16 heads (16 x 3 = 48 rows, 16 x 8 = 128). The
+ * argument list is identical, and so is the contract, in the same words: packed rows r = h * Nq + i; three strides each for q and o;
+ * the one pool [num_pages, P, 576]; device-side tables read by the kernels only (graph-capturable); causal bottom-right aligned; a row
+ * with no visible key gets O = 0 exactly and LSE = -inf; slots >= L_b and pages outside the pool read as zeros; no dependence on the
+ * workspace's prior contents; bitwise reproducible; asynchronous, allocates nothing; O rows of 512 elements are written, never 576.
+ * Supported: f16 / bf16, (Dqk, Dv) = (576, 512), 1 <= Hq * Nq <= 128, P in {16, 32, 64, 128, 256}; anything else FA_ERR_UNSUPPORTED with
+ * a message that names what was given. Both calls validate on one path: every rule they share carries the same status and the same
+ * text after the function name.
+ * How it runs (csrc/fa_mla_wide_kernel.hip): a WORKGROUP of NW waves shares one tile image in LDS, NW = 2 for
+ * Hq * Nq <= 32 and NW = 4 above. Row-to-wave map: wave w of row block wb holds packed rows 16 * (wb * NW + w) .. + 15 and does with
+ * them exactly what a one-wave item of fa_fwd_mla_decode_paged does (the same source text: over the same key split its bits are that
+ * call's); wave w stages rows (64 / NW) * w .. of every 64-key tile, so each latent row is streamed once for 16 * NW query rows. Grid
+ * (B * S, WB) with WB = ceil(Hq * Nq / (16 * NW)) row blocks, 64 * NW threads, 144 KiB of LDS. Split rule: S is
+ * fa_fwd_mla_decode_paged's rule fed WB in place of the number of 16-row blocks, evaluated at the capacity (host scalars only, S <= 256).
+ * The workspace has that call's format, B * S * rows16 * (Dv + 2) floats with rows16 = 16 * ceil(Hq * Nq / 16) (wave w of block wb
+ * writes 16-row slot wb * NW + w; a wave whose 16 rows are all padding has no slot and writes nothing), and its combine kernel runs
+ * unchanged. For Hq * Nq <= 32 both calls are legal; they differ in S, hence in the last bits, and in cost (README.md, round 26).
+ * Not here: e4m3 latent pools, more than 128 packed rows, window / sink / softcap.
+ */
+int fa_fwd_mla_decode_paged_wide(const void *q, const void *kv_pages, void *o, float *lse,
+                                 const int *block_table, const int *seqlens_k,
+                                 int B, int Hq, int Nq, int Dqk, int Dv,
+                                 int page_size, int num_pages, int max_pages_per_seq, float scale,
+                                 long long q_batch_stride, long long q_head_stride, long long q_row_stride,
+                                 long long o_batch_stride, long long o_head_stride, long long o_row_stride,
+                                 long long kv_page_stride, long long kv_row_stride, long long block_table_stride,
+                                 int is_causal, int dtype, void *workspace, long long workspace_bytes, void *hip_stream);
+/* depends on host scalars only (the split rule at the capacity); 0 if a size is invalid or unsupported */
+long long fa_fwd_mla_decode_paged_wide_workspace_bytes(int B, int Hq, int Nq, int Dv, int page_size, int max_pages_per_seq);
+int fa_fwd_mla_decode_paged_wide_supported(int dtype, int Dqk, int Dv, int Hq, int Nq, int page_size);
 
 /*
  * Multi-head latent attention (prefill): fa_fwd_varlen_mla is the NON-absorbed form of the same layer, as serving engines run its
