@@ -29,6 +29,8 @@ from .ops import (  # noqa: F401
     flash_attention_varlen_paged,
     forward_kernel_name,
     kv_append_paged,
+    mla_decode_paged_kv8_supported,
+    mla_decode_paged_kv8_workspace_bytes,
     mla_decode_paged_supported,
     mla_decode_paged_wide_supported,
     mla_decode_paged_wide_workspace_bytes,

@@ -31,6 +31,9 @@ SYMBOLS = {
     "fa_fwd_mla_decode_paged_wide": (c_int, [c_void_p] * 6 + [c_int] * 8 + [c_float] + [c_longlong] * 9 + [c_int, c_int, c_void_p, c_longlong, c_void_p]),
     "fa_fwd_mla_decode_paged_wide_workspace_bytes": (c_longlong, [c_int] * 6),
     "fa_fwd_mla_decode_paged_wide_supported": (c_int, [c_int] * 6),
+    "fa_fwd_mla_decode_paged_kv8": (c_int, [c_void_p] * 6 + [c_int] * 8 + [c_float] + [c_longlong] * 9 + [c_int, c_int, c_int, c_void_p, c_longlong, c_void_p]),
+    "fa_fwd_mla_decode_paged_kv8_workspace_bytes": (c_longlong, [c_int] * 6),
+    "fa_fwd_mla_decode_paged_kv8_supported": (c_int, [c_int] * 7),
     "fa_fwd_varlen_mla": (c_int, [c_void_p] * 7 + [c_int] * 9 + [c_float] + [c_longlong] * 8 + [c_int, c_int, c_void_p]),
     "fa_fwd_varlen_mla_supported": (c_int, [c_int] * 3),
     "fa_fwd_varlen_paged": (c_int, [c_void_p] * 8+ [c_int] * 9 + [c_float] + [c_longlong] * 6 + [c_int, c_int, c_void_p]),

@@ -699,9 +699,10 @@ int fa_fwd_decode_paged_softcap(const void *q, const void *k_pages, const void *
                            &softcap);
 }
 
-// ---- fa_fwd_mla_decode_paged and fa_fwd_mla_decode_paged_wide: the paged decode's rules on one latent pool. q and o carry three strides
-// each (a rule of these calls' own); everything else is the shared helpers, in fa_fwd_decode_paged's order, with its statuses and texts.
-// One path for both: the row limit (32 / 128), the block count the split rule is fed and the launcher are all that differ.
+// ---- fa_fwd_mla_decode_paged, fa_fwd_mla_decode_paged_wide and fa_fwd_mla_decode_paged_kv8: the paged decode's rules on one latent pool.
+// q and o carry three strides each (a rule of these calls' own); everything else is the shared helpers, in fa_fwd_decode_paged's order,
+// with its statuses and texts. One path for all three: the row limit (32 / 128), the block count the split rule is fed, the launcher
+// and, for the e4m3 pool, the dtype pair and the pool's stride multiple are all that differ.
 static bool mla_decode_shape_ok(int dtype, int Dqk, int Dv, int Hq, int Nq, int page_size, int max_rows) {
   return fa::mla_decode_supported(dtype, Dqk, Dv) && Hq >= 1 && Nq >= 1 && (long long)Hq * Nq <= max_rows && fa::page_size_ok(page_size);
 }
@@ -730,47 +731,66 @@ static int mla_strides_ok(const char *fn, const char *what, int B, int D, long l
                 what, bs, hs, rs, D);
   return FA_OK;
 }
-// wide: workgroups of 2 or 4 waves over a shared tile (fa_mla_wide_kernel.hip), up to 128 rows; otherwise one-wave items, up to 32
-static int mla_decode_paged_impl(const char *fn, bool wide, const void *q, const void *kv_pages, void *o, float *lse, const int *block_table,
+// The three modes of the one path. MLA_WIDE: workgroups of 2 or 4 waves over a shared tile (fa_mla_wide_kernel.hip), up to 128 rows.
+// MLA_ONE: one-wave items, up to 32. MLA_KV8: bf16 queries on an e4m3 pool (fa_mla_kv8_kernel.hip), always four waves, up to 128 rows, the
+// wide call's split count and workspace; `dtype` is the queries' and kv_dtype the pool's (the other modes: both are `dtype`)
+enum { MLA_ONE = 0, MLA_WIDE = 1, MLA_KV8 = 2 };
+static bool mla_kv8_shape_ok(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int Nq, int page_size) {
+  return q_dtype == FA_DTYPE_BF16 && kv_dtype == FA_DTYPE_FP8_E4M3 && mla_decode_shape_ok(FA_DTYPE_BF16, Dqk, Dv, Hq, Nq, page_size, 128);
+}
+static int mla_decode_paged_impl(const char *fn, int mode, const void *q, const void *kv_pages, void *o, float *lse, const int *block_table,
                                  const int *seqlens_k, int B, int Hq, int Nq, int Dqk, int Dv, int page_size, int num_pages,
                                  int max_pages_per_seq, float scale, long long q_batch_stride, long long q_head_stride, long long q_row_stride,
                                  long long o_batch_stride, long long o_head_stride, long long o_row_stride, long long kv_page_stride,
-                                 long long kv_row_stride, long long block_table_stride, int is_causal, int dtype, void *workspace,
+                                 long long kv_row_stride, long long block_table_stride, int is_causal, int dtype, int kv_dtype, void *workspace,
                                  long long workspace_bytes, void *hip_stream) {
   g_err[0] = 0;
+  const bool wide = mode != MLA_ONE;  // (the e4m3 mode has the wide call's row limit, split count and workspace)
   const int max_rows = wide ? 128 : 32;
   TRY(nonnull(fn, {q, kv_pages, o, block_table, seqlens_k, workspace}));
   TRY(positive(fn, {B, Hq, Nq, Dqk, Dv, page_size, num_pages, max_pages_per_seq}));
   TRY(scale_ok(fn, scale));
-  if (!mla_decode_shape_ok(dtype, Dqk, Dv, Hq, Nq, page_size, max_rows))
+  if (mode == MLA_KV8) {
+    if (!mla_kv8_shape_ok(dtype, kv_dtype, Dqk, Dv, Hq, Nq, page_size))
+      return fail(FA_ERR_UNSUPPORTED, "%s: needs bf16 queries on an e4m3 pool, (Dqk, Dv) = (576, 512), Hq * Nq <= %d packed query rows and a "
+                  "page size of 16, 32, 64, 128 or 256; got q=%s kv=%s Dqk=%d Dv=%d Hq=%d Nq=%d page_size=%d", fn, max_rows,
+                  fa_dtype_name(dtype), fa_dtype_name(kv_dtype), Dqk, Dv, Hq, Nq, page_size);
+  } else if (!mla_decode_shape_ok(dtype, Dqk, Dv, Hq, Nq, page_size, max_rows))
     return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 (q and the pool alike), (Dqk, Dv) = (576, 512), Hq * Nq <= %d packed query rows and a "
                 "page size of 16, 32, 64, 128 or 256; got dtype=%s Dqk=%d Dv=%d Hq=%d Nq=%d page_size=%d", fn, max_rows, fa_dtype_name(dtype),
                 Dqk, Dv, Hq, Nq, page_size);
   TRY(table_stride_ok(fn, block_table_stride, max_pages_per_seq));
   TRY(mla_strides_ok(fn, "", B, Dqk, q_batch_stride, q_head_stride, q_row_stride));
   TRY(mla_strides_ok(fn, "output ", B, Dv, o_batch_stride, o_head_stride, o_row_stride));
-  TRY(page_strides_ok(fn, Dqk, page_size, kv_page_stride, kv_row_stride, kv_row_stride, block_table_stride, dtype));  // (one latent head: no head stride)
+  // (one latent head: no head stride. An e4m3 pool: strides in elements = bytes, multiples of 16 -- fa_fwd_decode_paged's rule)
+  TRY(page_strides_ok(fn, Dqk, page_size, kv_page_stride, kv_row_stride, kv_row_stride, block_table_stride, kv_dtype));
   TRY(aligned16(fn, "tensors and workspace", {q, kv_pages, o, workspace}));
   TRY(page_tables_ok(fn, page_size, max_pages_per_seq, block_table, seqlens_k));
   const int cap = page_size * max_pages_per_seq;
-  TRY(workspace_fits(fn, workspace_bytes, wide ? fa::mla_decode_wide_workspace_bytes(B, Hq, Nq, cap) : fa::mla_decode_workspace_bytes(B, Hq, Nq, cap),
-                     wide ? "fa_fwd_mla_decode_paged_wide_workspace_bytes" : "fa_fwd_mla_decode_paged_workspace_bytes"));
+  TRY(workspace_fits(fn, workspace_bytes,
+                     mode == MLA_KV8    ? fa::mla_decode_kv8_workspace_bytes(B, Hq, Nq, cap)
+                     : mode == MLA_WIDE ? fa::mla_decode_wide_workspace_bytes(B, Hq, Nq, cap)
+                                        : fa::mla_decode_workspace_bytes(B, Hq, Nq, cap),
+                     mode == MLA_KV8    ? "fa_fwd_mla_decode_paged_kv8_workspace_bytes"
+                     : mode == MLA_WIDE ? "fa_fwd_mla_decode_paged_wide_workspace_bytes"
+                                        : "fa_fwd_mla_decode_paged_workspace_bytes"));
   const int rblk = (Hq * Nq + 15) / 16;
   if ((long long)B * Hq * Nq > 0x7fffffffLL || (long long)B * 256 * rblk > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
-  const int nw = fa::mla_wide_waves(Hq * Nq);
+  const int nw = mode == MLA_KV8 ? 4 : fa::mla_wide_waves(Hq * Nq);
   fa::MlaDecodeParams p;
   p.q = q; p.kv = kv_pages; p.o = o; p.lse = lse; p.ws = (float *)workspace;
   p.block_table = block_table; p.seqlens = seqlens_k;
   p.B = B; p.Hq = Hq; p.Nq = Nq; p.RBLK = rblk; p.scale = scale;
-  p.S = fa::mla_decode_splits(B, wide ? (rblk + nw - 1) / nw : rblk, cap);  // (the wide call: workgroup row blocks of 16 NW rows)
+  p.S = fa::mla_decode_splits(B, wide ? (rblk + nw - 1) / nw : rblk, cap);  // (the wide and e4m3 calls: workgroup row blocks of 16 NW rows)
   p.q_bs = q_batch_stride; p.q_hs = q_head_stride; p.q_rs = q_row_stride;
   p.o_bs = o_batch_stride; p.o_hs = o_head_stride; p.o_rs = o_row_stride;
   p.page_stride = kv_page_stride; p.row_stride = kv_row_stride;
   p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
   p.lp = log2_of(page_size);
   p.is_causal = is_causal ? 1 : 0;
-  return launched(fn, wide ? fa::launch_mla_decode_paged_wide(p, dtype, (hipStream_t)hip_stream)
-                           : fa::launch_mla_decode_paged(p, dtype, (hipStream_t)hip_stream));
+  return launched(fn, mode == MLA_KV8    ? fa::launch_mla_decode_paged_kv8(p, (hipStream_t)hip_stream)
+                      : mode == MLA_WIDE ? fa::launch_mla_decode_paged_wide(p, dtype, (hipStream_t)hip_stream)
+                                         : fa::launch_mla_decode_paged(p, dtype, (hipStream_t)hip_stream));
 }
 int fa_fwd_mla_decode_paged(const void *q, const void *kv_pages, void *o, float *lse, const int *block_table, const int *seqlens_k, int B,
                             int Hq, int Nq, int Dqk, int Dv, int page_size, int num_pages, int max_pages_per_seq, float scale,
@@ -778,10 +798,10 @@ int fa_fwd_mla_decode_paged(const void *q, const void *kv_pages, void *o, float 
                             long long o_head_stride, long long o_row_stride, long long kv_page_stride, long long kv_row_stride,
                             long long block_table_stride, int is_causal, int dtype, void *workspace, long long workspace_bytes,
                             void *hip_stream) {
-  return mla_decode_paged_impl("fa_fwd_mla_decode_paged", false, q, kv_pages, o, lse, block_table, seqlens_k, B, Hq, Nq, Dqk, Dv, page_size,
+  return mla_decode_paged_impl("fa_fwd_mla_decode_paged", MLA_ONE, q, kv_pages, o, lse, block_table, seqlens_k, B, Hq, Nq, Dqk, Dv, page_size,
                                num_pages, max_pages_per_seq, scale, q_batch_stride, q_head_stride, q_row_stride, o_batch_stride, o_head_stride,
-                               o_row_stride, kv_page_stride, kv_row_stride, block_table_stride, is_causal, dtype, workspace, workspace_bytes,
-                               hip_stream);
+                               o_row_stride, kv_page_stride, kv_row_stride, block_table_stride, is_causal, dtype, dtype, workspace,
+                               workspace_bytes, hip_stream);
 }
 int fa_fwd_mla_decode_paged_wide(const void *q, const void *kv_pages, void *o, float *lse, const int *block_table, const int *seqlens_k, int B,
                                  int Hq, int Nq, int Dqk, int Dv, int page_size, int num_pages, int max_pages_per_seq, float scale,
@@ -789,10 +809,30 @@ int fa_fwd_mla_decode_paged_wide(const void *q, const void *kv_pages, void *o, f
                                  long long o_head_stride, long long o_row_stride, long long kv_page_stride, long long kv_row_stride,
                                  long long block_table_stride, int is_causal, int dtype, void *workspace, long long workspace_bytes,
                                  void *hip_stream) {
-  return mla_decode_paged_impl("fa_fwd_mla_decode_paged_wide", true, q, kv_pages, o, lse, block_table, seqlens_k, B, Hq, Nq, Dqk, Dv, page_size,
+  return mla_decode_paged_impl("fa_fwd_mla_decode_paged_wide", MLA_WIDE, q, kv_pages, o, lse, block_table, seqlens_k, B, Hq, Nq, Dqk, Dv, page_size,
                                num_pages, max_pages_per_seq, scale, q_batch_stride, q_head_stride, q_row_stride, o_batch_stride, o_head_stride,
-                               o_row_stride, kv_page_stride, kv_row_stride, block_table_stride, is_causal, dtype, workspace, workspace_bytes,
-                               hip_stream);
+                               o_row_stride, kv_page_stride, kv_row_stride, block_table_stride, is_causal, dtype, dtype, workspace,
+                               workspace_bytes, hip_stream);
+}
+
+// fa_fwd_mla_decode_paged_kv8: the wide call on an e4m3 pool under bf16 queries -- the third mode of the path above
+int fa_fwd_mla_decode_paged_kv8_supported(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int Nq, int page_size) {
+  return mla_kv8_shape_ok(q_dtype, kv_dtype, Dqk, Dv, Hq, Nq, page_size);
+}
+long long fa_fwd_mla_decode_paged_kv8_workspace_bytes(int B, int Hq, int Nq, int Dv, int page_size, int max_pages_per_seq) {
+  if (!mla_workspace_scalars_ok(B, Hq, Nq, Dv, page_size, max_pages_per_seq, 128)) return 0;
+  return fa::mla_decode_kv8_workspace_bytes(B, Hq, Nq, page_size * max_pages_per_seq);
+}
+int fa_fwd_mla_decode_paged_kv8(const void *q, const void *kv_pages, void *o, float *lse, const int *block_table, const int *seqlens_k, int B,
+                                int Hq, int Nq, int Dqk, int Dv, int page_size, int num_pages, int max_pages_per_seq, float scale,
+                                long long q_batch_stride, long long q_head_stride, long long q_row_stride, long long o_batch_stride,
+                                long long o_head_stride, long long o_row_stride, long long kv_page_stride, long long kv_row_stride,
+                                long long block_table_stride, int is_causal, int q_dtype, int kv_dtype, void *workspace,
+                                long long workspace_bytes, void *hip_stream) {
+  return mla_decode_paged_impl("fa_fwd_mla_decode_paged_kv8", MLA_KV8, q, kv_pages, o, lse, block_table, seqlens_k, B, Hq, Nq, Dqk, Dv,
+                               page_size, num_pages, max_pages_per_seq, scale, q_batch_stride, q_head_stride, q_row_stride, o_batch_stride,
+                               o_head_stride, o_row_stride, kv_page_stride, kv_row_stride, block_table_stride, is_causal, q_dtype, kv_dtype,
+                               workspace, workspace_bytes, hip_stream);
 }
 
 int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size) { return fa::mfma_varlen_paged_supported(dtype, D, page_size); }

@@ -301,6 +301,10 @@ inline int mla_wide_waves(int rows) { return rows <= 32 ? 2 : 4; }
 hipError_t launch_mla_decode_paged_wide(const MlaDecodeParams &p, int dtype, hipStream_t s);
 hipError_t launch_mla_combine(const MlaDecodeParams &p, int dtype, hipStream_t s);
 long long mla_decode_wide_workspace_bytes(int B, int Hq, int Nq, int Nk);
+// fa_fwd_mla_decode_paged_kv8 (csrc/fa_mla_kv8_kernel.hip): bf16 queries on an e4m3 latent pool, always four waves, the tile staged through
+// registers and widened into the wide call's image; the wide call's split count, workspace and combine kernel
+hipError_t launch_mla_decode_paged_kv8(const MlaDecodeParams &p, hipStream_t s);
+long long mla_decode_kv8_workspace_bytes(int B, int Hq, int Nq, int Nk);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);

@@ -364,6 +364,14 @@ def mla_decode_paged_wide_workspace_bytes(B: int, Hq: int, Nq: int, d_v: int, pa
     return int(load_library().fa_fwd_mla_decode_paged_wide_workspace_bytes(B, Hq, Nq, d_v, page_size, max_pages_per_seq))
 
 
+def mla_decode_paged_kv8_supported(q_dtype: str, kv_dtype: str, d_qk: int, d_v: int, Hq: int, Nq: int, page_size: int) -> bool:
+    return bool(load_library().fa_fwd_mla_decode_paged_kv8_supported(DTYPES[q_dtype], DTYPES[kv_dtype], d_qk, d_v, Hq, Nq, page_size))
+
+
+def mla_decode_paged_kv8_workspace_bytes(B: int, Hq: int, Nq: int, d_v: int, page_size: int, max_pages_per_seq: int) -> int:
+    return int(load_library().fa_fwd_mla_decode_paged_kv8_workspace_bytes(B, Hq, Nq, d_v, page_size, max_pages_per_seq))
+
+
 def flash_attention_mla_decode_paged(
     q: torch.Tensor,
     kv_pages: torch.Tensor,
@@ -390,12 +398,21 @@ def flash_attention_mla_decode_paged(
     tensor of at least mla_decode_paged_workspace_bytes(...) bytes (allocated here if None). `wide` chooses the entry point: None sends
     Hq * Nq <= 32 to fa_fwd_mla_decode_paged (one-wave items) and more rows to fa_fwd_mla_decode_paged_wide (workgroups of two or four waves
     over a shared tile); True forces the wide call for any row count it supports, False the other. The wide call's workspace is sized by
-    mla_decode_paged_wide_workspace_bytes(...)."""
+    mla_decode_paged_wide_workspace_bytes(...).
+    A torch.float8_e4m3fn pool under bf16 q goes to fa_fwd_mla_decode_paged_kv8 for every row count up to 128 (no scales: the bytes are
+    read as plain e4m3 values; a caller that appended with k_mul = v_mul = 1 / s passes scale * s and multiplies O by s). O is bf16, the
+    workspace is sized by mla_decode_paged_kv8_workspace_bytes(...); `wide` is ignored there, except that wide=False raises ValueError
+    (that pool has no one-wave form), and f16 q on such a pool raises ValueError."""
     lib = load_library()
     if scale is None:
         raise ValueError("flash_attention_mla_decode_paged needs the model's scale: there is no default (the head dim of the model is not 576)")
     if q.dim() != 4 or kv_pages.dim() not in (3, 4) or (kv_pages.dim() == 4 and kv_pages.shape[2] != 1):
         raise ValueError("q [B,Hq,Nq,576], kv_pages one [num_pages,P,576] or [num_pages,P,1,576] latent pool")
+    kv8 = _FP8 is not None and kv_pages.dtype == _FP8
+    if kv8 and q.dtype != torch.bfloat16:
+        raise ValueError(f"unsupported dtypes {q.dtype} {kv_pages.dtype}: a float8_e4m3fn latent pool takes bf16 queries only")
+    if kv8 and wide is not None and not wide:
+        raise ValueError("wide=False on a float8_e4m3fn latent pool: fa_fwd_mla_decode_paged_kv8 has no one-wave form")
     if not all(t.is_cuda and t.device == q.device for t in (q, kv_pages, block_table, seqlens_k)):
         raise ValueError("flash_attention_mla_decode_paged needs q, the pool and both tables on one device: there is no CPU path")
     B, Hq, Nq, Dqk = q.shape
@@ -406,7 +423,7 @@ def flash_attention_mla_decode_paged(
     if (block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or not block_table.is_contiguous()
             or seqlens_k.dtype != torch.int32 or seqlens_k.shape != (B,) or not seqlens_k.is_contiguous()):
         raise ValueError("block_table must be a contiguous int32 [B, max_pages_per_seq] tensor and seqlens_k a contiguous int32 [B] one")
-    if q.dtype not in (torch.float16, torch.bfloat16) or kv_pages.dtype != q.dtype:
+    if not kv8 and (q.dtype not in (torch.float16, torch.bfloat16) or kv_pages.dtype != q.dtype):
         raise ValueError(f"unsupported / mixed dtypes {q.dtype} {kv_pages.dtype} (f16 or bf16, q and the pool alike)")
     d_v = int(d_v)
     if out is None:
@@ -415,6 +432,14 @@ def flash_attention_mla_decode_paged(
         raise ValueError("out must be a [B,Hq,Nq,d_v] device tensor of q's dtype with a unit last stride")
     lse = _lse(lse, return_lse, q)
     max_pages = block_table.shape[1]
+    if kv8:
+        ws = _workspace(workspace, mla_decode_paged_kv8_workspace_bytes(B, Hq, Nq, d_v, P, max(max_pages, 1)), q.device)
+        _call(lib, "fa_fwd_mla_decode_paged_kv8",
+              (q.data_ptr(), kv_pages.data_ptr(), out.data_ptr(), _ptr(lse), block_table.data_ptr(), seqlens_k.data_ptr(), B, Hq, Nq, Dqk, d_v,
+               P, num_pages, max_pages, float(scale), q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2), ps,
+               rs, block_table.stride(0), int(bool(is_causal)), _TORCH2FA[q.dtype], _TORCH2FA[kv_pages.dtype], ws.data_ptr(), ws.numel()),
+              q.device, stream)
+        return out, lse
     wide = Hq * Nq > 32 if wide is None else bool(wide)
     need = (mla_decode_paged_wide_workspace_bytes if wide else mla_decode_paged_workspace_bytes)(B, Hq, Nq, d_v, P, max(max_pages, 1))
     ws = _workspace(workspace, need, q.device)

@@ -799,7 +799,8 @@ int fa_bwd_varlen_softcap(const void *q, const void *k, const void *v, const voi
  * fa_fwd_decode's, formed on the 576-wide rows.
  * The append needs no entry point of its own: fa_kv_append_paged with Hkv = 1, D = 576, k_new == v_new and k_pages == v_pages (a row is
  * 72 whole 16-byte chunks; both copies write the same bytes).
- * Not here: e4m3 latent pools, more than 32 packed rows (fa_fwd_mla_decode_paged_wide, below: up to 128), window / sink / softcap, the MLA prefill
+ * Not here: more than 32 packed rows (fa_fwd_mla_decode_paged_wide, below: up to 128), e4m3 latent pools (fa_fwd_mla_decode_paged_kv8, below),
+ * window / sink / softcap, the MLA prefill
  * (192 / 128 head dims: fa_fwd_varlen_mla, below), a backward.
  */
 int fa_fwd_mla_decode_paged(const void *q, const void *kv_pages, void *o, float *lse,
@@ -833,7 +834,7 @@ int fa_fwd_mla_decode_paged_supported(int dtype, int Dqk, int Dv, int Hq, int Nq
  * The workspace has that call's format, B * S * rows16 * (Dv + 2) floats with rows16 = 16 * ceil(Hq * Nq / 16) (wave w of block wb
  * writes 16-row slot wb * NW + w; a wave whose 16 rows are all padding has no slot and writes nothing), and its combine kernel runs
  * unchanged. For Hq * Nq <= 32 both calls are legal; they differ in S, hence in the last bits, and in cost (README.md, round 26).
- * Not here: e4m3 latent pools, more than 128 packed rows, window / sink / softcap.
+ * Not here: more than 128 packed rows, window / sink / softcap (e4m3 latent pools: fa_fwd_mla_decode_paged_kv8, below).
  */
 int fa_fwd_mla_decode_paged_wide(const void *q, const void *kv_pages, void *o, float *lse,
                                  const int *block_table, const int *seqlens_k,
@@ -846,6 +847,50 @@ int fa_fwd_mla_decode_paged_wide(const void *q, const void *kv_pages, void *o, f
 /* depends on host scalars only (the split rule at the capacity); 0 if a size is invalid or unsupported */
 long long fa_fwd_mla_decode_paged_wide_workspace_bytes(int B, int Hq, int Nq, int Dv, int page_size, int max_pages_per_seq);
 int fa_fwd_mla_decode_paged_wide_supported(int dtype, int Dqk, int Dv, int Hq, int Nq, int page_size);
+
+/*
+ * Multi-head latent attention (decode, e4m3 pool): fa_fwd_mla_decode_paged_kv8 is fa_fwd_mla_decode_paged_wide under bf16 queries on a latent
+ * pool of OCP e4m3 (e4m3fn) bytes: 576 bytes per key in place of 1152, twice the context or the batch in the same memory. The argument
+ * list is the wide call's with `int dtype` replaced by `int q_dtype, int kv_dtype`.
+ * Supported: (q_dtype, kv_dtype) = (FA_DTYPE_BF16, FA_DTYPE_FP8_E4M3) only, O is bf16; (Dqk, Dv) = (576, 512), 1 <= Hq * Nq <= 128,
+ * P in {16, 32, 64, 128, 256}; anything else -- (f16, e4m3), (e4m3, e4m3) and (bf16, bf16) included -- FA_ERR_UNSUPPORTED with a message
+ * that names what was given. fa_fwd_mla_decode_paged_supported / _wide_supported keep answering 0 for e4m3: those calls are untouched.
+ * The pool is [num_pages, P, 576] bytes; kv_page_stride and kv_row_stride count elements (= bytes), are multiples of 16 and at least 576,
+ * the base is 16-byte aligned (fa_fwd_decode_paged's rule for e4m3 pools, with its status and text); one page stays below 2 GiB. q and o
+ * keep the wide call's rules: three strides each, multiples of 8, bf16.
+ * NO SCALES, in the words of fa_fwd_decode_kv8: the bytes are read as plain e4m3 values. K and V are the same bytes here, so there is one
+ * per-tensor scale s: a caller that appended with k_mul = v_mul = 1 / s passes scale * s to this call and multiplies O by s (or folds s
+ * into the projection behind it).
+ * THE CONTRACT: the result is the wide call on the exactly widened pool. O and LSE are BIT-IDENTICAL to
+ * fa_fwd_mla_decode_paged_wide(..., FA_DTYPE_BF16) on a bf16 pool that holds the same values widened (every e4m3 value is a bf16 value) --
+ * the same page order, the same strides in elements, the same slots unused, the same table entries out of range -- for every legal
+ * Hq * Nq. The split count S and the workspace size are the wide call's: fa_fwd_mla_decode_paged_kv8_workspace_bytes equals
+ * fa_fwd_mla_decode_paged_wide_workspace_bytes on every legal input and is 0 where that is 0. Everything else is inherited in the same
+ * words: the tolerances and "LSE accuracy"; a row with no visible key gets O = 0 exactly and LSE = -inf; clamped lengths; slots >= L_b
+ * and pages outside [0, num_pages) read as zeros (the e4m3 NaN bytes 0x7F / 0xFF there are harmless); no dependence on the workspace's
+ * prior contents; bitwise reproducible; device-side tables read by the kernels only (graph-capturable); asynchronous, allocates nothing.
+ * Validation runs on the path of the other two calls: every rule shared with the wide call carries the same status and the same text
+ * after the function name; only the dtype pair and the 16-element stride rule differ.
+ * The quantising append needs no entry point of its own: fa_kv_append_paged_quant with Hkv = 1, D = 576, k_pages == v_pages, k_new ==
+ * v_new and k_mul == v_mul (a row is 36 whole 16-byte chunks; both copies write the same bytes).
+ * How it runs (csrc/fa_mla_kv8_kernel.hip): the wide call's four-wave workgroup for EVERY row count (for
+ * Hq * Nq <= 32 the split rule is still fed one row block, so S is the wide call's). LDS-DMA cannot widen, so wave w stages rows
+ * 16 * w .. + 15 of a tile through registers: nine 16-byte loads per lane under one range-checked descriptor, widened and written into
+ * the wide call's tile image with its swizzles, one tile ahead of the arithmetic. From LDS onwards the source text is the wide call's.
+ * Not here: f16 or e4m3 queries, scales inside the kernel, block or per-token scales, a bf16 rotary part behind an e4m3 latent part,
+ * more than 128 rows, window / sink / softcap.
+ */
+int fa_fwd_mla_decode_paged_kv8(const void *q, const void *kv_pages, void *o, float *lse,
+                                const int *block_table, const int *seqlens_k,
+                                int B, int Hq, int Nq, int Dqk, int Dv,
+                                int page_size, int num_pages, int max_pages_per_seq, float scale,
+                                long long q_batch_stride, long long q_head_stride, long long q_row_stride,
+                                long long o_batch_stride, long long o_head_stride, long long o_row_stride,
+                                long long kv_page_stride, long long kv_row_stride, long long block_table_stride,
+                                int is_causal, int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes, void *hip_stream);
+/* the wide call's size on every legal input; 0 if a size is invalid or unsupported */
+long long fa_fwd_mla_decode_paged_kv8_workspace_bytes(int B, int Hq, int Nq, int Dv, int page_size, int max_pages_per_seq);
+int fa_fwd_mla_decode_paged_kv8_supported(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int Nq, int page_size);
 
 /*
  * Multi-head latent attention (prefill): fa_fwd_varlen_mla is the NON-absorbed form of the same layer, as serving engines run its
