@@ -26,6 +26,7 @@ from .ops import (  # noqa: F401
     flash_attention_varlen,
     flash_attention_varlen_backward,
     flash_attention_varlen_mla,
+    flash_attention_varlen_mla_backward,
     flash_attention_varlen_paged,
     forward_kernel_name,
     kv_append_paged,
@@ -38,6 +39,7 @@ from .ops import (  # noqa: F401
     supported,
     varlen_backward_supported,
     varlen_backward_workspace_bytes,
+    varlen_mla_backward_supported,
     varlen_mla_supported,
     varlen_paged_kv8_supported,
     varlen_paged_num_splits,

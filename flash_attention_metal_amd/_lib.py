@@ -36,6 +36,8 @@ SYMBOLS = {
     "fa_fwd_mla_decode_paged_kv8_supported": (c_int, [c_int] * 7),
     "fa_fwd_varlen_mla": (c_int, [c_void_p] * 7 + [c_int] * 9 + [c_float] + [c_longlong] * 8 + [c_int, c_int, c_void_p]),
     "fa_fwd_varlen_mla_supported": (c_int, [c_int] * 3),
+    "fa_bwd_varlen_mla": (c_int, [c_void_p] * 12 + [c_int] * 9 + [c_float] + [c_longlong] * 8 + [c_int, c_int, c_void_p]),
+    "fa_bwd_varlen_mla_supported": (c_int, [c_int] * 3),
     "fa_fwd_varlen_paged": (c_int, [c_void_p] * 8+ [c_int] * 9 + [c_float] + [c_longlong] * 6 + [c_int, c_int, c_void_p]),
     "fa_fwd_varlen_paged_supported": (c_int, [c_int] * 3),
     "fa_fwd_varlen_window": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_float] + [c_longlong] * 4 + [c_int, c_int, c_int, c_void_p]),

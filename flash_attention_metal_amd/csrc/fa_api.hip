@@ -1239,6 +1239,43 @@ int fa_bwd_varlen_softcap(const void *q, const void *k, const void *v, const voi
                          total_k, max_seqlen_q, max_seqlen_k, D, scale, q_row_stride, q_head_stride, kv_row_stride, kv_head_stride,
                          window_left, window_right, dtype, hip_stream, nullptr, nullptr, &softcap);
 }
+// fa_bwd_varlen_mla: fa_bwd_varlen's rules in its order, with the stride, alignment and 4 GiB rules once per tensor as fa_fwd_varlen_mla
+// has them (q, k, v, o; d_o under o's strides, the gradients under those of q, k, v)
+int fa_bwd_varlen_mla_supported(int dtype, int Dqk, int Dv) { return fa::bwd_varlen_mla_supported(dtype, Dqk, Dv); }
+int fa_bwd_varlen_mla(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq, float *dk,
+                      float *dv, void *workspace, const int *cu_seqlens_q, const int *cu_seqlens_k, int B, int Hq, int Hkv, int total_q,
+                      int total_k, int max_seqlen_q, int max_seqlen_k, int Dqk, int Dv, float scale, long long q_row_stride,
+                      long long q_head_stride, long long k_row_stride, long long k_head_stride, long long v_row_stride,
+                      long long v_head_stride, long long o_row_stride, long long o_head_stride, int is_causal, int dtype, void *hip_stream) {
+  const char *fn = "fa_bwd_varlen_mla";
+  g_err[0] = 0;
+  TRY(nonnull(fn, {q, k, v, o, d_o, lse, dq, dk, dv, workspace, cu_seqlens_q, cu_seqlens_k}));
+  TRY(positive(fn, {B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, Dqk, Dv}));
+  TRY(grouped(fn, Hq, Hkv));
+  TRY(scale_ok(fn, scale));
+  if (!fa_bwd_varlen_mla_supported(dtype, Dqk, Dv))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 and (Dqk, Dv) = (192, 128), got dtype=%s Dqk=%d Dv=%d", fn, fa_dtype_name(dtype), Dqk, Dv);
+  if (max_seqlen_q > total_q || max_seqlen_k > total_k)
+    return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen (%d, %d) exceeds the token count (%d, %d)", fn, max_seqlen_q, max_seqlen_k, total_q, total_k);
+  TRY(varlen_strides_ok(fn, "", Dqk, q_row_stride, q_head_stride, stride_mult(dtype)));
+  TRY(varlen_strides_ok(fn, "key ", Dqk, k_row_stride, k_head_stride, stride_mult(dtype)));
+  TRY(varlen_strides_ok(fn, "value ", Dv, v_row_stride, v_head_stride, stride_mult(dtype)));
+  TRY(varlen_strides_ok(fn, "output ", Dv, o_row_stride, o_head_stride, stride_mult(dtype)));
+  TRY(aligned16(fn, "tensors", {q, k, v, o, d_o, dq, dk, dv}));
+  if (((uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k) & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q / cu_seqlens_k must be int32-aligned", fn);
+  if (((uintptr_t)lse | (uintptr_t)workspace) & 3) return fail(FA_ERR_INVALID_ARG, "%s: lse / workspace must be fp32-aligned", fn);
+  // 32-bit byte offsets inside ONE sequence of one head of the 16-bit tensors, per tensor (the gradients are stored through 64-bit addresses)
+  TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)q_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
+  TRY(head_fits(fn, (double)(max_seqlen_q + 128) * (double)o_row_stride * 2, 4, " (one sequence of max_seqlen_q rows)"));
+  TRY(head_fits(fn, (double)(max_seqlen_k + 128) * (double)k_row_stride * 2, 4, " (one sequence of max_seqlen_k rows)"));
+  TRY(head_fits(fn, (double)(max_seqlen_k + 128) * (double)v_row_stride * 2, 4, " (one sequence of max_seqlen_k rows)"));
+  TRY(grid_fits(fn, (long long)B * Hq, max_seqlen_q));   // the dQ kernel's
+  TRY(grid_fits(fn, (long long)B * Hkv, max_seqlen_k));  // the dK/dV kernel's
+  return launched(fn, fa::launch_bwd_varlen_mla(q, k, v, o, d_o, lse, dq, dk, dv, (float *)workspace, cu_seqlens_q, cu_seqlens_k, B, Hq, Hkv,
+                                                total_q, total_k, max_seqlen_q, max_seqlen_k, scale, q_row_stride, q_head_stride, k_row_stride,
+                                                k_head_stride, v_row_stride, v_head_stride, o_row_stride, o_head_stride, is_causal ? 1 : 0,
+                                                dtype, (hipStream_t)hip_stream));
+}
 int fa_window_query_range(int Lq, int Lk, int window_left, int window_right, int key_first, int key_last, int *row_lo, int *row_hi) {
   g_err[0] = 0;
   if (!row_lo || !row_hi) return fail(FA_ERR_INVALID_ARG, "fa_window_query_range: null pointer");

@@ -332,6 +332,13 @@ hipError_t launch_bwd_varlen_softcap(const void *q, const void *k, const void *v
                                      float *dk, float *dv, float *ws, const int *cu_q, const int *cu_k, int B, int H, int Hkv, int total_q,
                                      int total_k, int max_q, int max_k, int D, float scale, long long q_rs, long long q_hs, long long kv_rs,
                                      long long kv_hs, int wl, int wr, float softcap, int dtype, hipStream_t s);
+// fa_bwd_varlen_mla (csrc/fa_bwd_mla_kernels.hip): the backward of the MLA prefill, head dims (192, 128), a stride pair per tensor
+bool bwd_varlen_mla_supported(int dtype, int Dqk, int Dv);
+hipError_t launch_bwd_varlen_mla(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse, float *dq,
+                                 float *dk, float *dv, float *ws, const int *cu_q, const int *cu_k, int B, int H, int Hkv, int total_q,
+                                 int total_k, int max_q, int max_k, float scale, long long q_rs, long long q_hs, long long k_rs,
+                                 long long k_hs, long long v_rs, long long v_hs, long long o_rs, long long o_hs, int causal, int dtype,
+                                 hipStream_t s);
 // the sinks' gradient of fa_bwd_varlen_sink (csrc/fa_sink_kernels.hip): dsinks[h] = -sum_i exp(sinks[h] - lse[h, i]) * delta[h, i] over the
 // query tokens a sequence owns, one workgroup per head, launched behind the dQ kernel that wrote delta
 hipError_t launch_dsink(const float *sinks, const float *lse, const float *delta, float *dsinks, const int *cu_q, int B, int H, int total_q,

@@ -558,8 +558,8 @@ def flash_attention_varlen_mla(
     int32 [B + 1] on q's device, read by the kernel only, so the call can be captured and replayed after the tables change in place;
     causal is bottom-right aligned per sequence; a row with no visible key gets O = 0 and LSE = -inf; unowned tokens are not written.
     scale=None means 192 ** -0.5 (nothing is derived from the value head dim). out: [total_q, Hq, 128], contiguous by default; any
-    strided tensor of that shape with unit element stride is written in place (a slice of a wider buffer). An inference path: no
-    backward. The chunked-context recipe (an un-masked call per cached chunk, a causal call on the new tokens, the LSE merge) is in
+    strided tensor of that shape with unit element stride is written in place (a slice of a wider buffer). The backward is
+    flash_attention_varlen_mla_backward; torch.ops.fa_mi355.attention_varlen_mla is the differentiable op. The chunked-context recipe (an un-masked call per cached chunk, a causal call on the new tokens, the LSE merge) is in
     INTEGRATION.md, "Latent-attention layers: prefill".
     Returns (out, lse): out [total_q, Hq, 128], lse [Hq, total_q]."""
     lib = load_library()
@@ -897,6 +897,84 @@ def flash_attention_varlen_backward(
            int(max_seqlen_q), int(max_seqlen_k), D, _scale(scale, D), q.stride(0), q.stride(1), k.stride(0), k.stride(1),
            *mask, _TORCH2FA[q.dtype]), q.device, stream)
     return (dq, dk, dv) if sinks is None else (dq, dk, dv, dsinks)
+
+
+def varlen_mla_backward_supported(dtype: str, d_qk: int, d_v: int) -> bool:
+    return bool(load_library().fa_bwd_varlen_mla_supported(DTYPES[dtype], int(d_qk), int(d_v)))
+
+
+def flash_attention_varlen_mla_backward(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    o: torch.Tensor,
+    d_o: torch.Tensor,
+    lse: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    cu_seqlens_k: torch.Tensor,
+    max_seqlen_q: int,
+    max_seqlen_k: int,
+    is_causal: bool = False,
+    scale: Optional[float] = None,
+    dq: Optional[torch.Tensor] = None,
+    dk: Optional[torch.Tensor] = None,
+    dv: Optional[torch.Tensor] = None,
+    workspace: Optional[torch.Tensor] = None,
+    stream: Optional[int] = None,
+):
+    """The backward of flash_attention_varlen_mla (include/fa_mi355.h fa_bwd_varlen_mla): q [total_q, Hq, 192], k [total_k, Hkv, 192],
+    v [total_k, Hkv, 128], o and d_o [total_q, Hq, 128], f16 / bf16; lse the forward's [Hq, total_q]; the tables as in the forward.
+    Strides are taken from EACH of q, k, v, o (unit element stride); d_o must have o's strides. Returns (dq, dk, dv) in fp32 under the
+    ELEMENT strides of q / k / v respectively (allocated so unless given: with v the upper half of a [total_k, Hkv, 256] up-projection,
+    dv is the upper half of an fp32 buffer of that shape). Only tokens owned by a sequence are written (allocate with zeros if the rest
+    is read); a query row without a visible key gets dQ = 0 and adds nothing to dK / dV; a key no query sees gets dK = dV = 0.
+    scale=None means 192 ** -0.5. With dq, dk, dv and `workspace` (uint8, at least varlen_backward_workspace_bytes(Hq, total_q) bytes)
+    given the call allocates nothing, and it never synchronises or reads a device value: it can be captured in a graph and replayed
+    after the tables change in place."""
+    lib = load_library()
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or o.dim() != 3 or d_o.shape != o.shape:
+        raise ValueError(f"q [total_q,Hq,192], k [total_k,Hkv,192], v [total_k,Hkv,128], o and d_o [total_q,Hq,128], got {tuple(q.shape)} "
+                         f"{tuple(k.shape)} {tuple(v.shape)} {tuple(o.shape)} {tuple(d_o.shape)}")
+    total_q, Hq, Dqk = q.shape
+    total_k, Hkv, Dk = k.shape
+    Dv = v.shape[2]
+    if Dk != Dqk or tuple(v.shape[:2]) != (total_k, Hkv) or tuple(o.shape) != (total_q, Hq, Dv) or Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"incompatible shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} o {tuple(o.shape)}")
+    if q.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q.dtype for t in (k, v, o, d_o)):
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {k.dtype} {v.dtype} {o.dtype} {d_o.dtype} (f16 or bf16)")
+    if q.stride(2) != 1 or k.stride(2) != 1 or v.stride(2) != 1 or o.stride(2) != 1:
+        raise ValueError("q, k, v, o need a unit element stride (a head of a token is contiguous elements)")
+    if d_o.stride() != o.stride():
+        raise ValueError("o and d_o must share row/head strides")
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if cu.dtype != torch.int32 or cu.dim() != 1 or cu.shape[0] < 2 or not cu.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 [B + 1] tensor")
+    if cu_seqlens_k.shape != cu_seqlens_q.shape:
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must both be [B + 1]")
+    B = cu_seqlens_q.shape[0] - 1
+    if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.shape != (Hq, total_q):
+        raise ValueError("lse must be contiguous fp32 [Hq, total_q]")
+    if not all(t.is_cuda and t.device == q.device for t in (q, k, v, o, d_o, lse, cu_seqlens_q, cu_seqlens_k)):
+        raise RuntimeError("flash_attention_varlen_mla_backward needs every tensor and both cu_seqlens on one device: there is no CPU path")
+    grads = []
+    for name, g, like, like_name in (("dq", dq, q, "q"), ("dk", dk, k, "k"), ("dv", dv, v, "v")):
+        if g is None:
+            g = torch.empty_strided(like.shape, like.stride(), dtype=torch.float32, device=q.device)
+        elif not g.is_cuda or g.device != q.device or g.dtype != torch.float32 or g.shape != like.shape or g.stride() != like.stride():
+            raise ValueError(f"{name} must be an fp32 device tensor with the shape and element strides of {like_name} "
+                             "(the kernels write it under those strides)")
+        grads.append(g)
+    dq, dk, dv = grads
+    need = varlen_backward_workspace_bytes(Hq, total_q)
+    ws = _workspace(workspace, need, q.device)
+    if ws.numel() < need:
+        raise ValueError(f"workspace of {ws.numel()} bytes, varlen_backward_workspace_bytes() asks for {need}")
+    _call(lib, "fa_bwd_varlen_mla",
+          (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+           dv.data_ptr(), ws.data_ptr(), cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), B, Hq, Hkv, total_q, total_k,
+           int(max_seqlen_q), int(max_seqlen_k), Dqk, Dv, _scale(scale, Dqk), q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+           v.stride(0), v.stride(1), o.stride(0), o.stride(1), int(bool(is_causal)), _TORCH2FA[q.dtype]), q.device, stream)
+    return dq, dk, dv
 
 
 def flash_attention_backward(

@@ -30,6 +30,11 @@ same way. attention_varlen(..., window=(left, right)) dispatches to it.
 attention_varlen_window with one learnt sink logit per query head in every softmax denominator (fa_fwd_varlen_sink / fa_bwd_varlen_sink):
 sinks [Hq], any float dtype. Autograd gives q, k, v AND sinks their gradients, the sinks' in the parameter's own dtype.
 attention_varlen(..., sinks=) dispatches to it.
+
+    torch.ops.fa_mi355.attention_varlen_mla(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, scale) -> (o, lse)
+
+The MLA prefill (fa_fwd_varlen_mla / fa_bwd_varlen_mla): q [total_q, Hq, 192], k [total_k, Hkv, 192], v [total_k, Hkv, 128], o
+[total_q, Hq, 128], each under its own strides; scale = 0.0 means 192 ** -0.5. Differentiable in q, k, v like attention_varlen.
 """
 from __future__ import annotations
 
@@ -38,7 +43,7 @@ from typing import Tuple
 import torch
 
 from .ops import (_TORCH2FA, FaError, _out_dtype, _sink_window, _window, flash_attention_backward, flash_attention_forward, flash_attention_varlen,
-                  flash_attention_varlen_backward, load_library)
+                  flash_attention_varlen_backward, flash_attention_varlen_mla, flash_attention_varlen_mla_backward, load_library)
 
 _LIB = torch.library.Library("fa_mi355", "DEF")
 _LIB.define("attention_forward(Tensor q, Tensor k, Tensor v, bool is_causal=False, float scale=0.0) -> (Tensor, Tensor)")
@@ -309,6 +314,57 @@ def _varlen_softcap_backward(ctx, grad_o, grad_lse):
 
 torch.library.register_autograd("fa_mi355::attention_varlen_softcap", _varlen_softcap_backward, setup_context=_varlen_softcap_setup_context,
                                 lib=_LIB)
+
+
+_LIB.define("attention_varlen_mla(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor cu_seqlens_k, int max_seqlen_q, int max_seqlen_k, "
+            "bool is_causal=False, float scale=0.0) -> (Tensor, Tensor)")
+
+
+def _varlen_mla_impl(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=False, scale=0.0):
+    # (O zero-initialised and LSE -inf-initialised: tokens owned by no sequence are not written by the kernel)
+    out = torch.zeros((q.shape[0], q.shape[1], v.shape[2]), dtype=q.dtype, device=q.device)
+    lse = torch.full((q.shape[1], q.shape[0]), float("-inf"), dtype=torch.float32, device=q.device)
+    return flash_attention_varlen_mla(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=is_causal,
+                                      scale=(scale if scale > 0 else None), out=out, lse=lse)
+
+
+def _varlen_mla_meta(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=False, scale=0.0):
+    return q.new_empty((q.shape[0], q.shape[1], v.shape[2])), q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32)
+
+
+_LIB.impl("attention_varlen_mla", _varlen_mla_impl, "CUDA")
+_LIB.impl("attention_varlen_mla", _varlen_mla_meta, "Meta")
+
+
+def _varlen_mla_backward(ctx, grad_o, grad_lse):
+    q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
+    if grad_lse is not None:
+        raise NotImplementedError("fa_mi355::attention_varlen_mla: no gradient through the LSE output")
+    none = (None,) * 9
+    if grad_o is None:
+        return none
+    if q.dtype not in _TORCH2FA or not load_library().fa_bwd_varlen_mla_supported(_TORCH2FA[q.dtype], q.shape[2], v.shape[2]):
+        raise FaError(-2, f"no MLA backward kernel for q {tuple(q.shape)} v {tuple(v.shape)} {q.dtype} (f16 / bf16, head dims 192 / 128)",
+                      "fa_bwd_varlen_mla")
+    go = grad_o.to(o.dtype)
+    if go.stride() != o.stride():  # d_o is addressed under o's strides
+        go = torch.empty_strided(o.shape, o.stride(), dtype=o.dtype, device=q.device).copy_(go)
+    # zero-initialised: tokens owned by no sequence are not written by the kernels and get a zero gradient
+    dq = torch.empty_strided(q.shape, q.stride(), dtype=torch.float32, device=q.device).zero_()
+    dk = torch.empty_strided(k.shape, k.stride(), dtype=torch.float32, device=q.device).zero_()
+    dv = torch.empty_strided(v.shape, v.stride(), dtype=torch.float32, device=q.device).zero_()
+    flash_attention_varlen_mla_backward(q, k, v, o, go, lse, cu_q, cu_k, ctx.max_q, ctx.max_k, is_causal=ctx.is_causal,
+                                        scale=(ctx.scale if ctx.scale > 0 else None), dq=dq, dk=dk, dv=dv)
+    return (dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)) + none[3:]
+
+
+# (the context is attention_varlen's: the same inputs, outputs and host scalars)
+torch.library.register_autograd("fa_mi355::attention_varlen_mla", _varlen_mla_backward, setup_context=_varlen_setup_context, lib=_LIB)
+
+
+def attention_varlen_mla(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_seqlen_k: int, is_causal: bool = False, scale: float = 0.0):
+    """fa_mi355::attention_varlen_mla: the MLA prefill (head dims 192 / 128), differentiable in q, k, v through fa_bwd_varlen_mla."""
+    return torch.ops.fa_mi355.attention_varlen_mla(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, scale)
 
 
 def attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_seqlen_k: int, is_causal: bool = False, scale: float = 0.0,

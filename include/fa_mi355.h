@@ -925,8 +925,8 @@ int fa_fwd_mla_decode_paged_kv8_supported(int q_dtype, int kv_dtype, int Dqk, in
  * fa_fwd_varlen at D = 128 on the first 128 columns under the same scale.
  * Chunked context ("Latent-attention layers: prefill"): one un-masked call per chunk of cached context, one causal
  * call on the new tokens, merged by the caller through the LSEs.
- * Not here: the rotary key as a separate broadcast tensor, a paged or e4m3 key side, window / sink / softcap, a key split, a backward,
- * other head-dim pairs, an in-library merge.
+ * Not here: the rotary key as a separate broadcast tensor, a paged or e4m3 key side, window / sink / softcap, a key split, other
+ * head-dim pairs, an in-library merge. (The backward: fa_bwd_varlen_mla, below.)
  */
 int fa_fwd_varlen_mla(const void *q, const void *k, const void *v, void *o, float *lse,
                       const int *cu_seqlens_q, const int *cu_seqlens_k,
@@ -938,6 +938,44 @@ int fa_fwd_varlen_mla(const void *q, const void *k, const void *v, void *o, floa
                       long long o_row_stride, long long o_head_stride,
                       int is_causal, int dtype, void *hip_stream);
 int fa_fwd_varlen_mla_supported(int dtype, int Dqk, int Dv);   /* f16 | bf16, (192, 128) */
+
+/*
+ * Multi-head latent attention (prefill, backward): fa_bwd_varlen_mla is the backward of fa_fwd_varlen_mla -- the form in which these
+ * layers are trained. Per sequence it is fa_bwd_ex's operator with two head dims, on the forward's operator:
+ *     P = exp(scale * q.k - lse) over 192 columns       delta_i = sum_d dO_id O_id and dP = dO.V^T over 128 columns
+ *     dS = P o (dP - delta)       dQ = scale * dS K (192 wide)
+ *     dK = scale * dS^T Q (192 wide) and dV = P^T dO (128 wide), both summed over the query heads of a group.
+ * Layout: q, k, v and o each keep the forward's own (row, head) ELEMENT stride pair under the forward's rules (multiples of 8, at least
+ * 192 / 192 / 128 / 128, bases 16-byte aligned, the 4 GiB rule per tensor). d_o is addressed under o's strides. The fp32 gradients dq,
+ * dk, dv are addressed under the element strides of q, k, v respectively -- fa_bwd_varlen's convention applied tensor by tensor: with v
+ * the upper half of a [total_k, H, 256] kv up-projection, dv is the upper half of an fp32 buffer of that shape. lse is the forward's
+ * [Hq, total_q]. `workspace`: caller-owned device memory of fa_bwd_varlen_workspace_bytes(Hq, total_q) bytes; it holds delta,
+ * [Hq, total_q] fp32. There is no size function of its own.
+ * What is kept from fa_bwd_varlen, in its words: the cu_seqlens tables are DEVICE memory read by the kernels and clamped as the forward
+ * clamps them; both grids depend on host scalars only (B * Hq * ceil(max_seqlen_q / 128) and B * Hkv * ceil(max_seqlen_k / 128)
+ * workgroups), so the call can be captured in a graph. Only owned tokens are written -- dq rows of owned query tokens (192 elements),
+ * dk / dv rows of owned keys (192 / 128 elements) -- and no bytes between heads or rows under wide strides. dK = dV = 0 for a key no
+ * query sees. A dead query row (no visible key) is recognised by the forward's integer test and never by its LSE: it gets dQ = 0 exactly
+ * and adds exactly nothing to dK / dV. The result does not depend on the workspace's prior contents. Bitwise reproducible: no atomics,
+ * no allocation; asynchronous on hip_stream.
+ * f16 / bf16, (Dqk, Dv) = (192, 128): anything else FA_ERR_UNSUPPORTED with a message that names what was given. Every rule shared with
+ * fa_fwd_varlen_mla or fa_bwd_varlen carries that call's status and its text after the function name.
+ * The bit contract mirrors the forward's. With columns 128..191 of q and k zero, dq[..., :128], dk[..., :128] and dv are BIT-IDENTICAL to
+ * fa_bwd_varlen at D = 128 on the first 128 columns under the same scale, per sequence, and columns 128..191 of dq and dk are zero: the
+ * eight nope k-steps of a score chain run first in that kernel's order, then the four rotary ones; the dP chain and both second
+ * products run in its order (csrc/fa_bwd_mla_kernels.hip).
+ * Not here: a paged or e4m3 key side, window / sink / softcap, other head-dim pairs, the rotary key as a separate broadcast tensor, a
+ * gradient through LSE, a dense (non-varlen) form.
+ */
+int fa_bwd_varlen_mla(const void *q, const void *k, const void *v, const void *o, const void *d_o, const float *lse,
+                      float *dq, float *dk, float *dv, void *workspace,
+                      const int *cu_seqlens_q, const int *cu_seqlens_k,
+                      int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k,
+                      int Dqk, int Dv, float scale,
+                      long long q_row_stride, long long q_head_stride, long long k_row_stride, long long k_head_stride,
+                      long long v_row_stride, long long v_head_stride, long long o_row_stride, long long o_head_stride,
+                      int is_causal, int dtype, void *hip_stream);
+int fa_bwd_varlen_mla_supported(int dtype, int Dqk, int Dv);   /* f16 | bf16, (192, 128) */
 
 /* 1 if fa_fwd has a kernel for the combination, else 0 (no GPU needed). */
 int fa_supported(int dtype, int variant, int D);
