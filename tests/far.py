@@ -1,9 +1,11 @@
-"""Far addresses (test side only; Python ints, torch only inside the checker): where every call of tests/test_gpu_far_addresses.py puts
-its tensors, which 32-bit thresholds those placements cross, and a checker of what a call wrote into a sentinel-filled buffer.
+"""Far addresses (test side only; Python ints, torch only inside the checker): where every call of tests/test_gpu_far_addresses.py
+(cases()) and of tests/test_gpu_far_addresses_mla.py (mla_cases(): the MLA family) puts its tensors, which 32-bit thresholds those
+placements cross, and a checker of what a call wrote into a sentinel-filled buffer.
 
 The planner restates the host rules of include/fa_mi355.h and returns, per case, the scalars of the call and, per tensor it touches, the
-rows it owns as blocks (start, rows, row length, pitch) in ELEMENTS from the tensor's base, so that the smallest and largest element and
-byte offset follow in exact integers. A case names the thresholds it claims to cross (byte offset 2^31 / 2^32 / 2^33, element offset
+rows it owns as blocks (start, rows, row length, pitch) in ELEMENTS of the allocation (whose element `base`, 0 unless the tensor is a
+view into a wider buffer, is the one the call's pointer names), so that the smallest and largest element and byte offset from that base
+follow in exact integers. A case names the thresholds it claims to cross (byte offset 2^31 / 2^32 / 2^33, element offset
 2^30 / 2^31 / 2^32); tests/test_far_cases.py holds every claim to the integers, on the CPU.
 
 The checker (footprint) walks an integer view of an output buffer in chunks: every element outside the owned rows must still hold the
@@ -19,16 +21,18 @@ GIB = 1 << 30
 # ---- the planner -------------------------------------------------------------------------------------------------------------------------
 class Tensor:
     """One tensor of a call: `numel` elements of `itemsize` bytes are allocated; the call touches `blocks`, each (start, rows, row_len,
-    pitch): `rows` rows of `row_len` contiguous elements, row i at element start + i * pitch from the base. role: "load" or "store"."""
+    pitch): `rows` rows of `row_len` contiguous elements, row i at element start + i * pitch of the allocation. role: "load" or "store".
+    base: the element of the allocation the call's pointer names (a half-view of a wider buffer: 128); lo / hi and every crossing are
+    offsets from it, as the kernel forms them."""
 
-    def __init__(self, name, kind, numel, role, blocks):
-        self.name, self.kind, self.itemsize, self.numel, self.role = name, kind, ITEMSIZE[kind], int(numel), role
+    def __init__(self, name, kind, numel, role, blocks, base=0):
+        self.name, self.kind, self.itemsize, self.numel, self.role, self.base = name, kind, ITEMSIZE[kind], int(numel), role, int(base)
         self.blocks = [tuple(int(x) for x in b) for b in blocks]
         assert self.blocks and all(n >= 1 and ln >= 1 and (n == 1 or p >= ln) for _, n, ln, p in self.blocks), name
-        self.lo_elem = min(s for s, _, _, _ in self.blocks)
-        self.hi_elem = max(s + (n - 1) * p + ln - 1 for s, n, ln, p in self.blocks)
+        self.lo_elem = min(s for s, _, _, _ in self.blocks) - self.base
+        self.hi_elem = max(s + (n - 1) * p + ln - 1 for s, n, ln, p in self.blocks) - self.base
         self.lo_byte, self.hi_byte = self.lo_elem * self.itemsize, self.hi_elem * self.itemsize + self.itemsize - 1
-        assert 0 <= self.lo_elem and self.hi_elem < self.numel, (name, "touched outside its allocation", self.hi_elem, self.numel)
+        assert 0 <= self.lo_elem and self.base + self.hi_elem < self.numel, (name, "touched outside its allocation", self.hi_elem, self.numel)
 
     def crosses(self, unit, threshold):
         return (self.hi_byte if unit == "byte" else self.hi_elem) >= threshold
@@ -41,6 +45,7 @@ class Tensor:
         per = self.itemsize if unit == "byte" else 1
         count = 0
         for s, n, _, p in self.blocks:
+            s -= self.base
             if n == 1 or p == 0:
                 count += n if s * per >= threshold else 0
                 continue
@@ -262,6 +267,231 @@ def cases():
     out += [ksplit("G-ksplit-workspace")]
     out += [dense(f"H-dense-forward-{k}", k, "both") for k in ("f32", "f16", "bf16", "fp8")]
     out += [dense("H-dense-backward-q-bf16", "bf16", "q", backward=True), dense("H-dense-backward-kv-bf16", "bf16", "kv", backward=True)]
+    return {p.name: p for p in out}
+
+
+# ---- the MLA family: fa_fwd_mla_decode_paged / _wide / _kv8, fa_fwd_varlen_mla, fa_bwd_varlen_mla ------------------------------------------
+MLA_DQK, MLA_DV = 576, 512    # the decode: a latent row, and the part of it that is the value
+MLA_PQK, MLA_PV = 192, 128    # the prefill and its backward: q / k rows, v / o rows
+MLA_ROW = {"q": MLA_PQK, "k": MLA_PQK, "v": MLA_PV, "o": MLA_PV, "d_o": MLA_PV, "dq": MLA_PQK, "dk": MLA_PQK, "dv": MLA_PV}
+MLA_IST = 16 * (MLA_DV + 2)   # floats of one 16-row slot of the decode workspace: [16][512] O, then [16][2] (m, l)
+
+
+def latent_pool_rules(P, ps, rs, itemsize, max_pages):
+    """The one-head pool [num_pages, P, 576]: no head stride, so the row stride stands in for it (fa_fwd_decode_paged's rules)."""
+    return pool_rules(P, MLA_DQK, ps, rs, rs, itemsize, max_pages)
+
+
+def decode_stride_rules(what, B, D, bs, hs, rs):
+    return [(f"{what}: three strides, multiples of 8, at least D (batch: >= 0 when B = 1)",
+             rs >= D and hs >= D and bs >= 0 and (B == 1 or bs >= D) and bs % 8 == 0 and hs % 8 == 0 and rs % 8 == 0)]
+
+
+def decode_grid_rule(B, Hq, Nq):
+    rblk = (Hq * Nq + 15) // 16
+    return [("B * Hq * Nq and B * 256 * rblk fit an int", 0 < B * Hq * Nq < (1 << 31) and B * 256 * rblk < (1 << 31))]
+
+
+def prefill_rules(strides, max_q, max_k, total_q, total_k, B, Hq):
+    """fa_fwd_varlen_mla / fa_bwd_varlen_mla: a stride pair and the 4 GiB sequence rule PER TENSOR. strides: name -> (row, head)."""
+    out = []
+    for n in ("q", "k", "v", "o"):
+        rs, hs = strides[n]
+        out += stride_rules(n, rs, hs, MLA_ROW[n]) + sequence_rule(n, max_q if n in "qo" else max_k, rs)
+    return out + [("max_seqlen <= total", max_q <= total_q and max_k <= total_k), ("totals fit an int", max(total_q, total_k) < (1 << 31))] + \
+        grid_rule(B * Hq * ((max_q + 127) // 128))
+
+
+def mla_packed(name, side, layout="THD", dtype="bf16", Hq=16, Hkv=8, backward=False):
+    """Cases M-A and M-B: packed sequences with one side far, as packed(): sequence 0 at token 0, clamped to max_seqlen = 300 rows,
+    sequence 1 the last tokens. The forward's token count is set by the NARROWEST row pitch of the far side, 512 tokens past 4 GiB in 16
+    bits, so that every tensor of the side crosses byte 2^32 and element 2^31: o's (Hq * 128) on the q side; on the kv side v is the
+    upper half of a [total_k, Hkv, 256] buffer (head stride 256, base 128), whose rows are wider than k's, so k's (Hkv * 192).
+    The backward's q side is the forward's, with d_o beside o and dq an fp32 store past byte 2^33 (26 GiB). The backward's kv side: v
+    is a plain [total_k, Hkv, 128] and k sets the total: k and dk cross 2^32 / 2^33 bytes, v crosses 2^31 and dv 2^32 (20 GiB).
+    NOT COVERED: dv past byte 2^33. That needs 2^33 / (8 * 128 * 4) = 2 Mi tokens, at which dk alone is 12 GiB and the case 30 GiB
+    before its compact twin and the checker's temporaries: it does not fit under the 32 GiB peak limit, and the limit stays."""
+    half_v = side == "kv" and not backward
+    H = Hq if side == "q" else Hkv
+    width = dict(q=MLA_PQK, o=MLA_PV, k=MLA_PQK, v=2 * MLA_PV if half_v else MLA_PV)
+    mine = ("q", "o") if side == "q" else ("k", "v")
+    total = (1 << 32) // (H * min(width[n] for n in mine if not (backward and n == "v")) * 2) + 512
+    last = L_LAST if side == "q" else L_SEQ
+    owned = [(0, L_SEQ), (total - last, last)]
+    other = [L_SEQ, L_SEQ] if side == "q" else [L_SEQ, L_LAST]
+    strides, base = {}, {}
+    for n in mine:
+        strides[n] = (H * width[n], width[n]) if layout == "THD" else (width[n], total * width[n])
+        base[n] = MLA_PV if (n == "v" and half_v) else 0
+    tensors, claims = [], []
+
+    def add(n, like, kind, role, past):
+        rs, hs = strides[like]
+        blocks = [(s + base[like], r, ln, p) for s, r, ln, p in seq_blocks(owned, H, MLA_ROW[n], rs, hs)]
+        tensors.append(Tensor(n, kind, total * H * width[like], role, blocks, base=base[like]))
+        claims.extend((n, u, t) for u, t in past)
+    both = (("byte", 1 << 32), ("elem", 1 << 31))
+    if side == "q":
+        add("q", "q", dtype, "load", both)
+        add("o", "o", dtype, "load" if backward else "store", both)
+        if backward:
+            add("d_o", "o", dtype, "load", both)
+            add("dq", "q", "f32", "store", (("byte", 1 << 33),))
+    else:
+        add("k", "k", dtype, "load", both)
+        add("v", "v", dtype, "load", (("byte", 1 << 31),) if backward else both)
+        if backward:
+            add("dk", "k", "f32", "store", (("byte", 1 << 33),))
+            add("dv", "v", "f32", "store", (("byte", 1 << 32),))
+    near = {n: ((Hq if n in "qo" else Hkv) * MLA_ROW[n], MLA_ROW[n]) for n in ("q", "k", "v", "o")}
+    tq, tk = (total, sum(other)) if side == "q" else (sum(other), total)
+    rules = prefill_rules({**near, **strides}, L_SEQ, L_SEQ, tq, tk, 2, Hq)
+    sc = dict(side=side, layout=layout, dtype=dtype, Hq=Hq, Hkv=Hkv, total=total, strides=strides, base=base, owned=owned, half_v=half_v,
+              cu_far=[0, total - last, total], cu_near=[0, other[0], other[0] + other[1]], max_far=L_SEQ, max_near=L_SEQ,
+              lens_far=[L_SEQ, last], lens_near=other)
+    return Plan(name, sc, tensors, claims, rules)
+
+
+# four different row strides near 2^22, one per tensor: a load or a store made under a neighbour's stride lands between the rows
+MLA_WIDE_STRIDES = {"q": (1 << 22) + 3 * 256, "k": (1 << 22) + 5 * 256, "v": (1 << 22) + 2 * 256, "o": (1 << 22) + 7 * 256}
+
+
+def mla_wide(name, side, dtype="bf16", Hq=4, Hkv=2, backward=False):
+    """Case M-C: one sequence of 300 rows, heads adjacent inside a row, FOUR different row strides near 2^22 elements: in-sequence offsets
+    of 2 - 4 GiB in 16 bits, up to 5 GiB in fp32. v is the upper half of a buffer whose heads are 256 wide (head stride 256, base 128).
+    side "both" (the forward), "q" or "kv" (the backward with that side wide)."""
+    L = L_SEQ
+    strides = {n: (MLA_WIDE_STRIDES[n], 2 * MLA_PV if n == "v" else MLA_ROW[n]) for n in ("q", "k", "v", "o")}
+    base = {"q": 0, "k": 0, "v": MLA_PV, "o": 0}
+    tensors, claims = [], []
+
+    def add(n, like, kind, role, past):
+        rs, hs = strides[like]
+        H = Hq if like in "qo" else Hkv
+        blocks = [(s + base[like], r, ln, p) for s, r, ln, p in seq_blocks([(0, L)], H, MLA_ROW[n], rs, hs)]
+        tensors.append(Tensor(n, kind, L * rs, role, blocks, base=base[like]))
+        claims.extend((n, "byte", t) for t in past)
+    if side in ("q", "both"):
+        add("q", "q", dtype, "load", (1 << 31,))
+        add("o", "o", dtype, "load" if backward else "store", (1 << 31,))
+        if backward:
+            add("d_o", "o", dtype, "load", (1 << 31,))
+            add("dq", "q", "f32", "store", (1 << 31, 1 << 32))
+    if side in ("kv", "both"):
+        add("k", "k", dtype, "load", (1 << 31,))
+        add("v", "v", dtype, "load", (1 << 31,))
+        if backward:
+            add("dk", "k", "f32", "store", (1 << 31, 1 << 32))
+            add("dv", "v", "f32", "store", (1 << 31, 1 << 32))
+    near = {n: ((Hq if n in "qo" else Hkv) * MLA_ROW[n], MLA_ROW[n]) for n in ("q", "k", "v", "o")}
+    far_names = {"both": "qkvo", "q": "qo", "kv": "kv"}[side]
+    used = {n: (strides[n] if n in far_names else near[n]) for n in near}
+    rules = prefill_rules(used, L, L, L, L, 1, Hq) + [("four different row strides", len({s[0] for s in strides.values()}) == 4)]
+    sc = dict(side=side, dtype=dtype, Hq=Hq, Hkv=Hkv, L=L, strides=strides, base=base, total=L)
+    return Plan(name, sc, tensors, claims, rules)
+
+
+MLA_POOL_LENS = [700, 300]         # keys per sequence of every pool case (POOL_LENS' key counts)
+MLA_POOL_NEW = [130, 40]           # ... of which the append cases write the last ones (POOL_LENS' new rows)
+# (Hq, Nq, causal, wide) of the decode calls on the far pools: 16 rows and 32 rows on one-wave items, 32 rows again through the wide call
+# (NW = 2), 33 and 128 rows (NW = 4); causal with Nq = 2 in every call. The e4m3 pool takes the rows of the kv8 call.
+MLA_POOL_CALLS = {"bf16": [(8, 2, True, False), (16, 2, True, False), (16, 2, True, True), (33, 1, False, True), (64, 2, True, True)],
+                  "fp8": [(8, 2, True, None), (33, 1, False, None), (64, 2, True, None)]}
+
+
+def mla_pool(name, kind, gib_halves, rs=MLA_DQK, pad_page=False, P=256, store=False):
+    """Cases M-D and M-F: ONE latent pool [num_pages, P, 576] of gib_halves / 2 GiB whose used pages start three pages past ELEMENT
+    offset 2^32, as pool(). rs: the row stride (640: padded rows); pad_page: a page stride of one row more than P. store: the case
+    appends the last MLA_POOL_NEW keys of every sequence."""
+    isz = ITEMSIZE[kind]
+    ps = (P + (1 if pad_page else 0)) * rs
+    num_pages = (gib_halves << 29) // (ps * isz)
+    first = (1 << 32) // ps + 3
+    pages, tables, blocks, new_blocks = first, [], [], []
+    for n_new, L in zip(MLA_POOL_NEW, MLA_POOL_LENS):
+        mine = list(range(pages, pages + (L + P - 1) // P))
+        pages += len(mine)
+        tables.append(mine)
+        for j, pg in enumerate(mine):
+            n = min(P, L - j * P)
+            blocks.append((pg * ps, n, MLA_DQK, rs))
+            lo = max(L - n_new - j * P, 0)
+            if lo < n:
+                new_blocks.append((pg * ps + lo * rs, n - lo, MLA_DQK, rs))
+    max_pages = max(len(t) for t in tables)
+    tensors = [Tensor("kv_pages", kind, num_pages * ps, "store" if store else "load", new_blocks if store else blocks)]
+    claims = [("kv_pages", u, 1 << 32) for u in ("byte", "elem")]
+    rules = latent_pool_rules(P, ps, rs, isz, max_pages) + [("the pages lie inside the pool", pages + 1 <= num_pages)]
+    for Hq, Nq, _, _ in MLA_POOL_CALLS[kind]:
+        rules += decode_grid_rule(len(MLA_POOL_LENS), Hq, Nq)
+    sc = dict(kind=kind, P=P, num_pages=num_pages, first_page=first, used_pages=pages - first, tables=tables, max_pages=max_pages,
+              page_stride=ps, row_stride=rs, pad_page=pad_page, lens=MLA_POOL_LENS, new=MLA_POOL_NEW, calls=MLA_POOL_CALLS[kind])
+    return Plan(name, sc, tensors, claims, rules)
+
+
+def mla_batch(name, call, token_major, Hq, Nq):
+    """Case M-H: q and o of a decode call with batch entry 1 lying 2^32 bytes plus 1 MiB behind entry 0, for q and independently for o.
+    Head-major [B, Hq, Nq, D] with rows back to back, or token-major [B, Nq, Hq, D] where o's rows are 576 apart (the first 512 columns
+    of a [B, Nq, Hq, 576] buffer): rows of 512 are written, never 576. The pool is small and compact."""
+    B, R = 2, Hq * Nq
+    bs = ((1 << 32) + (1 << 20)) // 2
+    o_row = MLA_DQK if token_major else MLA_DV
+    q_st = (bs, MLA_DQK, Hq * MLA_DQK) if token_major else (bs, Nq * MLA_DQK, MLA_DQK)
+    o_st = (bs, o_row, Hq * o_row) if token_major else (bs, Nq * o_row, o_row)
+    tensors = [Tensor("q", "bf16", bs + R * MLA_DQK, "load", [(b * bs, R, MLA_DQK, MLA_DQK) for b in range(B)]),
+               Tensor("o", "bf16", bs + R * o_row, "store", [(b * bs, R, MLA_DV, o_row) for b in range(B)])]
+    rules = (decode_stride_rules("q", B, MLA_DQK, *q_st) + decode_stride_rules("o", B, MLA_DV, *o_st) + decode_grid_rule(B, Hq, Nq)
+             + [("the row count fits the call", R <= (32 if call == "one" else 128))])
+    sc = dict(call=call, token_major=token_major, B=B, Hq=Hq, Nq=Nq, q_strides=q_st, o_strides=o_st, batch_stride=bs, o_row=o_row,
+              lens=MLA_POOL_LENS, P=64)
+    return Plan(name, sc, tensors, [("q", "byte", 1 << 32), ("o", "byte", 1 << 32)], rules)
+
+
+def mla_workspace(name, B=32768, Hq=64, Nq=2, P=256, o_row=520):
+    """Case M-G: the wide decode's workspace, B * S * rows16 * 514 floats, above 2^31 floats: 128 packed rows and B = 32768, where the
+    split rule gives S = 1 (the test takes S from the library's size function and asserts it). All but three sequences are empty; the
+    live ones lie at batch indices whose workspace slots start past element 2^31 and whose q and o rows start past byte 2^32 (o's rows
+    are 520 elements apart: back to back, entry 32767 would end exactly at byte 2^32). The grid rule B * 256 * rblk < 2^31 and the peak
+    limit both admit this shape: neither rows16 nor B was shrunk."""
+    R = Hq * Nq
+    rows16 = 16 * ((R + 15) // 16)
+    S = 1
+    live = {0: 300, 32700: 700, 32767: 257}  # batch index -> keys
+    ws = B * S * rows16 * (MLA_DV + 2)
+    q_st, o_st = (R * MLA_DQK, Nq * MLA_DQK, MLA_DQK), (R * o_row, Nq * o_row, o_row)
+    tensors = [Tensor("workspace", "f32", ws, "store", [(0, B * S * rows16 // 16, MLA_IST, MLA_IST)]),
+               Tensor("q", "bf16", B * R * MLA_DQK, "load", [(b * q_st[0], R, MLA_DQK, MLA_DQK) for b in live]),
+               Tensor("o", "bf16", B * R * o_row, "store", [(0, B * R, MLA_DV, o_row)])]
+    far_live = [b for b in live if b]
+    rules = (decode_stride_rules("q", B, MLA_DQK, *q_st) + decode_stride_rules("o", B, MLA_DV, *o_st) + decode_grid_rule(B, Hq, Nq)
+             + latent_pool_rules(P, P * MLA_DQK, MLA_DQK, 2, 3)
+             + [("the far live sequences' slots start past element 2^31", all(b * S * rows16 * (MLA_DV + 2) >= (1 << 31) for b in far_live)),
+                ("... and their q and o rows past byte 2^32", all(b * q_st[0] * 2 >= (1 << 32) and b * o_st[0] * 2 >= (1 << 32) for b in far_live))])
+    sc = dict(B=B, Hq=Hq, Nq=Nq, P=P, S=S, rows16=rows16, live=live, q_strides=q_st, o_strides=o_st, o_row=o_row, workspace_bytes=4 * ws,
+              max_pages=3)
+    claims = [("workspace", "elem", 1 << 31), ("workspace", "byte", 1 << 33), ("q", "byte", 1 << 32), ("o", "byte", 1 << 32)]
+    return Plan(name, sc, tensors, claims, rules)
+
+
+def mla_cases():
+    """Every case of tests/test_gpu_far_addresses_mla.py by name."""
+    out = [
+        mla_packed("M-A-prefill-q-far", "q"),
+        mla_packed("M-A-prefill-kv-far", "kv"),
+        mla_packed("M-A-prefill-q-far-head-major-f16", "q", layout="HTD", dtype="f16"),
+        mla_packed("M-A-prefill-kv-far-head-major-f16", "kv", layout="HTD", dtype="f16"),
+        mla_packed("M-B-backward-q-far", "q", backward=True),
+        mla_packed("M-B-backward-kv-far", "kv", backward=True),
+    ]
+    for dtype in ("bf16", "f16"):
+        out += [mla_wide(f"M-C-wide-forward-{dtype}", "both", dtype), mla_wide(f"M-C-wide-backward-q-{dtype}", "q", dtype, backward=True),
+                mla_wide(f"M-C-wide-backward-kv-{dtype}", "kv", dtype, backward=True)]
+    out += [mla_pool("M-D-bf16-pool", "bf16", 17), mla_pool("M-D-bf16-pool-padded", "bf16", 17, rs=640, pad_page=True),
+            mla_pool("M-D-e4m3-pool", "fp8", 9)]
+    out += [mla_pool("M-F-append-bf16-pool", "bf16", 17, store=True), mla_pool("M-F-append-e4m3-pool", "fp8", 9, store=True)]
+    out += [mla_workspace("M-G-wide-workspace")]
+    for call, Hq, Nq in (("one", 16, 2), ("wide", 64, 2), ("kv8", 33, 2)):
+        out += [mla_batch(f"M-H-decode-{call}-{'token' if tm else 'head'}-major", call, tm, Hq, Nq) for tm in (False, True)]
     return {p.name: p for p in out}
 
 

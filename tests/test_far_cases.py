@@ -1,6 +1,7 @@
 """CPU: the far-address cases are what they claim to be (tests/far.py), and the footprint checker sees what it must.
 
-  * every case of the catalogue crosses the thresholds it names: asserted from the planner's integers, re-derived here row by row;
+  * every case of both catalogues (cases(), and mla_cases() of the MLA family: tests/test_far_cases_mla.py holds what is particular to
+    it) crosses the thresholds it names: asserted from the planner's integers, re-derived here row by row;
   * every planned call satisfies the host rules of include/fa_mi355.h, and the restated rules refuse what the library refuses;
   * the checker on small CPU tensors under a wrap modulus of 2^16: a clean footprint passes; a row stored at its offset modulo the
     modulus, a row stored at the offset of a sign-extended 16-bit product, one stray element between two rows under a wide stride and
@@ -11,19 +12,21 @@ import pytest
 import far
 
 CASES = far.cases()
+MLA = far.mla_cases()
+ALL = {**CASES, **MLA}
 SENTINEL = 0x7FA5
 
 
 # ---- the planner ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.parametrize("name", list(ALL))
 def test_case_crosses_what_it_claims(name):
-    plan = CASES[name]
+    plan = ALL[name]
     assert plan.claims, name
     for tname, unit, threshold in plan.claims:
         t = plan.tensors[tname]
         per = t.itemsize if unit == "byte" else 1
         # the last element of the last row of every block, from the block's own integers
-        last = max((s + (n - 1) * p + ln - 1) for s, n, ln, p in t.blocks)
+        last = max((s + (n - 1) * p + ln - 1) for s, n, ln, p in t.blocks) - t.base  # (offsets count from the element the pointer names)
         assert last == t.hi_elem and (last * per + per - 1 if unit == "byte" else last) >= threshold, (name, tname, unit, threshold, last)
         # ... and not by a row's tail alone: whole rows START at or past the threshold
         assert t.rows_at_or_past(unit, threshold) >= 1, (name, tname, unit, threshold)
@@ -31,12 +34,12 @@ def test_case_crosses_what_it_claims(name):
         assert t.numel * t.itemsize > threshold * (1 if unit == "byte" else t.itemsize) - t.itemsize, (name, tname, "the allocation is that large")
 
 
-@pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.parametrize("name", list(ALL))
 def test_case_is_legal_and_fits(name):
-    plan = CASES[name]
+    plan = ALL[name]
     assert plan.rules and plan.legal(), (name, [text for text, ok in plan.rules if not ok])
     for t in plan.tensors.values():  # rows disjoint inside a block, every row inside the allocation
-        assert all(p >= ln or n == 1 for _, n, ln, p in t.blocks) and 0 <= t.lo_elem <= t.hi_elem < t.numel, (name, t.name)
+        assert all(p >= ln or n == 1 for _, n, ln, p in t.blocks) and 0 <= t.lo_elem <= t.hi_elem < t.numel - t.base, (name, t.name)
     assert plan.device_bytes() < 30 * far.GIB, (name, plan.device_bytes() / far.GIB)  # under 32 GiB with the compact twins
 
 
