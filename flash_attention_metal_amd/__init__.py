@@ -23,6 +23,7 @@ from .ops import (  # noqa: F401
     flash_attention_decode_paged,
     flash_attention_forward,
     flash_attention_mla_decode_paged,
+    flash_attention_mla_decode_sparse,
     flash_attention_varlen,
     flash_attention_varlen_backward,
     flash_attention_varlen_mla,
@@ -36,6 +37,8 @@ from .ops import (  # noqa: F401
     mla_decode_paged_wide_supported,
     mla_decode_paged_wide_workspace_bytes,
     mla_decode_paged_workspace_bytes,
+    mla_decode_sparse_supported,
+    mla_decode_sparse_workspace_bytes,
     supported,
     varlen_backward_supported,
     varlen_backward_workspace_bytes,

@@ -835,6 +835,63 @@ int fa_fwd_mla_decode_paged_kv8(const void *q, const void *kv_pages, void *o, fl
                                workspace, workspace_bytes, hip_stream);
 }
 
+// ---- fa_fwd_mla_decode_sparse: the wide call's rules on q, o, the pool and the workspace (the shared helpers, in its order, with its
+// statuses and texts; a token is its (b, i) with Nq = 1, so the row stride it checks is the row itself), and in place of the block table
+// and the lengths the rules of the index lists. The split count is the wide call's at B = T, Nq = 1 and a capacity of
+// cap = 64 ceil(topk / 64) keys: the call's bits are that call's on the gathered pool.
+static long long mla_sparse_cap(int topk) { return ((long long)topk + 63) / 64 * 64; }
+int fa_fwd_mla_decode_sparse_supported(int dtype, int Dqk, int Dv, int Hq, int page_size) {
+  return mla_decode_shape_ok(dtype, Dqk, Dv, Hq, 1, page_size, 128);
+}
+long long fa_fwd_mla_decode_sparse_workspace_bytes(int T, int Hq, int Dv, int topk) {
+  if (topk < 1 || mla_sparse_cap(topk) > (1 << 30)) return 0;
+  return fa_fwd_mla_decode_paged_wide_workspace_bytes(T, Hq, 1, Dv, 64, (int)(mla_sparse_cap(topk) / 64));
+}
+int fa_fwd_mla_decode_sparse(const void *q, const void *kv_pages, void *o, float *lse, const int *indices, const int *index_counts, int T,
+                             int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages, float scale, long long q_token_stride,
+                             long long q_head_stride, long long o_token_stride, long long o_head_stride, long long kv_page_stride,
+                             long long kv_row_stride, long long indices_stride, int dtype, void *workspace, long long workspace_bytes,
+                             void *hip_stream) {
+  const char *fn = "fa_fwd_mla_decode_sparse";
+  g_err[0] = 0;
+  TRY(nonnull(fn, {q, kv_pages, o, indices, workspace}));
+  TRY(positive(fn, {T, Hq, Dqk, Dv, topk, page_size, num_pages}));
+  TRY(scale_ok(fn, scale));
+  if (!mla_decode_shape_ok(dtype, Dqk, Dv, Hq, 1, page_size, 128))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 (q and the pool alike), (Dqk, Dv) = (576, 512), Hq <= 128 heads and a page size of "
+                "16, 32, 64, 128 or 256; got dtype=%s Dqk=%d Dv=%d Hq=%d page_size=%d", fn, fa_dtype_name(dtype), Dqk, Dv, Hq, page_size);
+  if (indices_stride < topk || (indices_stride % 4))
+    return fail(FA_ERR_INVALID_ARG, "%s: indices_stride=%lld must be a multiple of 4 and >= topk=%d", fn, indices_stride, topk);
+  TRY(mla_strides_ok(fn, "", T, Dqk, q_token_stride, q_head_stride, Dqk));
+  TRY(mla_strides_ok(fn, "output ", T, Dv, o_token_stride, o_head_stride, Dv));
+  TRY(page_strides_ok(fn, Dqk, page_size, kv_page_stride, kv_row_stride, kv_row_stride, 0, dtype));
+  TRY(aligned16(fn, "tensors and workspace", {q, kv_pages, o, workspace}));
+  TRY(aligned16(fn, "indices", {indices}));
+  if ((uintptr_t)index_counts & 3) return fail(FA_ERR_INVALID_ARG, "%s: index_counts must be int32-aligned", fn);
+  if (mla_sparse_cap(topk) > (1 << 30)) return fail(FA_ERR_INVALID_ARG, "%s: capacity above 2^30 keys", fn);
+  if ((long long)num_pages * page_size > (1 << 30))
+    return fail(FA_ERR_INVALID_ARG, "%s: num_pages * page_size = %lld slots, above 2^30", fn, (long long)num_pages * page_size);
+  const int cap = (int)mla_sparse_cap(topk);
+  TRY(workspace_fits(fn, workspace_bytes, fa::mla_decode_sparse_workspace_bytes(T, Hq, cap), "fa_fwd_mla_decode_sparse_workspace_bytes"));
+  const int rblk = (Hq + 15) / 16;
+  if ((long long)T * Hq > 0x7fffffffLL || (long long)T * 256 * rblk > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  const int nw = fa::mla_wide_waves(Hq);
+  fa::MlaSparseParams p;
+  p.q = q; p.kv = kv_pages; p.ws = (float *)workspace;
+  p.indices = indices; p.counts = index_counts;
+  p.T = T; p.Hq = Hq; p.Nq = 1; p.RBLK = rblk; p.scale = scale;
+  p.S = fa::mla_decode_splits(T, (rblk + nw - 1) / nw, cap);  // the wide call's own rule at (T, 1, cap)
+  p.q_bs = q_token_stride; p.q_hs = q_head_stride; p.q_rs = Dqk;
+  p.page_stride = kv_page_stride; p.row_stride = kv_row_stride; p.idx_stride = indices_stride;
+  p.topk = topk; p.num_slots = num_pages * page_size;
+  p.lp = log2_of(page_size);
+  fa::MlaDecodeParams pc = {};  // what the combine kernel reads: the workspace's shape and the output
+  pc.o = o; pc.lse = lse; pc.ws = p.ws;
+  pc.B = T; pc.Hq = Hq; pc.Nq = 1; pc.S = p.S; pc.RBLK = rblk;
+  pc.o_bs = o_token_stride; pc.o_hs = o_head_stride; pc.o_rs = Dv;
+  return launched(fn, fa::launch_mla_decode_sparse(p, pc, dtype, (hipStream_t)hip_stream));
+}
+
 int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size) { return fa::mfma_varlen_paged_supported(dtype, D, page_size); }
 // the key split's scalars: sizes >= 1, a head_dim and a page size the paged prefill has, a capacity of at most 2^30 keys
 static bool ksplit_scalars_ok(int B, int Hq, int max_seqlen_q, int D, int page_size, int max_pages_per_seq) {

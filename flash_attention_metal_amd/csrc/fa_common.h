@@ -220,6 +220,22 @@ struct MlaDecodeParams {
   int is_causal;
 };
 
+// one fa_fwd_mla_decode_sparse call (csrc/fa_mla_sparse_kernel.hip): the partial kernel's view. A token is what the dense calls name
+// (b, i): fa_mla_body.h reads q, q_bs (the token stride), q_hs, q_rs, Nq (= 1), Hq, scale, ws and RBLK under these names. Keys are SLOTS
+// x = page * P + row of the pool, named by indices[t][0 .. n_t - 1]. The combine kernel gets a MlaDecodeParams with B = T, Nq = 1.
+struct MlaSparseParams {
+  const void *q, *kv;
+  float *ws;  // workspace: the dense calls' format, per (token, split, row block)
+  const int *indices, *counts;  // [T, idx_stride]; [T] or null (every list holds topk entries)
+  int T, Hq, Nq;
+  int S;     // key splits per token
+  int RBLK;  // 16-row blocks: ceil(Hq / 16)
+  float scale;
+  long long q_bs, q_hs, q_rs, page_stride, row_stride, idx_stride;  // elements
+  int topk, num_slots;  // entries per list; num_pages * P
+  int lp;               // log2 of the page size (16 .. 256)
+};
+
 // dtype tags
 struct F32 {};
 struct F16 {};
@@ -305,6 +321,11 @@ long long mla_decode_wide_workspace_bytes(int B, int Hq, int Nq, int Nk);
 // registers and widened into the wide call's image; the wide call's split count, workspace and combine kernel
 hipError_t launch_mla_decode_paged_kv8(const MlaDecodeParams &p, hipStream_t s);
 long long mla_decode_kv8_workspace_bytes(int B, int Hq, int Nq, int Nk);
+// fa_fwd_mla_decode_sparse (csrc/fa_mla_sparse_kernel.hip): the wide call's workgroup over tiles gathered from a per-token list of slots,
+// always four waves; the wide call's split count and workspace at B = T, Nq = 1 and the capacity cap = 64 ceil(topk / 64), its combine
+// kernel on pc
+hipError_t launch_mla_decode_sparse(const MlaSparseParams &p, const MlaDecodeParams &pc, int dtype, hipStream_t s);
+long long mla_decode_sparse_workspace_bytes(int T, int Hq, int cap);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);

@@ -450,6 +450,76 @@ def flash_attention_mla_decode_paged(
     return out, lse
 
 
+def mla_decode_sparse_supported(dtype: str, d_qk: int, d_v: int, Hq: int, page_size: int) -> bool:
+    return bool(load_library().fa_fwd_mla_decode_sparse_supported(DTYPES[dtype], d_qk, d_v, Hq, page_size))
+
+
+def mla_decode_sparse_workspace_bytes(T: int, Hq: int, d_v: int, topk: int) -> int:
+    return int(load_library().fa_fwd_mla_decode_sparse_workspace_bytes(T, Hq, d_v, topk))
+
+
+def flash_attention_mla_decode_sparse(
+    q: torch.Tensor,
+    kv_pages: torch.Tensor,
+    indices: torch.Tensor,
+    scale: float,
+    index_counts: Optional[torch.Tensor] = None,
+    d_v: int = 512,
+    return_lse: bool = True,
+    out: Optional[torch.Tensor] = None,
+    lse: Optional[torch.Tensor] = None,
+    workspace: Optional[torch.Tensor] = None,
+    stream: Optional[int] = None,
+) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The absorbed MLA step over a list of keys per query token (include/fa_mi355.h fa_fwd_mla_decode_sparse): q [T,Hq,576] under any
+    strides with a unit last stride, up to 128 heads; kv_pages ONE pool [num_pages, P, 576] or [num_pages, P, 1, 576], f16 / bf16 like q,
+    P in {16, 32, 64, 128, 256}. indices int32 [T, topk] with a unit last stride (the row stride a multiple of 4, the base 16-byte
+    aligned) names token t's keys by SLOT, page * P + row; index_counts int32 [T] contiguous says how many entries of each row count
+    (None: all topk). Both are device tensors read by the kernels only: nothing here synchronises, the call can be captured in a graph.
+    A slot named twice enters twice; an entry among the counted ones outside the pool is a key of zeros; entries behind the count are
+    never read. `scale` is required (the model's: the head dim of the model is not 576). Returns O [T,Hq,d_v] (allocated contiguous if
+    `out` is None; any strides with a unit last stride otherwise) and LSE [T,Hq] fp32 or None. A token with no key gets O = 0 and
+    LSE = -inf. `workspace`: a uint8 device tensor of at least mla_decode_sparse_workspace_bytes(T, Hq, d_v, topk) bytes (allocated here
+    if None)."""
+    lib = load_library()
+    if scale is None:
+        raise ValueError("flash_attention_mla_decode_sparse needs the model's scale: there is no default (the head dim of the model is not 576)")
+    if q.dim() != 3 or kv_pages.dim() not in (3, 4) or (kv_pages.dim() == 4 and kv_pages.shape[2] != 1):
+        raise ValueError("q [T,Hq,576], kv_pages one [num_pages,P,576] or [num_pages,P,1,576] latent pool")
+    tensors = (q, kv_pages, indices) + (() if index_counts is None else (index_counts,))
+    if not all(t.is_cuda and t.device == q.device for t in tensors):
+        raise ValueError("flash_attention_mla_decode_sparse needs q, the pool, the index lists and their counts on one device: there is no CPU path")
+    T, Hq, Dqk = q.shape
+    num_pages, P, Dk = kv_pages.shape[0], kv_pages.shape[1], kv_pages.shape[-1]
+    ps, rs, es = kv_pages.stride(0), kv_pages.stride(1), kv_pages.stride(-1)
+    if Dk != Dqk or es != 1 or q.stride(2) != 1:
+        raise ValueError(f"incompatible q {tuple(q.shape)} and pool {tuple(kv_pages.shape)} (same last dim, unit element strides)")
+    if indices.dtype != torch.int32 or indices.dim() != 2 or indices.shape[0] != T or indices.shape[1] < 1 or indices.stride(1) != 1:
+        raise ValueError("indices must be an int32 [T, topk] tensor with a unit last stride")
+    if index_counts is not None and (index_counts.dtype != torch.int32 or index_counts.shape != (T,) or not index_counts.is_contiguous()):
+        raise ValueError("index_counts must be a contiguous int32 [T] tensor, or None")
+    if q.dtype not in (torch.float16, torch.bfloat16) or kv_pages.dtype != q.dtype:
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {kv_pages.dtype} (f16 or bf16, q and the pool alike)")
+    d_v = int(d_v)
+    topk = indices.shape[1]
+    if out is None:
+        out = torch.empty((T, Hq, d_v), dtype=q.dtype, device=q.device)
+    elif not out.is_cuda or out.device != q.device or out.dtype != q.dtype or out.shape != (T, Hq, d_v) or out.stride(2) != 1:
+        raise ValueError("out must be a [T,Hq,d_v] device tensor of q's dtype with a unit last stride")
+    if lse is None:
+        lse = torch.empty((T, Hq), dtype=torch.float32, device=q.device) if return_lse else None
+    elif not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.shape != (T, Hq):
+        raise ValueError("lse must be contiguous fp32 [T,Hq] on q's device")
+    # (one row: its stride addresses nothing, and torch reports any value for a dimension of size 1)
+    istride = indices.stride(0) if T > 1 else (topk + 3) // 4 * 4
+    ws = _workspace(workspace, mla_decode_sparse_workspace_bytes(T, Hq, d_v, topk), q.device)
+    _call(lib, "fa_fwd_mla_decode_sparse",
+          (q.data_ptr(), kv_pages.data_ptr(), out.data_ptr(), _ptr(lse), indices.data_ptr(), _ptr(index_counts), T, Hq, Dqk, d_v, topk, P,
+           num_pages, float(scale), q.stride(0), q.stride(1), out.stride(0), out.stride(1), ps, rs, istride,
+           _TORCH2FA[q.dtype], ws.data_ptr(), ws.numel()), q.device, stream)
+    return out, lse
+
+
 def varlen_supported(dtype: str, D: int) -> bool:
     return bool(load_library().fa_fwd_varlen_supported(DTYPES[dtype], D))
 

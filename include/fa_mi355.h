@@ -893,6 +893,60 @@ long long fa_fwd_mla_decode_paged_kv8_workspace_bytes(int B, int Hq, int Nq, int
 int fa_fwd_mla_decode_paged_kv8_supported(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int Nq, int page_size);
 
 /*
+ * Multi-head latent attention (decode, sparse): fa_fwd_mla_decode_sparse is the absorbed MLA step over a LIST of keys per query token, as
+ * the models with an indexer in front of attention run it (DeepSeek-V3.2 and its successors: at most topk = 2048 keys per token), in
+ * decode and in prefill alike. The rows named by the list are read in place: no gather into a second pool.
+ * Queries are packed TOKENS: q is [T, Hq, 576] and o is [T, Hq, 512], each under its own (token, head) element strides -- the wide call's
+ * rules for q and o: multiples of 8, at least 576 / 512, bases 16-byte aligned, the token stride free when T = 1. lse is [T, Hq] fp32
+ * contiguous, or NULL. O rows of 512 elements are written, never 576. A token is what the dense calls name (b, i): a decode step with
+ * Nq tokens per sequence passes T = B * Nq, a prefill chunk its packed tokens.
+ * The pool is the family's [num_pages, P, 576] under kv_page_stride / kv_row_stride, with the wide call's rules, statuses and texts: the
+ * pool may exceed 4 GiB, one page stays below 2 GiB. A key is named by its SLOT x = page * P + row, 0 <= x < num_pages * P; its address
+ * is (x >> log2 P) * kv_page_stride + (x & (P - 1)) * kv_row_stride. (Slots, not positions: a serving engine turns the indexer's output
+ * into slots once per step for all layers, and packed prefill tokens then need no block table.)
+ * indices is int32 DEVICE memory, [T, indices_stride] with indices_stride >= topk a multiple of 4 and a 16-byte aligned base.
+ * index_counts is int32 [T] DEVICE memory or NULL: n_t = clamp(index_counts[t], 0, topk), and n_t = topk under NULL. The kernels read
+ * both; the host never does, and both grids depend on host scalars alone: one captured graph serves every step.
+ * For token t and head h, with x_j = indices[t][j] for j < n_t: s_j = q[t,h,0:576] . row(x_j)[0:576], P = softmax_j(scale * s_j),
+ * O[t,h,0:512] = sum_j P_j row(x_j)[0:512]; LSE in natural log. The list is a list, not a set: a slot named twice enters twice. There is
+ * no mask and no is_causal: visibility is the list. n_t = 0 gives O = 0 exactly and LSE = -inf. An entry among the first n_t outside
+ * [0, num_pages * P) reads as a row of zeros (a key of score 0 and value 0) and touches nothing outside the pool -- the family's rule for
+ * a page outside the pool. That is a safety rule, not a way to mask: valid entries stand in front and index_counts says how many.
+ * Entries at j >= n_t have no influence, whatever they hold, and are never read; nor are positions j >= topk of a row. Pool rows that
+ * no list names have no influence: NaN there is harmless.
+ * Supported: f16 / bf16 (q and the pool of one type), (Dqk, Dv) = (576, 512), 1 <= Hq <= 128, topk >= 1, T >= 1, P in {16, 32, 64, 128,
+ * 256}; anything else FA_ERR_UNSUPPORTED with a message that names what was given. Every rule shared with
+ * fa_fwd_mla_decode_paged_wide carries that call's status and text after the function name. Rules of this call's own, each
+ * FA_ERR_INVALID_ARG before any launch: null indices; topk < 1; indices_stride < topk or not a multiple of 4; misaligned indices (16
+ * bytes) or index_counts (4); 64 * ceil(topk / 64) or num_pages * P above 2^30; a grid that does not fit an int.
+ * THE CONTRACT: with cap = 64 * ceil(topk / 64), O and LSE are BIT-IDENTICAL to fa_fwd_mla_decode_paged_wide(B = T, Nq = 1,
+ * page_size = 64, max_pages_per_seq = cap / 64, is_causal = 0, seqlens_k = n) on a pool into which every token's listed rows were
+ * copied in list order (row j of token t in slot j % 64 of page block_table[t][j / 64]; out-of-range entries as zero rows). The split
+ * count is that call's own rule there, S = splits(T, ceil(Hq / (16 * NW(Hq))), cap), and fa_fwd_mla_decode_sparse_workspace_bytes equals
+ * fa_fwd_mla_decode_paged_wide_workspace_bytes(T, Hq, 1, 512, 64, cap / 64) on every legal input and is 0 elsewhere. Everything else is
+ * inherited in the wide call's words: the tolerances and "LSE accuracy" on the 576-wide rows; no dependence on the workspace's prior
+ * contents; bitwise reproducible; asynchronous, allocates nothing.
+ * How it runs (csrc/fa_mla_sparse_kernel.hip): the wide call's four-wave workgroup for every head count, over
+ * the item (token, split). Only the staging of a tile is new: each of a tile's 64 latent rows moves by LDS-DMA under a descriptor of its
+ * OWN, built on the row's 64-bit address (num_records = 1152, or 0 for an entry behind n_t or outside the pool); the rotary 128 bytes
+ * of a row go through registers, two predicated 16-byte loads per lane and tile, written into the image behind the tile's arithmetic.
+ * From LDS onwards the source text is the wide call's.
+ * Not here: e4m3 pools and the 656-byte rows with per-tile scales; a mask inside the list; more than 128 heads; sinks; the indexer
+ * itself; a sparse backward. No dense call is rerouted.
+ */
+int fa_fwd_mla_decode_sparse(const void *q, const void *kv_pages, void *o, float *lse,
+                             const int *indices, const int *index_counts,
+                             int T, int Hq, int Dqk, int Dv, int topk,
+                             int page_size, int num_pages, float scale,
+                             long long q_token_stride, long long q_head_stride,
+                             long long o_token_stride, long long o_head_stride,
+                             long long kv_page_stride, long long kv_row_stride, long long indices_stride,
+                             int dtype, void *workspace, long long workspace_bytes, void *hip_stream);
+/* the wide call's size at (T, Hq, 1, 512, 64, ceil(topk / 64)) on every legal input; 0 if a size is invalid or unsupported */
+long long fa_fwd_mla_decode_sparse_workspace_bytes(int T, int Hq, int Dv, int topk);
+int fa_fwd_mla_decode_sparse_supported(int dtype, int Dqk, int Dv, int Hq, int page_size);
+
+/*
  * Multi-head latent attention (prefill): fa_fwd_varlen_mla is the NON-absorbed form of the same layer, as serving engines run its
  * prefill: the latent rows are up-projected to per-head keys and values, and ordinary multi-head attention runs over packed sequences
  * with a query / key head dim of Dqk = 192 (128 "nope" + 64 rotary) and a value head dim of Dv = 128. Per sequence the operator is
