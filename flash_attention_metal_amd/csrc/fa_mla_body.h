@@ -1,16 +1,40 @@
 // fa_mla_body.h -- what ONE WAVE of the absorbed latent-attention decode does with its 16 packed query rows, as TEXT that the partial
-// kernels of fa_mla_kernel.hip (one wave per item, a private double buffer) and fa_mla_wide_kernel.hip (two or four waves over one shared
-// double buffer) include into their bodies, in the manner of fa_bwd_dq_body.inc: the same tokens in both, so a wave of either computes the
-// same bits from the same tile image, and fa_mla_kernel.hip compiles to the instructions it had before the text moved here. (As inlined
-// functions the same statements came out with other registers and two instructions fewer: text it is.)
+// kernels of the family include into their bodies, in the manner of fa_bwd_dq_body.inc: fa_mla_paged_partial.inc (the paged 16-bit pool:
+// fa_mla_kernel.hip's one wave per item over a private double buffer, fa_mla_wide_kernel.hip's two or four waves over one shared double
+// buffer), fa_mla_kv8_kernel.hip and fa_mla_sparse_kernel.hip. The same tokens in all, so a wave of any computes the same bits from the
+// same tile image. (As inlined functions the same statements came out with other registers and two instructions fewer: text it is.)
 // Define FA_MLA_BODY_PART and include; the part undefines it.
-//   0  at namespace scope, behind the shape constants (MLA_DQK .. MLA_IST, mla_swz; each file states them itself): the MFMA types
+//   0  at namespace scope, once per file: the tile's shape and image (MLA_DQK .. MLA_IST, mla_swz), stated here and nowhere else, the MFMA
+//      types, and the launch tail of every call of the family (launch_mla_partial_and_combine)
 //   1  the query fragments and the per-lane LDS read offsets. In scope: M / vec8 / elem, KSL, KSR, p, b, c, g, R, Nk, coff and
 //      rb, the wave's 16-row slot. Declares qf[], rlim, kl[], kr[], vl[]
 //   2  one 64-key tile, t, folded into the wave's (oacc[], m, l). In scope besides: DT, KT, smem, t0. The image and its swizzles are
 //      described at the head of fa_mla_kernel.hip
 //   3  the partial store. In scope: item (b * S + s), rb, oacc[], m, l
 #if FA_MLA_BODY_PART == 0
+// ---- the tile's shape and image. Parts 1 and 2, every file's staging and the combine kernel are written against these; that the latent
+// part's swizzle serves both read patterns without a bank conflict is argued at the head of fa_mla_kernel.hip
+constexpr int MLA_DQK = 576, MLA_DV = 512, MLA_DR = MLA_DQK - MLA_DV;
+constexpr int MLA_LRB = MLA_DV * 2, MLA_RRB = MLA_DR * 2;              // row bytes of the latent / rotary part (of 16-bit elements)
+constexpr int MLA_LAT = BN * MLA_LRB, MLA_ROT = BN * MLA_RRB;          // bytes of a tile's two parts
+constexpr int MLA_IMG = MLA_LAT + MLA_ROT;                             // one tile: 72 KiB
+constexpr size_t mla_lds_bytes() { return 2 * (size_t)MLA_IMG; }       // the double buffer
+constexpr int MLA_IST = 16 * (MLA_DV + 2);                             // floats of one 16-row slot's partial: [16][512] O . l, then [16][2] (m, l)
+__host__ __device__ constexpr int mla_swz(int r) { return (((r & 7) << 1) ^ (9 * ((r >> 3) & 1))) & 15; }  // the latent part's swizzle f
+
+// ---- the launch tail of every call: the partial kernel over `grid` workgroups of nw waves under the double buffer, then fa_mla_kernel.hip's
+// combine kernel over the output rows of pc (the call as that kernel sees it), on the same stream
+template <typename K, typename PT>
+inline hipError_t launch_mla_partial_and_combine(K partial, dim3 grid, int nw, const PT &p, const MlaDecodeParams &pc, int dtype, hipStream_t s) {
+  (void)hipGetLastError();
+  hipError_t e = set_dyn_lds_once((const void *)partial, (int)mla_lds_bytes());
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(partial, grid, dim3(64 * nw), mla_lds_bytes(), s, p);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_mla_combine(pc, dtype, s);
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <typename Tag> struct ML16;

@@ -6,8 +6,8 @@
 //   * the packed row block: r = h * Nq + iq (every query head shares the one latent "key head": G = Hq), 16 rows per item;
 //   * the keys of a sequence SPLIT over S one-wave items (no barrier anywhere), 64-key tiles streamed through a private double buffer
 //     in LDS by LDS-DMA, 16x16x32 MFMA, the exact online softmax, the pre-scaled query operand Q~ = round(scale . log2(e) . Q);
-//   * per-page range-checked descriptors with the whole offset in voffset (rows >= L_b, pages outside the pool: hardware zeros),
-//     table entries fetched one tile ahead and clamped to max_pages - 1;
+//   * per-page range-checked descriptors (rows >= L_b, pages outside the pool: hardware zeros), table entries fetched one tile ahead: the
+//     rules stand at the head of fa_mla_paged_partial.inc, the text of the partial kernel, with the staging they govern;
 //   * partial (O . l, m, l) in the caller's workspace, a second launch that combines the S partials of a row by their maxima.
 // What is new:
 //   * THE IMAGE. A 64-key tile is a latent part [64][512] (rows of 1024 B: one 1-KiB LDS-DMA piece per row) and a rotary part [64][64]
@@ -28,7 +28,8 @@
 //   * ROWS 17..32 are two 16-row items over the same keys (blockIdx.y: the row block). A 32-row item would hold 256 accumulator and
 //     144 query-fragment registers before a single score or address: no room in the 512-entry file without scratch.
 //     (fa_mla_wide_kernel.hip, fa_fwd_mla_decode_paged_wide: two or four such items as the waves of ONE workgroup over a shared tile, up
-//     to 128 rows. What a wave does with its 16 rows is the text of fa_mla_body.h, included below and there.)
+//     to 128 rows. Both partial kernels are one text, fa_mla_paged_partial.inc, at NW = 1, 2 or 4 waves; what a wave does with its 16
+//     rows from LDS onwards is the text of fa_mla_body.h, whose part 0 states the image's constants for every file of the family.)
 #include <stdlib.h>
 
 #include <algorithm>
@@ -45,121 +46,18 @@
 
 namespace fa {
 
-constexpr int MLA_DQK = 576, MLA_DV = 512, MLA_DR = MLA_DQK - MLA_DV;
-constexpr int MLA_LRB = MLA_DV * 2, MLA_RRB = MLA_DR * 2;              // row bytes of the latent / rotary part
-constexpr int MLA_LAT = BN * MLA_LRB, MLA_ROT = BN * MLA_RRB;          // bytes of a tile's two parts
-constexpr int MLA_IMG = MLA_LAT + MLA_ROT;                             // one tile: 72 KiB
-constexpr size_t mla_lds_bytes() { return 2 * (size_t)MLA_IMG; }       // the double buffer
-constexpr int MLA_IST = 16 * (MLA_DV + 2);                             // floats of one item's partial: [16][512] O . l, then [16][2] (m, l)
-
-// the latent part's swizzle (see the head of the file)
-__host__ __device__ constexpr int mla_swz(int r) { return (((r & 7) << 1) ^ (9 * ((r >> 3) & 1))) & 15; }
-
 #define FA_MLA_BODY_PART 0
-#include "fa_mla_body.h"  // the types; parts 1 - 3 are the text of one wave's work, shared with fa_mla_wide_kernel.hip
+#include "fa_mla_body.h"  // the tile's shape and image, the MFMA types, the launch tail
 
-// item (b, s) x row block rb: rows r = 16 rb + c = h * Nq + iq of the packed block, keys of tiles [t0, t1) of sequence b
+// item (b, s) x row block rb: rows r = 16 rb + c = h * Nq + iq of the packed block, keys of tiles [t0, t1) of sequence b. The body is
+// the text fa_mla_wide_kernel.hip's kernel includes, at one wave: no barrier, no padding wave, the whole tile staged by this wave
 template <typename Tag, bool CAUSAL>
 __global__ __launch_bounds__(64) void mla_partial_kernel(MlaDecodeParams p) {
-  using M = ML16<Tag>;
-  using vec8 = typename M::vec8;
-  using elem = typename M::elem;
-  constexpr int KSL = MLA_DV / 32, KSR = MLA_DR / 32;  // k-steps of the score product over the latent / rotary part
-  constexpr int DT = MLA_DV / 16;                      // 16-wide d tiles of O^T
-  constexpr int KT = BN / 16;                          // 16-key tiles per 64-key tile
-
-  extern __shared__ __attribute__((aligned(16))) char smem_generic[];
-  lds_char *smem = (lds_char *)smem_generic;  // buffer u: latent part at u * MLA_IMG, rotary part behind it
-
-  const int lane = threadIdx.x;
-  const int c = lane & 15, g = lane >> 4;
-  const int S = p.S, item = blockIdx.x, rb = blockIdx.y;
-  const int b = item / S, s = item - b * S;
-  const int R = p.Hq * p.Nq;
-  const int Nk = min(max(__builtin_amdgcn_readfirstlane(p.seqlens[b]), 0), p.max_pages << p.lp);  // keys of this item's sequence
-  const int coff = Nk - p.Nq;
-  const int nT = (Nk + BN - 1) / BN;
-  const int t0 = (int)((long long)s * nT / S), t1 = (int)((long long)(s + 1) * nT / S);
-
-#define FA_MLA_BODY_PART 1  // the Q fragments qf[] (pre-scaled), the row limit rlim, the LDS read offsets kl[], kr[], vl[]
-#include "fa_mla_body.h"
-
-  // ---- LDS-DMA: this wave moves every piece of a tile, the chunk swizzle sits on the source address.
-  // latent piece j = row j of the tile: lane -> chunk lane ^ f(j & 15); rotary piece j = rows 8 j .. 8 j + 7: lane -> row lane / 8,
-  // chunk (lane % 8) ^ ((row >> 1) & 7) behind the row's 512 latent elements
-  const unsigned dma_l0 = (unsigned)lane << 4;
-  const int drow = lane >> 3, dpc = lane & 7;
-  const unsigned dma_r0 = (unsigned)(MLA_LRB + ((dpc ^ (drow >> 1)) << 4));
-
-  // ---- pg[] holds the table entries of the next tile to stage (its pages: max(1, 64 / P), at most four), loaded one tile ahead
-  const int lp = p.lp;
-  const unsigned rsb = (unsigned)p.row_stride * 2;  // the pool's row stride in bytes
-  const unsigned dma_rrow = (unsigned)drow * rsb;
-  int pg[4] = {-1, -1, -1, -1};
-  auto fetch_pages = [&](int t) __attribute__((always_inline)) {
-    const int *tbl = p.block_table + (long long)b * p.bt_stride;
-    const int i0 = (t * BN) >> lp, npg = max(1, BN >> lp);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pg[k] = k < npg ? tbl[min(i0 + k, p.max_pages - 1)] : -1;  // (never past the row's max_pages entries)
-  };
-  // stage tile t into buffer buf. LPC = min(lp, 6): the tile's 64 / 2^LPC pages are compile-time entries of pg[], one descriptor each,
-  // built on the page's 64-bit base with a range that covers only the page's valid rows
-  auto stage = [&](auto lpc, int t, int buf) __attribute__((always_inline)) {
-    constexpr int LPC = decltype(lpc)::value, NPG = BN >> LPC, PM = (1 << LPC) - 1;
-    const int P = 1 << lp, key0 = (t * BN) & -P;  // first key of the tile's first page
-    const unsigned row0 = LPC == 6 ? (unsigned)((t * BN) & (P - 1)) : 0u;  // the tile's first slot in it (pages of 64 keys and more)
-    __amdgpu_buffer_rsrc_t rs[NPG];
-#pragma unroll
-    for (int k = 0; k < NPG; ++k) {
-      const int page = __builtin_amdgcn_readfirstlane(pg[k]);
-      const int nv = min(Nk - (key0 + k * P), P);  // valid rows of the page
-      const bool ok = nv > 0 && (unsigned)page < (unsigned)p.num_pages;  // an index outside the pool reads as zeros
-      const long long off = ok ? (long long)page * p.page_stride : 0;
-      const unsigned nrec = ok ? (unsigned)(nv - 1) * rsb + MLA_DQK * 2 : 0u;
-      rs[k] = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.kv + off * 2), 0, nrec, 0x00020000);
-    }
-    const unsigned lbase = (unsigned)(__UINTPTR_TYPE__)smem + buf * MLA_IMG;
-#pragma unroll
-    for (int j = 0; j < BN; ++j) {
-      const unsigned so = (row0 + (unsigned)(j & PM)) * rsb;  // (the whole offset in voffset: inside the range check)
-      const unsigned vo = so + (dma_l0 ^ (unsigned)(mla_swz(j & 15) << 4));
-      const unsigned ld = lbase + j * MLA_LRB;
-      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(ld), "v"(vo), "s"(rs[j >> LPC]) : "memory");
-    }
-#pragma unroll
-    for (int j = 0; j < BN / 8; ++j) {
-      const unsigned so = (row0 + (unsigned)((8 * j) & PM)) * rsb + dma_rrow;
-      const unsigned vo = so + (dma_r0 ^ (unsigned)((j & 1) << 6));  // ((row >> 1) & 7) gains 4 on odd pieces
-      const unsigned ld = lbase + MLA_LAT + j * 1024;
-      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(ld), "v"(vo), "s"(rs[(8 * j) >> LPC]) : "memory");
-    }
-    fetch_pages(t + 1);
-  };
-
-  f32x4 oacc[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) oacc[dt][i] = 0.0f;
-  float m = -INFINITY, l = 0.0f;
-
-  if (t0 < t1) fetch_pages(t0);
-  // iteration t: wait for tile t, stage tile t + 1 under its arithmetic; iteration t0 - 1 only stages tile t0 (one staging site)
-  for (int t = t0 - 1; t < t1; ++t) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile t has landed (this wave issued every piece of it: no barrier needed)
-    if (t + 1 < t1) {
-      const int nb = (t + 1 - t0) & 1;
-      if (lp == 4) stage(std::integral_constant<int, 4>{}, t + 1, nb);
-      else if (lp == 5) stage(std::integral_constant<int, 5>{}, t + 1, nb);
-      else stage(std::integral_constant<int, 6>{}, t + 1, nb);
-    }
-    if (t < t0) continue;
-#define FA_MLA_BODY_PART 2  // tile t: 18 k-steps of scores, the mask, the online softmax, 64 PV steps
-#include "fa_mla_body.h"
-  }
-
-#define FA_MLA_BODY_PART 3  // the partial (O . l, m, l) -> workspace slot (item, rb)
-#include "fa_mla_body.h"
+  constexpr int NW = 1;
+// (this spelling and not the wide file's loop: with the loop these four kernels come out 16 or 17 instructions apart, in the scalar
+// prologue that fetches the first table entries)
+#define FA_MLA_PG_DECL int pg[4] = {-1, -1, -1, -1};
+#include "fa_mla_paged_partial.inc"
 }
 
 // one wave per output row (b, h, iq): fa_decode_kernel.hip's paged combine at 512 columns. Lanes take the splits' (m, l) pairs in
@@ -252,15 +150,7 @@ hipError_t launch_mla_combine(const MlaDecodeParams &p, int dtype, hipStream_t s
 hipError_t launch_mla_decode_paged(const MlaDecodeParams &p, int dtype, hipStream_t s) {
   return with_tag(dtype, [&](auto tag) {
     using Tag = decltype(tag);
-    auto go = [&](auto partial) {
-      (void)hipGetLastError();
-      hipError_t e = set_dyn_lds_once((const void *)partial, (int)mla_lds_bytes());
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(partial, dim3(p.B * p.S, p.RBLK), dim3(64), mla_lds_bytes(), s, p);
-      e = hipGetLastError();
-      if (e != hipSuccess) return e;
-      return launch_mla_combine(p, dtype, s);
-    };
+    auto go = [&](auto partial) { return launch_mla_partial_and_combine(partial, dim3(p.B * p.S, p.RBLK), 1, p, p, dtype, s); };
     return p.is_causal ? go(mla_partial_kernel<Tag, true>) : go(mla_partial_kernel<Tag, false>);
   });
 }

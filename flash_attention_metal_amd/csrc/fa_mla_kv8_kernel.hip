@@ -18,7 +18,7 @@
 //     of tile t - 1 have returned), then the raw s_barrier (everyone's have). Then the raw loads of tile t + 1 go out into registers, the
 //     body's part 2 runs on tile t, and last the registers are widened and written into the other buffer, which nobody reads before the
 //     next barrier. The prologue loads and writes tile t0.
-//   * BARRIER UNIFORMITY: as in fa_mla_wide_kernel.hip. (b, s), Nk and [t0, t1) are the same in all waves of a workgroup; every wave runs
+//   * BARRIER UNIFORMITY: as in fa_mla_paged_partial.inc. (b, s), Nk and [t0, t1) are the same in all waves of a workgroup; every wave runs
 //     every iteration; a wave whose 16 rows are all padding stages its share, meets every barrier, skips the arithmetic, stores nothing.
 #include <stdlib.h>
 
@@ -29,17 +29,8 @@
 
 namespace fa {
 
-// the tile's shape and image: fa_mla_kernel.hip's constants (stated in each file; fa_mla_body.h is written against them)
-constexpr int MLA_DQK = 576, MLA_DV = 512, MLA_DR = MLA_DQK - MLA_DV;
-constexpr int MLA_LRB = MLA_DV * 2, MLA_RRB = MLA_DR * 2;              // row bytes of the latent / rotary part of the (bf16) image
-constexpr int MLA_LAT = BN * MLA_LRB, MLA_ROT = BN * MLA_RRB;          // bytes of a tile's two parts
-constexpr int MLA_IMG = MLA_LAT + MLA_ROT;                             // one tile: 72 KiB
-constexpr size_t mla_lds_bytes() { return 2 * (size_t)MLA_IMG; }       // the double buffer
-constexpr int MLA_IST = 16 * (MLA_DV + 2);                             // floats of one 16-row slot's partial: [16][512] O . l, then [16][2] (m, l)
-__host__ __device__ constexpr int mla_swz(int r) { return (((r & 7) << 1) ^ (9 * ((r >> 3) & 1))) & 15; }
-
 #define FA_MLA_BODY_PART 0
-#include "fa_mla_body.h"
+#include "fa_mla_body.h"  // the tile's shape and image, the MFMA types, the launch tail
 
 constexpr int MLA_KV8_NW = 4;  // waves of a workgroup, for every row count
 
@@ -187,13 +178,7 @@ long long mla_decode_kv8_workspace_bytes(int B, int Hq, int Nq, int Nk) { return
 // over the output rows, on the same stream
 hipError_t launch_mla_decode_paged_kv8(const MlaDecodeParams &p, hipStream_t s) {
   auto go = [&](auto partial) {
-    (void)hipGetLastError();
-    hipError_t e = set_dyn_lds_once((const void *)partial, (int)mla_lds_bytes());
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(partial, dim3(p.B * p.S, (p.RBLK + MLA_KV8_NW - 1) / MLA_KV8_NW), dim3(64 * MLA_KV8_NW), mla_lds_bytes(), s, p);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_mla_combine(p, FA_DTYPE_BF16, s);
+    return launch_mla_partial_and_combine(partial, dim3(p.B * p.S, (p.RBLK + MLA_KV8_NW - 1) / MLA_KV8_NW), MLA_KV8_NW, p, p, FA_DTYPE_BF16, s);
   };
   return p.is_causal ? go(mla_kv8_partial_kernel<true>) : go(mla_kv8_partial_kernel<false>);
 }

@@ -22,7 +22,7 @@
 //   * ONE BARRIER PER TILE, at the top of iteration t: s_waitcnt vmcnt(0) lgkmcnt(0) (this wave's pieces of tile t have landed, its
 //     rotary writes of tile t too, and its reads of tile t - 1 are back), then the raw s_barrier (everyone's have, and everyone has left
 //     iteration t - 1, whose buffer tile t + 1 is about to overwrite). Iteration t0 - 1 only stages tile t0: one staging site.
-//   * BARRIER UNIFORMITY: as in fa_mla_wide_kernel.hip. (token, s) and with them Nk, [t0, t1) come from blockIdx.x and scalars: the same
+//   * BARRIER UNIFORMITY: as in fa_mla_paged_partial.inc. (token, s) and with them Nk, [t0, t1) come from blockIdx.x and scalars: the same
 //     in all waves of a workgroup. Every wave runs every iteration -- once for an empty split -- and nothing leaves the loop early. A wave
 //     whose 16 rows are all padding (slot >= RBLK) stages its share, meets every barrier, skips the arithmetic and stores nothing.
 #include <stdlib.h>
@@ -34,17 +34,8 @@
 
 namespace fa {
 
-// the tile's shape and image: fa_mla_kernel.hip's constants (stated in each file; fa_mla_body.h is written against them)
-constexpr int MLA_DQK = 576, MLA_DV = 512, MLA_DR = MLA_DQK - MLA_DV;
-constexpr int MLA_LRB = MLA_DV * 2, MLA_RRB = MLA_DR * 2;              // row bytes of the latent / rotary part
-constexpr int MLA_LAT = BN * MLA_LRB, MLA_ROT = BN * MLA_RRB;          // bytes of a tile's two parts
-constexpr int MLA_IMG = MLA_LAT + MLA_ROT;                             // one tile: 72 KiB
-constexpr size_t mla_lds_bytes() { return 2 * (size_t)MLA_IMG; }       // the double buffer
-constexpr int MLA_IST = 16 * (MLA_DV + 2);                             // floats of one 16-row slot's partial: [16][512] O . l, then [16][2] (m, l)
-__host__ __device__ constexpr int mla_swz(int r) { return (((r & 7) << 1) ^ (9 * ((r >> 3) & 1))) & 15; }
-
 #define FA_MLA_BODY_PART 0
-#include "fa_mla_body.h"
+#include "fa_mla_body.h"  // the tile's shape and image, the MFMA types, the launch tail
 
 constexpr int MLA_SPARSE_NW = 4;  // waves of a workgroup, for every head count
 
@@ -164,15 +155,8 @@ long long mla_decode_sparse_workspace_bytes(int T, int Hq, int cap) { return mla
 // the output rows (pc: the call as that kernel sees it, B = T, Nq = 1), on the same stream
 hipError_t launch_mla_decode_sparse(const MlaSparseParams &p, const MlaDecodeParams &pc, int dtype, hipStream_t s) {
   return with_tag(dtype, [&](auto tag) {
-    using Tag = decltype(tag);
-    auto partial = mla_sparse_partial_kernel<Tag>;
-    (void)hipGetLastError();
-    hipError_t e = set_dyn_lds_once((const void *)partial, (int)mla_lds_bytes());
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(partial, dim3(p.T * p.S, (p.RBLK + MLA_SPARSE_NW - 1) / MLA_SPARSE_NW), dim3(64 * MLA_SPARSE_NW), mla_lds_bytes(), s, p);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_mla_combine(pc, dtype, s);
+    return launch_mla_partial_and_combine(mla_sparse_partial_kernel<decltype(tag)>, dim3(p.T * p.S, (p.RBLK + MLA_SPARSE_NW - 1) / MLA_SPARSE_NW),
+                                          MLA_SPARSE_NW, p, pc, dtype, s);
   });
 }
 

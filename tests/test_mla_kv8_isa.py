@@ -11,7 +11,7 @@ import pytest
 
 from test_isa_audit import makefile_flags
 from test_ksplit_isa import rows_of
-from test_mla_isa import CSRC
+from test_mla_isa import CSRC, image_is_stated_in_the_body_header_alone, launch_tail_uses_the_double_buffer
 from test_mla_wide_isa import OTHERS, WIDE
 from test_varlen_paged_isa import _compile
 
@@ -40,10 +40,9 @@ def test_no_static_lds_and_the_shared_double_buffer_fits_the_cu(listing):
     sizes = dict(re.findall(r"Function Name: (\S+).*?LDS Size \[bytes/block\]: (\d+)", listing[1], re.S))
     assert len(sizes) == 2 and all(int(v) == 0 for v in sizes.values()), sizes
     src = open(os.path.join(CSRC, "fa_mla_kv8_kernel.hip")).read()
-    # the double buffer as the file states it: two tiles of 64 keys x (512 + 64) bf16 elements, ONE per workgroup of four waves
-    assert "constexpr size_t mla_lds_bytes() { return 2 * (size_t)MLA_IMG; }" in src
-    assert re.search(r"MLA_DQK = 576, MLA_DV = 512", src) and "MLA_IMG = MLA_LAT + MLA_ROT" in src
-    assert "constexpr int MLA_KV8_NW = 4;" in src and "dim3(64 * MLA_KV8_NW), mla_lds_bytes(), s, p)" in src
+    # the double buffer as fa_mla_body.h states it: two tiles of 64 keys x (512 + 64) bf16 elements, ONE per workgroup of four waves
+    assert "constexpr int MLA_KV8_NW = 4;" in src
+    launch_tail_uses_the_double_buffer(image_is_stated_in_the_body_header_alone(), src, "MLA_KV8_NW")
     lds = 2 * 64 * (512 + 64) * 2
     assert lds == 144 * 1024 and lds <= 160 * 1024
     # from LDS onwards the text is the wide kernel's: the four parts of fa_mla_body.h, each included once

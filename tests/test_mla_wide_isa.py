@@ -10,7 +10,7 @@ import pytest
 
 from test_isa_audit import makefile_flags
 from test_ksplit_isa import rows_of
-from test_mla_isa import COMBINE, CSRC, OTHERS, PARTIAL
+from test_mla_isa import COMBINE, CSRC, OTHERS, PARTIAL, image_is_stated_in_the_body_header_alone, launch_tail_uses_the_double_buffer
 from test_varlen_paged_isa import _compile
 
 WIDE = "mla_wide_partial_kernel"
@@ -42,10 +42,8 @@ def test_no_static_lds_and_the_shared_double_buffer_fits_the_cu(listing):
     sizes = dict(re.findall(r"Function Name: (\S+).*?LDS Size \[bytes/block\]: (\d+)", listing[1], re.S))
     assert len(sizes) == 8 and all(int(v) == 0 for v in sizes.values()), sizes
     src = open(os.path.join(CSRC, "fa_mla_wide_kernel.hip")).read()
-    # the double buffer as the file states it: two tiles of 64 keys x (512 + 64) elements of two bytes, ONE per workgroup
-    assert "constexpr size_t mla_lds_bytes() { return 2 * (size_t)MLA_IMG; }" in src
-    assert re.search(r"MLA_DQK = 576, MLA_DV = 512", src) and "MLA_IMG = MLA_LAT + MLA_ROT" in src
-    assert "dim3(64 * nw), mla_lds_bytes(), s, p)" in src
+    # the double buffer as fa_mla_body.h states it: two tiles of 64 keys x (512 + 64) elements of two bytes, ONE per workgroup
+    launch_tail_uses_the_double_buffer(image_is_stated_in_the_body_header_alone(), src, "nw")
     lds = 2 * 64 * (512 + 64) * 2
     assert lds == 144 * 1024 and lds <= 160 * 1024
 
