@@ -37,6 +37,8 @@ from .ops import (  # noqa: F401
     mla_decode_paged_wide_supported,
     mla_decode_paged_wide_workspace_bytes,
     mla_decode_paged_workspace_bytes,
+    mla_decode_sparse_kv8_supported,
+    mla_decode_sparse_kv8_workspace_bytes,
     mla_decode_sparse_supported,
     mla_decode_sparse_workspace_bytes,
     supported,

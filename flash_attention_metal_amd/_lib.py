@@ -37,6 +37,9 @@ SYMBOLS = {
     "fa_fwd_mla_decode_sparse": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_float] + [c_longlong] * 7 + [c_int, c_void_p, c_longlong, c_void_p]),
     "fa_fwd_mla_decode_sparse_workspace_bytes": (c_longlong, [c_int] * 4),
     "fa_fwd_mla_decode_sparse_supported": (c_int, [c_int] * 5),
+    "fa_fwd_mla_decode_sparse_kv8": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_float] + [c_longlong] * 7 + [c_int, c_int, c_void_p, c_longlong, c_void_p]),
+    "fa_fwd_mla_decode_sparse_kv8_workspace_bytes": (c_longlong, [c_int] * 4),
+    "fa_fwd_mla_decode_sparse_kv8_supported": (c_int, [c_int] * 6),
     "fa_fwd_varlen_mla": (c_int, [c_void_p] * 7 + [c_int] * 9 + [c_float] + [c_longlong] * 8 + [c_int, c_int, c_void_p]),
     "fa_fwd_varlen_mla_supported": (c_int, [c_int] * 3),
     "fa_bwd_varlen_mla": (c_int, [c_void_p] * 12 + [c_int] * 9 + [c_float] + [c_longlong] * 8 + [c_int, c_int, c_void_p]),

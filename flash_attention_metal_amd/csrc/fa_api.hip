@@ -847,24 +847,36 @@ long long fa_fwd_mla_decode_sparse_workspace_bytes(int T, int Hq, int Dv, int to
   if (topk < 1 || mla_sparse_cap(topk) > (1 << 30)) return 0;
   return fa_fwd_mla_decode_paged_wide_workspace_bytes(T, Hq, 1, Dv, 64, (int)(mla_sparse_cap(topk) / 64));
 }
-int fa_fwd_mla_decode_sparse(const void *q, const void *kv_pages, void *o, float *lse, const int *indices, const int *index_counts, int T,
-                             int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages, float scale, long long q_token_stride,
-                             long long q_head_stride, long long o_token_stride, long long o_head_stride, long long kv_page_stride,
-                             long long kv_row_stride, long long indices_stride, int dtype, void *workspace, long long workspace_bytes,
-                             void *hip_stream) {
-  const char *fn = "fa_fwd_mla_decode_sparse";
+// The two modes of the one path. MLA_SPARSE_WIDE: f16 / bf16, q and the pool alike (fa_mla_sparse_kernel.hip). MLA_SPARSE_KV8: bf16
+// queries on an e4m3 pool (fa_mla_sparse_kv8_kernel.hip), the same split count and workspace; `dtype` is the queries' and kv_dtype the
+// pool's (the other mode: both are `dtype`). The dtype-pair rule and the pool's stride multiple are all that differ.
+enum { MLA_SPARSE_WIDE = 0, MLA_SPARSE_KV8 = 1 };
+static bool mla_sparse_kv8_shape_ok(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int page_size) {
+  return mla_kv8_shape_ok(q_dtype, kv_dtype, Dqk, Dv, Hq, 1, page_size);
+}
+static int mla_decode_sparse_impl(const char *fn, int mode, const void *q, const void *kv_pages, void *o, float *lse, const int *indices,
+                                  const int *index_counts, int T, int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages, float scale,
+                                  long long q_token_stride, long long q_head_stride, long long o_token_stride, long long o_head_stride,
+                                  long long kv_page_stride, long long kv_row_stride, long long indices_stride, int dtype, int kv_dtype,
+                                  void *workspace, long long workspace_bytes, void *hip_stream) {
   g_err[0] = 0;
   TRY(nonnull(fn, {q, kv_pages, o, indices, workspace}));
   TRY(positive(fn, {T, Hq, Dqk, Dv, topk, page_size, num_pages}));
   TRY(scale_ok(fn, scale));
-  if (!mla_decode_shape_ok(dtype, Dqk, Dv, Hq, 1, page_size, 128))
+  if (mode == MLA_SPARSE_KV8) {
+    if (!mla_sparse_kv8_shape_ok(dtype, kv_dtype, Dqk, Dv, Hq, page_size))
+      return fail(FA_ERR_UNSUPPORTED, "%s: needs bf16 queries on an e4m3 pool, (Dqk, Dv) = (576, 512), Hq <= 128 heads and a page size of "
+                  "16, 32, 64, 128 or 256; got q=%s kv=%s Dqk=%d Dv=%d Hq=%d page_size=%d", fn, fa_dtype_name(dtype), fa_dtype_name(kv_dtype),
+                  Dqk, Dv, Hq, page_size);
+  } else if (!mla_decode_shape_ok(dtype, Dqk, Dv, Hq, 1, page_size, 128))
     return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 (q and the pool alike), (Dqk, Dv) = (576, 512), Hq <= 128 heads and a page size of "
                 "16, 32, 64, 128 or 256; got dtype=%s Dqk=%d Dv=%d Hq=%d page_size=%d", fn, fa_dtype_name(dtype), Dqk, Dv, Hq, page_size);
   if (indices_stride < topk || (indices_stride % 4))
     return fail(FA_ERR_INVALID_ARG, "%s: indices_stride=%lld must be a multiple of 4 and >= topk=%d", fn, indices_stride, topk);
   TRY(mla_strides_ok(fn, "", T, Dqk, q_token_stride, q_head_stride, Dqk));
   TRY(mla_strides_ok(fn, "output ", T, Dv, o_token_stride, o_head_stride, Dv));
-  TRY(page_strides_ok(fn, Dqk, page_size, kv_page_stride, kv_row_stride, kv_row_stride, 0, dtype));
+  // (an e4m3 pool: strides in elements = bytes, multiples of 16, a page counted in bytes of 1 -- fa_fwd_mla_decode_paged_kv8's rule)
+  TRY(page_strides_ok(fn, Dqk, page_size, kv_page_stride, kv_row_stride, kv_row_stride, 0, kv_dtype));
   TRY(aligned16(fn, "tensors and workspace", {q, kv_pages, o, workspace}));
   TRY(aligned16(fn, "indices", {indices}));
   if ((uintptr_t)index_counts & 3) return fail(FA_ERR_INVALID_ARG, "%s: index_counts must be int32-aligned", fn);
@@ -872,7 +884,8 @@ int fa_fwd_mla_decode_sparse(const void *q, const void *kv_pages, void *o, float
   if ((long long)num_pages * page_size > (1 << 30))
     return fail(FA_ERR_INVALID_ARG, "%s: num_pages * page_size = %lld slots, above 2^30", fn, (long long)num_pages * page_size);
   const int cap = (int)mla_sparse_cap(topk);
-  TRY(workspace_fits(fn, workspace_bytes, fa::mla_decode_sparse_workspace_bytes(T, Hq, cap), "fa_fwd_mla_decode_sparse_workspace_bytes"));
+  TRY(workspace_fits(fn, workspace_bytes, fa::mla_decode_sparse_workspace_bytes(T, Hq, cap),
+                     mode == MLA_SPARSE_KV8 ? "fa_fwd_mla_decode_sparse_kv8_workspace_bytes" : "fa_fwd_mla_decode_sparse_workspace_bytes"));
   const int rblk = (Hq + 15) / 16;
   if ((long long)T * Hq > 0x7fffffffLL || (long long)T * 256 * rblk > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
   const int nw = fa::mla_wide_waves(Hq);
@@ -880,7 +893,9 @@ int fa_fwd_mla_decode_sparse(const void *q, const void *kv_pages, void *o, float
   p.q = q; p.kv = kv_pages; p.ws = (float *)workspace;
   p.indices = indices; p.counts = index_counts;
   p.T = T; p.Hq = Hq; p.Nq = 1; p.RBLK = rblk; p.scale = scale;
-  p.S = fa::mla_decode_splits(T, (rblk + nw - 1) / nw, cap);  // the wide call's own rule at (T, 1, cap)
+  // the wide call's own rule at (T, 1, cap), in both modes: both kernels run four waves for every head count, and for Hq <= 32 (rblk
+  // <= 2) the rule is fed ONE row block under either wave count, ceil(rblk / 2) = ceil(rblk / 4) = 1 -- the same S, the same workspace
+  p.S = fa::mla_decode_splits(T, (rblk + nw - 1) / nw, cap);
   p.q_bs = q_token_stride; p.q_hs = q_head_stride; p.q_rs = Dqk;
   p.page_stride = kv_page_stride; p.row_stride = kv_row_stride; p.idx_stride = indices_stride;
   p.topk = topk; p.num_slots = num_pages * page_size;
@@ -889,7 +904,34 @@ int fa_fwd_mla_decode_sparse(const void *q, const void *kv_pages, void *o, float
   pc.o = o; pc.lse = lse; pc.ws = p.ws;
   pc.B = T; pc.Hq = Hq; pc.Nq = 1; pc.S = p.S; pc.RBLK = rblk;
   pc.o_bs = o_token_stride; pc.o_hs = o_head_stride; pc.o_rs = Dv;
-  return launched(fn, fa::launch_mla_decode_sparse(p, pc, dtype, (hipStream_t)hip_stream));
+  return launched(fn, mode == MLA_SPARSE_KV8 ? fa::launch_mla_decode_sparse_kv8(p, pc, (hipStream_t)hip_stream)
+                                             : fa::launch_mla_decode_sparse(p, pc, dtype, (hipStream_t)hip_stream));
+}
+int fa_fwd_mla_decode_sparse(const void *q, const void *kv_pages, void *o, float *lse, const int *indices, const int *index_counts, int T,
+                             int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages, float scale, long long q_token_stride,
+                             long long q_head_stride, long long o_token_stride, long long o_head_stride, long long kv_page_stride,
+                             long long kv_row_stride, long long indices_stride, int dtype, void *workspace, long long workspace_bytes,
+                             void *hip_stream) {
+  return mla_decode_sparse_impl("fa_fwd_mla_decode_sparse", MLA_SPARSE_WIDE, q, kv_pages, o, lse, indices, index_counts, T, Hq, Dqk, Dv, topk,
+                                page_size, num_pages, scale, q_token_stride, q_head_stride, o_token_stride, o_head_stride, kv_page_stride,
+                                kv_row_stride, indices_stride, dtype, dtype, workspace, workspace_bytes, hip_stream);
+}
+
+// fa_fwd_mla_decode_sparse_kv8: the sparse call on an e4m3 pool under bf16 queries -- the second mode of the path above
+int fa_fwd_mla_decode_sparse_kv8_supported(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int page_size) {
+  return mla_sparse_kv8_shape_ok(q_dtype, kv_dtype, Dqk, Dv, Hq, page_size);
+}
+long long fa_fwd_mla_decode_sparse_kv8_workspace_bytes(int T, int Hq, int Dv, int topk) {
+  return fa_fwd_mla_decode_sparse_workspace_bytes(T, Hq, Dv, topk);
+}
+int fa_fwd_mla_decode_sparse_kv8(const void *q, const void *kv_pages, void *o, float *lse, const int *indices, const int *index_counts, int T,
+                                 int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages, float scale, long long q_token_stride,
+                                 long long q_head_stride, long long o_token_stride, long long o_head_stride, long long kv_page_stride,
+                                 long long kv_row_stride, long long indices_stride, int q_dtype, int kv_dtype, void *workspace,
+                                 long long workspace_bytes, void *hip_stream) {
+  return mla_decode_sparse_impl("fa_fwd_mla_decode_sparse_kv8", MLA_SPARSE_KV8, q, kv_pages, o, lse, indices, index_counts, T, Hq, Dqk, Dv,
+                                topk, page_size, num_pages, scale, q_token_stride, q_head_stride, o_token_stride, o_head_stride,
+                                kv_page_stride, kv_row_stride, indices_stride, q_dtype, kv_dtype, workspace, workspace_bytes, hip_stream);
 }
 
 int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size) { return fa::mfma_varlen_paged_supported(dtype, D, page_size); }

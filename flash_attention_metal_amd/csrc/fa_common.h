@@ -326,6 +326,10 @@ long long mla_decode_kv8_workspace_bytes(int B, int Hq, int Nq, int Nk);
 // kernel on pc
 hipError_t launch_mla_decode_sparse(const MlaSparseParams &p, const MlaDecodeParams &pc, int dtype, hipStream_t s);
 long long mla_decode_sparse_workspace_bytes(int T, int Hq, int cap);
+// fa_fwd_mla_decode_sparse_kv8 (csrc/fa_mla_sparse_kv8_kernel.hip): the sparse call over an e4m3 pool (p's pool strides count bytes), bf16
+// queries, the tile staged through registers and widened as fa_fwd_mla_decode_paged_kv8 does; the sparse call's split count, workspace
+// and (bf16) combine kernel
+hipError_t launch_mla_decode_sparse_kv8(const MlaSparseParams &p, const MlaDecodeParams &pc, hipStream_t s);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);

@@ -458,6 +458,14 @@ def mla_decode_sparse_workspace_bytes(T: int, Hq: int, d_v: int, topk: int) -> i
     return int(load_library().fa_fwd_mla_decode_sparse_workspace_bytes(T, Hq, d_v, topk))
 
 
+def mla_decode_sparse_kv8_supported(q_dtype: str, kv_dtype: str, d_qk: int, d_v: int, Hq: int, page_size: int) -> bool:
+    return bool(load_library().fa_fwd_mla_decode_sparse_kv8_supported(DTYPES[q_dtype], DTYPES[kv_dtype], d_qk, d_v, Hq, page_size))
+
+
+def mla_decode_sparse_kv8_workspace_bytes(T: int, Hq: int, d_v: int, topk: int) -> int:
+    return int(load_library().fa_fwd_mla_decode_sparse_kv8_workspace_bytes(T, Hq, d_v, topk))
+
+
 def flash_attention_mla_decode_sparse(
     q: torch.Tensor,
     kv_pages: torch.Tensor,
@@ -480,12 +488,19 @@ def flash_attention_mla_decode_sparse(
     never read. `scale` is required (the model's: the head dim of the model is not 576). Returns O [T,Hq,d_v] (allocated contiguous if
     `out` is None; any strides with a unit last stride otherwise) and LSE [T,Hq] fp32 or None. A token with no key gets O = 0 and
     LSE = -inf. `workspace`: a uint8 device tensor of at least mla_decode_sparse_workspace_bytes(T, Hq, d_v, topk) bytes (allocated here
-    if None)."""
+    if None).
+    A torch.float8_e4m3fn pool under bf16 q goes to fa_fwd_mla_decode_sparse_kv8 (no scales: the bytes are read as plain e4m3 values; a
+    caller that appended with k_mul = v_mul = 1 / s passes scale * s and multiplies O by s). The pool's strides are then bytes, a SLOT
+    is still page * P + row, O is bf16 and the workspace is sized by mla_decode_sparse_kv8_workspace_bytes(...), the same number; f16 q
+    on such a pool raises ValueError."""
     lib = load_library()
     if scale is None:
         raise ValueError("flash_attention_mla_decode_sparse needs the model's scale: there is no default (the head dim of the model is not 576)")
     if q.dim() != 3 or kv_pages.dim() not in (3, 4) or (kv_pages.dim() == 4 and kv_pages.shape[2] != 1):
         raise ValueError("q [T,Hq,576], kv_pages one [num_pages,P,576] or [num_pages,P,1,576] latent pool")
+    kv8 = _FP8 is not None and kv_pages.dtype == _FP8
+    if kv8 and q.dtype != torch.bfloat16:
+        raise ValueError(f"unsupported dtypes {q.dtype} {kv_pages.dtype}: a float8_e4m3fn latent pool takes bf16 queries only")
     tensors = (q, kv_pages, indices) + (() if index_counts is None else (index_counts,))
     if not all(t.is_cuda and t.device == q.device for t in tensors):
         raise ValueError("flash_attention_mla_decode_sparse needs q, the pool, the index lists and their counts on one device: there is no CPU path")
@@ -498,7 +513,7 @@ def flash_attention_mla_decode_sparse(
         raise ValueError("indices must be an int32 [T, topk] tensor with a unit last stride")
     if index_counts is not None and (index_counts.dtype != torch.int32 or index_counts.shape != (T,) or not index_counts.is_contiguous()):
         raise ValueError("index_counts must be a contiguous int32 [T] tensor, or None")
-    if q.dtype not in (torch.float16, torch.bfloat16) or kv_pages.dtype != q.dtype:
+    if not kv8 and (q.dtype not in (torch.float16, torch.bfloat16) or kv_pages.dtype != q.dtype):
         raise ValueError(f"unsupported / mixed dtypes {q.dtype} {kv_pages.dtype} (f16 or bf16, q and the pool alike)")
     d_v = int(d_v)
     topk = indices.shape[1]
@@ -512,6 +527,13 @@ def flash_attention_mla_decode_sparse(
         raise ValueError("lse must be contiguous fp32 [T,Hq] on q's device")
     # (one row: its stride addresses nothing, and torch reports any value for a dimension of size 1)
     istride = indices.stride(0) if T > 1 else (topk + 3) // 4 * 4
+    if kv8:  # (the pool's strides come from the tensor: bytes)
+        ws = _workspace(workspace, mla_decode_sparse_kv8_workspace_bytes(T, Hq, d_v, topk), q.device)
+        _call(lib, "fa_fwd_mla_decode_sparse_kv8",
+              (q.data_ptr(), kv_pages.data_ptr(), out.data_ptr(), _ptr(lse), indices.data_ptr(), _ptr(index_counts), T, Hq, Dqk, d_v, topk, P,
+               num_pages, float(scale), q.stride(0), q.stride(1), out.stride(0), out.stride(1), ps, rs, istride,
+               _TORCH2FA[q.dtype], _TORCH2FA[kv_pages.dtype], ws.data_ptr(), ws.numel()), q.device, stream)
+        return out, lse
     ws = _workspace(workspace, mla_decode_sparse_workspace_bytes(T, Hq, d_v, topk), q.device)
     _call(lib, "fa_fwd_mla_decode_sparse",
           (q.data_ptr(), kv_pages.data_ptr(), out.data_ptr(), _ptr(lse), indices.data_ptr(), _ptr(index_counts), T, Hq, Dqk, d_v, topk, P,

@@ -947,6 +947,56 @@ long long fa_fwd_mla_decode_sparse_workspace_bytes(int T, int Hq, int Dv, int to
 int fa_fwd_mla_decode_sparse_supported(int dtype, int Dqk, int Dv, int Hq, int page_size);
 
 /*
+ * Multi-head latent attention (decode, sparse, e4m3 pool): fa_fwd_mla_decode_sparse_kv8 is fa_fwd_mla_decode_sparse under bf16 queries on a
+ * latent pool of OCP e4m3 (e4m3fn) bytes, 576 bytes per key: what a sparse-attention model served with an fp8 KV cache calls at every
+ * layer and step. The listed rows are read in place; no gather into a second e4m3 pool. The argument list is the sparse call's with
+ * `int dtype` replaced by `int q_dtype, int kv_dtype`.
+ * Supported: (q_dtype, kv_dtype) = (FA_DTYPE_BF16, FA_DTYPE_FP8_E4M3) only, O is bf16; (Dqk, Dv) = (576, 512), 1 <= Hq <= 128, topk >= 1,
+ * T >= 1, P in {16, 32, 64, 128, 256}; anything else -- (f16, e4m3), (e4m3, e4m3) and (bf16, bf16) included -- FA_ERR_UNSUPPORTED with a
+ * message that names what was given. fa_fwd_mla_decode_sparse_supported keeps answering 0 for e4m3 and that call keeps refusing such pools.
+ * The pool is [num_pages, P, 576] BYTES; kv_page_stride and kv_row_stride count elements (= bytes), are multiples of 16 and at least 576,
+ * the base is 16-byte aligned (fa_fwd_mla_decode_paged_kv8's rule, with its statuses and texts). The pool may exceed 4 GiB, one page stays
+ * below 2 GiB. A key is the SLOT x = page * P + row; its byte address is (x >> log2 P) * kv_page_stride + (x & (P - 1)) * kv_row_stride.
+ * Lists, counts, q and o follow fa_fwd_mla_decode_sparse exactly, in its words: indices is int32 [T, indices_stride], the stride at
+ * least topk and a multiple of 4, the base 16-byte aligned; index_counts is int32 [T] or NULL; a slot named twice enters twice; an entry
+ * among the first n_t outside [0, num_pages * P) is a key of zeros and no address is formed from it; nothing at j >= n_t or j >= topk
+ * is ever read; n_t = 0 gives O = 0 exactly and LSE = -inf; pool bytes that no list names have no influence (the e4m3 NaN codes 0x7F /
+ * 0xFF there are harmless); the host reads neither table and both grids depend on host scalars alone (graph-capturable).
+ * NO SCALES, in the words of fa_fwd_mla_decode_paged_kv8: the bytes are read as plain e4m3 values. The cache's one per-tensor scale s goes
+ * into scale * s and behind O (a caller that appended with k_mul = v_mul = 1 / s multiplies O by s or folds s into the projection).
+ * THE CONTRACT: with cap = 64 * ceil(topk / 64), O and LSE are BIT-IDENTICAL to both of
+ *   1. fa_fwd_mla_decode_sparse(..., FA_DTYPE_BF16) on a bf16 pool that holds the same values widened (every e4m3 value is a bf16 value),
+ *      under the same lists and counts, the same strides in elements and the same page size;
+ *   2. fa_fwd_mla_decode_paged_kv8(B = T, Nq = 1, page_size = 64, max_pages_per_seq = cap / 64, is_causal = 0, seqlens_k = n) on an e4m3
+ *      pool into which every token's listed rows were copied in list order, out-of-range entries as zero rows.
+ * The split count S is what fa_fwd_mla_decode_sparse computes (for Hq <= 32 the split rule is fed one row block under either wave
+ * count), and fa_fwd_mla_decode_sparse_kv8_workspace_bytes equals fa_fwd_mla_decode_sparse_workspace_bytes(T, Hq, Dv, topk) on every legal
+ * input and is 0 elsewhere. Everything else is inherited in the same words: the tolerances and "LSE accuracy"; no dependence on the
+ * workspace's prior contents; bitwise reproducible; asynchronous, allocates nothing.
+ * Validation runs on the sparse call's path: every rule the two calls share carries the same status and the same text after the
+ * function name; only the dtype-pair rule and the 16-element stride rule differ.
+ * The quantising append is fa_kv_append_paged_quant on the aliased pool (Hkv = 1, D = 576, k_pages == v_pages, k_mul == v_mul).
+ * How it runs (csrc/fa_mla_sparse_kv8_kernel.hip): fa_fwd_mla_decode_paged_kv8's four-wave workgroup over the item
+ * (token, split). Wave w stages rows 16 * w .. + 15 of a tile through registers under that kernel's lane maps; only the nine raw loads
+ * per lane differ: each lane takes its row's entry from the wave's entry register, forms the row's 64-bit byte address and issues one
+ * predicated 16-byte load (an invalid entry: zeros, no load). Widening, the tile image and everything from LDS onwards are the twins'.
+ * Not here: f16 or e4m3 queries; scales inside the kernel, block or per-token scales; the 656-byte rows (e4m3 latent + fp32 tile scales
+ * + bf16 rotary); a mask inside the list; more than 128 heads; sinks, window and softcap; the indexer itself; a sparse backward. No
+ * dense call is rerouted.
+ */
+int fa_fwd_mla_decode_sparse_kv8(const void *q, const void *kv_pages, void *o, float *lse,
+                                 const int *indices, const int *index_counts,
+                                 int T, int Hq, int Dqk, int Dv, int topk,
+                                 int page_size, int num_pages, float scale,
+                                 long long q_token_stride, long long q_head_stride,
+                                 long long o_token_stride, long long o_head_stride,
+                                 long long kv_page_stride, long long kv_row_stride, long long indices_stride,
+                                 int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes, void *hip_stream);
+/* the sparse call's size on every legal input; 0 if a size is invalid or unsupported */
+long long fa_fwd_mla_decode_sparse_kv8_workspace_bytes(int T, int Hq, int Dv, int topk);
+int fa_fwd_mla_decode_sparse_kv8_supported(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int page_size);
+
+/*
  * Multi-head latent attention (prefill): fa_fwd_varlen_mla is the NON-absorbed form of the same layer, as serving engines run its
  * prefill: the latent rows are up-projected to per-head keys and values, and ordinary multi-head attention runs over packed sequences
  * with a query / key head dim of Dqk = 192 (128 "nope" + 64 rotary) and a value head dim of Dv = 128. Per sequence the operator is
