@@ -24,6 +24,7 @@ from .ops import (  # noqa: F401
     flash_attention_forward,
     flash_attention_mla_decode_paged,
     flash_attention_mla_decode_sparse,
+    flash_attention_mla_indexer_topk,
     flash_attention_varlen,
     flash_attention_varlen_backward,
     flash_attention_varlen_mla,
@@ -41,6 +42,11 @@ from .ops import (  # noqa: F401
     mla_decode_sparse_kv8_workspace_bytes,
     mla_decode_sparse_supported,
     mla_decode_sparse_workspace_bytes,
+    mla_indexer_chunk_keys,
+    mla_indexer_logits,
+    mla_indexer_select,
+    mla_indexer_supported,
+    mla_indexer_workspace_bytes,
     supported,
     varlen_backward_supported,
     varlen_backward_workspace_bytes,

@@ -934,6 +934,148 @@ int fa_fwd_mla_decode_sparse_kv8(const void *q, const void *kv_pages, void *o, f
                                 kv_page_stride, kv_row_stride, indices_stride, q_dtype, kv_dtype, workspace, workspace_bytes, hip_stream);
 }
 
+// ---- fa_mla_indexer_*: the indexer in front of the sparse decode (csrc/fa_mla_indexer_kernel.hip). The query side and the tables carry
+// fa_fwd_varlen_paged's rules (the shared helpers in its order, its statuses and texts), the lists fa_fwd_mla_decode_sparse's; the rules
+// of these calls' own (w, the logits buffer, the workspace) follow them. The composite call checks the rules of both stages, then its
+// workspace, before the first launch.
+int fa_mla_indexer_supported(int dtype, int Hi, int Di, int page_size) {
+  return (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) && (Hi == 32 || Hi == 64) && Di == 128 && fa::page_size_ok(page_size);
+}
+static bool mla_indexer_scalars_ok(int page_size, int max_pages_per_seq) {
+  return fa::page_size_ok(page_size) && max_pages_per_seq >= 1 && (long long)page_size * max_pages_per_seq <= (1 << 30);
+}
+int fa_mla_indexer_chunk_keys(int B, int max_seqlen_q, int page_size, int max_pages_per_seq) {
+  if (B < 1 || max_seqlen_q < 1 || !mla_indexer_scalars_ok(page_size, max_pages_per_seq)) return 0;
+  return 64 * fa::mla_indexer_chunk_tiles(B, max_seqlen_q, page_size, max_pages_per_seq);
+}
+long long fa_mla_indexer_topk_paged_workspace_bytes(int total_q, int page_size, int max_pages_per_seq) {
+  if (total_q < 1 || !mla_indexer_scalars_ok(page_size, max_pages_per_seq)) return 0;
+  return (long long)total_q * page_size * max_pages_per_seq * 4;  // < 2^31 * 2^30 * 4
+}
+// the select stage's rules on the tables and the token count: page_pool_ok's without a pool, in fa_fwd_varlen_paged's order
+static int mla_indexer_tables_ok(const char *fn, const void *cu_seqlens_q, const void *block_table, const void *seqlens_k, int total_q,
+                                 int max_seqlen_q, int page_size, int max_pages_per_seq, long long block_table_stride) {
+  if (max_seqlen_q > total_q)
+    return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen_q=%d exceeds the token count %d", fn, max_seqlen_q, total_q);
+  TRY(table_stride_ok(fn, block_table_stride, max_pages_per_seq));
+  if (block_table_stride > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: bad page strides", fn);
+  TRY(page_tables_ok(fn, page_size, max_pages_per_seq, block_table, seqlens_k));
+  if ((uintptr_t)cu_seqlens_q & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q must be int32-aligned", fn);
+  return FA_OK;
+}
+static int mla_indexer_logits_buffer_ok(const char *fn, const void *logits, long long logits_stride, int page_size, int max_pages_per_seq) {
+  if ((uintptr_t)logits & 3) return fail(FA_ERR_INVALID_ARG, "%s: logits must be fp32-aligned", fn);
+  if (logits_stride < (long long)page_size * max_pages_per_seq)
+    return fail(FA_ERR_INVALID_ARG, "%s: logits_stride=%lld < max_pages_per_seq * page_size = %lld", fn, logits_stride,
+                (long long)page_size * max_pages_per_seq);
+  return FA_OK;
+}
+static int mla_indexer_logits_check(const char *fn, fa::MlaIndexerParams &p, const void *q_idx, const float *w, const void *k_idx_pages,
+                                    float *logits, const int *cu_seqlens_q, const int *block_table, const int *seqlens_k, int B, int Hi,
+                                    int total_q, int max_seqlen_q, int Di, int page_size, int num_pages, int max_pages_per_seq,
+                                    long long q_row_stride, long long q_head_stride, long long w_row_stride, long long k_page_stride,
+                                    long long k_row_stride, long long block_table_stride, long long logits_stride, int dtype) {
+  TRY(nonnull(fn, {q_idx, w, k_idx_pages, logits, cu_seqlens_q, block_table, seqlens_k}));
+  TRY(positive(fn, {B, Hi, total_q, max_seqlen_q, Di, page_size, num_pages, max_pages_per_seq}));
+  if (!fa_mla_indexer_supported(dtype, Hi, Di, page_size))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 (q_idx and the pool alike), Hi = 32 | 64, Di = 128 and a page size of 16, 32, 64, "
+                "128 or 256; got dtype=%s Hi=%d Di=%d page_size=%d", fn, fa_dtype_name(dtype), Hi, Di, page_size);
+  if (max_seqlen_q > total_q)  // (in fa_fwd_varlen_paged's place: in front of the strides)
+    return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen_q=%d exceeds the token count %d", fn, max_seqlen_q, total_q);
+  TRY(varlen_strides_ok(fn, "", Di, q_row_stride, q_head_stride, stride_mult(dtype)));
+  TRY(page_pool_ok(fn, Di, page_size, max_pages_per_seq, k_page_stride, k_row_stride, k_row_stride, block_table_stride, dtype, block_table, seqlens_k));
+  TRY(aligned16(fn, "tensors", {q_idx, k_idx_pages}));
+  if ((uintptr_t)cu_seqlens_q & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q must be int32-aligned", fn);
+  if ((uintptr_t)w & 3) return fail(FA_ERR_INVALID_ARG, "%s: w must be fp32-aligned", fn);
+  if (w_row_stride < Hi) return fail(FA_ERR_INVALID_ARG, "%s: w_row_stride=%lld < Hi=%d", fn, w_row_stride, Hi);
+  TRY(mla_indexer_logits_buffer_ok(fn, logits, logits_stride, page_size, max_pages_per_seq));
+  p.q = q_idx; p.k = k_idx_pages; p.w = w; p.logits = logits;
+  p.cu_q = cu_seqlens_q; p.block_table = block_table; p.seqlens = seqlens_k;
+  p.B = B; p.total_q = total_q; p.max_q = max_seqlen_q;
+  p.tb = fa::mla_indexer_token_block(max_seqlen_q);
+  p.nblk = (max_seqlen_q + p.tb - 1) / p.tb;
+  p.chunk_tiles = fa::mla_indexer_chunk_tiles(B, max_seqlen_q, page_size, max_pages_per_seq);
+  const long long nT = ((long long)page_size * max_pages_per_seq + 63) / 64;
+  p.nchunks = (int)((nT + p.chunk_tiles - 1) / p.chunk_tiles);
+  p.q_rs = q_row_stride; p.q_hs = q_head_stride; p.w_rs = w_row_stride;
+  p.page_stride = k_page_stride; p.row_stride = k_row_stride; p.logits_stride = logits_stride;
+  p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
+  p.lp = log2_of(page_size);
+  if ((long long)B * p.nblk > 0x7fffffffLL / p.nchunks) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  return FA_OK;
+}
+static int mla_indexer_select_check(const char *fn, fa::MlaIndexerSelectParams &p, const float *logits, int *indices, int *index_counts,
+                                    const int *cu_seqlens_q, const int *block_table, const int *seqlens_k, int B, int total_q,
+                                    int max_seqlen_q, int topk, int page_size, int num_pages, int max_pages_per_seq, long long logits_stride,
+                                    long long indices_stride, long long block_table_stride) {
+  TRY(nonnull(fn, {logits, indices, index_counts, cu_seqlens_q, block_table, seqlens_k}));
+  TRY(positive(fn, {B, total_q, max_seqlen_q, topk, page_size, num_pages, max_pages_per_seq}));
+  if (!fa::page_size_ok(page_size))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs a page size of 16, 32, 64, 128 or 256; got page_size=%d", fn, page_size);
+  if (indices_stride < topk || (indices_stride % 4))
+    return fail(FA_ERR_INVALID_ARG, "%s: indices_stride=%lld must be a multiple of 4 and >= topk=%d", fn, indices_stride, topk);
+  TRY(mla_indexer_tables_ok(fn, cu_seqlens_q, block_table, seqlens_k, total_q, max_seqlen_q, page_size, max_pages_per_seq, block_table_stride));
+  TRY(aligned16(fn, "indices", {indices}));
+  if ((uintptr_t)index_counts & 3) return fail(FA_ERR_INVALID_ARG, "%s: index_counts must be int32-aligned", fn);
+  if ((long long)num_pages * page_size > (1 << 30))
+    return fail(FA_ERR_INVALID_ARG, "%s: num_pages * page_size = %lld slots, above 2^30", fn, (long long)num_pages * page_size);
+  TRY(mla_indexer_logits_buffer_ok(fn, logits, logits_stride, page_size, max_pages_per_seq));
+  if ((long long)B * max_seqlen_q > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  p.logits = logits; p.indices = indices; p.counts = index_counts;
+  p.cu_q = cu_seqlens_q; p.block_table = block_table; p.seqlens = seqlens_k;
+  p.B = B; p.total_q = total_q; p.max_q = max_seqlen_q; p.topk = topk;
+  p.logits_stride = logits_stride; p.idx_stride = indices_stride;
+  p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
+  p.lp = log2_of(page_size);
+  return FA_OK;
+}
+int fa_mla_indexer_logits_paged(const void *q_idx, const float *w, const void *k_idx_pages, float *logits, const int *cu_seqlens_q,
+                                const int *block_table, const int *seqlens_k, int B, int Hi, int total_q, int max_seqlen_q, int Di,
+                                int page_size, int num_pages, int max_pages_per_seq, long long q_row_stride, long long q_head_stride,
+                                long long w_row_stride, long long k_page_stride, long long k_row_stride, long long block_table_stride,
+                                long long logits_stride, int dtype, void *hip_stream) {
+  const char *fn = "fa_mla_indexer_logits_paged";
+  g_err[0] = 0;
+  fa::MlaIndexerParams p;
+  TRY(mla_indexer_logits_check(fn, p, q_idx, w, k_idx_pages, logits, cu_seqlens_q, block_table, seqlens_k, B, Hi, total_q, max_seqlen_q, Di,
+                               page_size, num_pages, max_pages_per_seq, q_row_stride, q_head_stride, w_row_stride, k_page_stride,
+                               k_row_stride, block_table_stride, logits_stride, dtype));
+  return launched(fn, fa::launch_mla_indexer_logits(p, Hi, dtype, (hipStream_t)hip_stream));
+}
+int fa_mla_indexer_select(const float *logits, int *indices, int *index_counts, const int *cu_seqlens_q, const int *block_table,
+                          const int *seqlens_k, int B, int total_q, int max_seqlen_q, int topk, int page_size, int num_pages,
+                          int max_pages_per_seq, long long logits_stride, long long indices_stride, long long block_table_stride,
+                          void *hip_stream) {
+  const char *fn = "fa_mla_indexer_select";
+  g_err[0] = 0;
+  fa::MlaIndexerSelectParams p;
+  TRY(mla_indexer_select_check(fn, p, logits, indices, index_counts, cu_seqlens_q, block_table, seqlens_k, B, total_q, max_seqlen_q, topk,
+                               page_size, num_pages, max_pages_per_seq, logits_stride, indices_stride, block_table_stride));
+  return launched(fn, fa::launch_mla_indexer_select(p, (hipStream_t)hip_stream));
+}
+int fa_mla_indexer_topk_paged(const void *q_idx, const float *w, const void *k_idx_pages, int *indices, int *index_counts,
+                              const int *cu_seqlens_q, const int *block_table, const int *seqlens_k, int B, int Hi, int total_q,
+                              int max_seqlen_q, int Di, int topk, int page_size, int num_pages, int max_pages_per_seq,
+                              long long q_row_stride, long long q_head_stride, long long w_row_stride, long long k_page_stride,
+                              long long k_row_stride, long long block_table_stride, long long indices_stride, int dtype, void *workspace,
+                              long long workspace_bytes, void *hip_stream) {
+  const char *fn = "fa_mla_indexer_topk_paged";
+  g_err[0] = 0;
+  TRY(nonnull(fn, {workspace}));
+  const long long cap = (long long)page_size * max_pages_per_seq;  // the workspace is the logits buffer under a row stride of the capacity
+  fa::MlaIndexerParams pl;
+  fa::MlaIndexerSelectParams ps;
+  TRY(mla_indexer_logits_check(fn, pl, q_idx, w, k_idx_pages, (float *)workspace, cu_seqlens_q, block_table, seqlens_k, B, Hi, total_q,
+                               max_seqlen_q, Di, page_size, num_pages, max_pages_per_seq, q_row_stride, q_head_stride, w_row_stride,
+                               k_page_stride, k_row_stride, block_table_stride, cap, dtype));
+  TRY(mla_indexer_select_check(fn, ps, (const float *)workspace, indices, index_counts, cu_seqlens_q, block_table, seqlens_k, B, total_q,
+                               max_seqlen_q, topk, page_size, num_pages, max_pages_per_seq, cap, indices_stride, block_table_stride));
+  TRY(workspace_fits(fn, workspace_bytes, fa_mla_indexer_topk_paged_workspace_bytes(total_q, page_size, max_pages_per_seq),
+                     "fa_mla_indexer_topk_paged_workspace_bytes"));
+  TRY(launched(fn, fa::launch_mla_indexer_logits(pl, Hi, dtype, (hipStream_t)hip_stream)));
+  return launched(fn, fa::launch_mla_indexer_select(ps, (hipStream_t)hip_stream));
+}
+
 int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size) { return fa::mfma_varlen_paged_supported(dtype, D, page_size); }
 // the key split's scalars: sizes >= 1, a head_dim and a page size the paged prefill has, a capacity of at most 2^30 keys
 static bool ksplit_scalars_ok(int B, int Hq, int max_seqlen_q, int D, int page_size, int max_pages_per_seq) {

@@ -236,6 +236,32 @@ struct MlaSparseParams {
   int lp;               // log2 of the page size (16 .. 256)
 };
 
+// one fa_mla_indexer_logits_paged call (csrc/fa_mla_indexer_kernel.hip): q is the packed index query [total_q, Hi, 128] under (row, head)
+// element strides, w the fp32 head weights [total_q, Hi] under a row stride, k the index-key pool [num_pages, P, 128] of q's type; the
+// three tables are fa_fwd_varlen_paged's. An item is (sequence, block of tb tokens, chunk of chunk_tiles 64-key tiles).
+struct MlaIndexerParams {
+  const void *q, *k;
+  const float *w;
+  float *logits;  // [total_q, logits_stride]
+  const int *cu_q, *block_table, *seqlens;
+  int B, total_q, max_q;
+  int tb, nblk;              // tokens per block (1, 2, 4); ceil(max_q / tb)
+  int chunk_tiles, nchunks;  // tiles of a chunk; ceil(ceil(capacity / 64) / chunk_tiles)
+  long long q_rs, q_hs, w_rs, page_stride, row_stride, logits_stride;  // elements
+  int bt_stride, num_pages, max_pages;
+  int lp;  // log2 of the page size (16 .. 256)
+};
+// one fa_mla_indexer_select call: fp32 logits -> the sparse decode's slot lists and counts; one workgroup per (sequence, token)
+struct MlaIndexerSelectParams {
+  const float *logits;
+  int *indices, *counts;  // [total_q, idx_stride]; [total_q]
+  const int *cu_q, *block_table, *seqlens;
+  int B, total_q, max_q, topk;
+  long long logits_stride, idx_stride;
+  int bt_stride, num_pages, max_pages;
+  int lp;
+};
+
 // dtype tags
 struct F32 {};
 struct F16 {};
@@ -330,6 +356,12 @@ long long mla_decode_sparse_workspace_bytes(int T, int Hq, int cap);
 // queries, the tile staged through registers and widened as fa_fwd_mla_decode_paged_kv8 does; the sparse call's split count, workspace
 // and (bf16) combine kernel
 hipError_t launch_mla_decode_sparse_kv8(const MlaSparseParams &p, const MlaDecodeParams &pc, hipStream_t s);
+// fa_mla_indexer_* (csrc/fa_mla_indexer_kernel.hip): the token block (1, 2, 4) and the chunk rule from host scalars, the logits kernel
+// over B * nblk * nchunks items of four waves, the select kernel over B * max_seqlen_q workgroups
+int mla_indexer_token_block(int max_seqlen_q);
+int mla_indexer_chunk_tiles(int B, int max_seqlen_q, int page_size, int max_pages_per_seq);
+hipError_t launch_mla_indexer_logits(const MlaIndexerParams &p, int Hi, int dtype, hipStream_t s);
+hipError_t launch_mla_indexer_select(const MlaIndexerSelectParams &p, hipStream_t s);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);

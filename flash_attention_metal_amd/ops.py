@@ -542,6 +542,121 @@ def flash_attention_mla_decode_sparse(
     return out, lse
 
 
+def mla_indexer_supported(dtype: str, Hi: int, Di: int, page_size: int) -> bool:
+    return bool(load_library().fa_mla_indexer_supported(DTYPES[dtype], Hi, Di, page_size))
+
+
+def mla_indexer_workspace_bytes(total_q: int, page_size: int, max_pages_per_seq: int) -> int:
+    return int(load_library().fa_mla_indexer_topk_paged_workspace_bytes(total_q, page_size, max_pages_per_seq))
+
+
+def mla_indexer_chunk_keys(B: int, max_seqlen_q: int, page_size: int, max_pages_per_seq: int) -> int:
+    """Keys of one chunk of the logits kernel's (sequence, token block, chunk) items under these scalars; 0 if they are illegal."""
+    return int(load_library().fa_mla_indexer_chunk_keys(B, max_seqlen_q, page_size, max_pages_per_seq))
+
+
+def _indexer_inputs(entry: str, q_idx: torch.Tensor, w: torch.Tensor, k_idx_pages: torch.Tensor):
+    if q_idx.dim() != 3 or w.dim() != 2 or k_idx_pages.dim() != 3:
+        raise ValueError("q_idx [total_q,Hi,128], w [total_q,Hi] fp32, k_idx_pages [num_pages,P,128]")
+    if not all(t.is_cuda and t.device == q_idx.device for t in (w, k_idx_pages)):
+        raise ValueError(f"{entry} needs q_idx, w and the pool on one device: there is no CPU path")
+    if q_idx.dtype not in (torch.float16, torch.bfloat16) or k_idx_pages.dtype != q_idx.dtype or w.dtype != torch.float32:
+        raise ValueError(f"unsupported / mixed dtypes {q_idx.dtype} {k_idx_pages.dtype} {w.dtype} (f16 or bf16, q_idx and the pool alike; w fp32)")
+    T, Hi, Di = q_idx.shape
+    if w.shape != (T, Hi) or k_idx_pages.shape[2] != Di or q_idx.stride(2) != 1 or w.stride(1) != 1 or k_idx_pages.stride(2) != 1:
+        raise ValueError(f"incompatible q_idx {tuple(q_idx.shape)}, w {tuple(w.shape)} and pool {tuple(k_idx_pages.shape)} (unit element strides)")
+    return T, Hi, Di, (w.stride(0) if T > 1 else Hi)
+
+
+def _indexer_logits_buffer(logits: Optional[torch.Tensor], T: int, cap: int, device: torch.device) -> torch.Tensor:
+    if logits is None:
+        return torch.empty((T, cap), dtype=torch.float32, device=device)
+    if (not logits.is_cuda or logits.device != device or logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[0] != T
+            or logits.shape[1] < cap or logits.stride(1) != 1):
+        raise ValueError("logits must be an fp32 [total_q, >= max_pages_per_seq * P] device tensor with a unit last stride")
+    return logits
+
+
+def _indexer_lists(indices, index_counts, T: int, topk: int, device: torch.device):
+    if indices is None:
+        indices = torch.empty((T, (topk + 3) // 4 * 4), dtype=torch.int32, device=device)
+    elif (not indices.is_cuda or indices.device != device or indices.dtype != torch.int32 or indices.dim() != 2 or indices.shape[0] != T
+          or indices.shape[1] < topk or indices.stride(1) != 1):
+        raise ValueError("indices must be an int32 [total_q, >= topk] device tensor with a unit last stride")
+    if index_counts is None:
+        index_counts = torch.empty((T,), dtype=torch.int32, device=device)
+    elif (not index_counts.is_cuda or index_counts.device != device or index_counts.dtype != torch.int32 or index_counts.shape != (T,)
+          or not index_counts.is_contiguous()):
+        raise ValueError("index_counts must be a contiguous int32 [total_q] device tensor")
+    return indices, index_counts, (indices.stride(0) if T > 1 else (indices.shape[1] + 3) // 4 * 4)
+
+
+def mla_indexer_logits(q_idx: torch.Tensor, w: torch.Tensor, k_idx_pages: torch.Tensor, cu_seqlens_q: torch.Tensor, block_table: torch.Tensor,
+                       seqlens_k: torch.Tensor, max_seqlen_q: int, logits: Optional[torch.Tensor] = None,
+                       stream: Optional[int] = None) -> torch.Tensor:
+    """The indexer's logits (include/fa_mi355.h fa_mla_indexer_logits_paged): logits[t, j] = sum_h w[t, h] relu(q_idx[t, h] . k_idx(b, j))
+    for the keys j < v token t sees under the bottom-right causal rule, fp32, into `logits` [total_q, >= max_pages_per_seq * P] (allocated
+    UNINITIALISED if None: columns at or behind v and rows of tokens nobody owns are not written). No scale inside: fold it into w."""
+    lib = load_library()
+    T, Hi, Di, wrs = _indexer_inputs("mla_indexer_logits", q_idx, w, k_idx_pages)
+    B = _tables("mla_indexer_logits", cu_seqlens_q, "cu_seqlens_q", block_table, seqlens_k)
+    num_pages, P = k_idx_pages.shape[0], k_idx_pages.shape[1]
+    mp = block_table.shape[1]
+    logits = _indexer_logits_buffer(logits, T, P * mp, q_idx.device)
+    _call(lib, "fa_mla_indexer_logits_paged",
+          (q_idx.data_ptr(), w.data_ptr(), k_idx_pages.data_ptr(), logits.data_ptr(), cu_seqlens_q.data_ptr(), block_table.data_ptr(),
+           seqlens_k.data_ptr(), B, Hi, T, int(max_seqlen_q), Di, P, num_pages, mp, q_idx.stride(0), q_idx.stride(1), wrs,
+           k_idx_pages.stride(0), k_idx_pages.stride(1), block_table.stride(0), logits.stride(0) if T > 1 else logits.shape[1],
+           _TORCH2FA[q_idx.dtype]), q_idx.device, stream)
+    return logits
+
+
+def mla_indexer_select(logits: torch.Tensor, cu_seqlens_q: torch.Tensor, block_table: torch.Tensor, seqlens_k: torch.Tensor, topk: int,
+                       max_seqlen_q: int, page_size: int, num_pages: int, indices: Optional[torch.Tensor] = None,
+                       index_counts: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 logits -> (indices int32 [total_q, >= topk], index_counts int32 [total_q]) as flash_attention_mla_decode_sparse takes them
+    (include/fa_mi355.h fa_mla_indexer_select): per token the min(topk, v) best visible keys under (logit descending, position
+    ascending), written in ascending position as pool slots, -1 under a page entry outside the pool. Entries behind the count are not
+    written (allocated UNINITIALISED if `indices` is None)."""
+    lib = load_library()
+    if logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("logits must be an fp32 [total_q, >= max_pages_per_seq * P] device tensor with a unit last stride")
+    T = logits.shape[0]
+    B = _tables("mla_indexer_select", cu_seqlens_q, "cu_seqlens_q", block_table, seqlens_k)
+    mp = block_table.shape[1]
+    logits = _indexer_logits_buffer(logits, T, int(page_size) * mp, logits.device)
+    indices, index_counts, istride = _indexer_lists(indices, index_counts, T, int(topk), logits.device)
+    _call(lib, "fa_mla_indexer_select",
+          (logits.data_ptr(), indices.data_ptr(), index_counts.data_ptr(), cu_seqlens_q.data_ptr(), block_table.data_ptr(),
+           seqlens_k.data_ptr(), B, T, int(max_seqlen_q), int(topk), int(page_size), int(num_pages), mp,
+           logits.stride(0) if T > 1 else logits.shape[1], istride, block_table.stride(0)), logits.device, stream)
+    return indices, index_counts
+
+
+def flash_attention_mla_indexer_topk(q_idx: torch.Tensor, w: torch.Tensor, k_idx_pages: torch.Tensor, cu_seqlens_q: torch.Tensor,
+                                     block_table: torch.Tensor, seqlens_k: torch.Tensor, topk: int, max_seqlen_q: int,
+                                     indices: Optional[torch.Tensor] = None, index_counts: Optional[torch.Tensor] = None,
+                                     workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The MLA indexer (include/fa_mi355.h fa_mla_indexer_topk_paged): mla_indexer_logits, then mla_indexer_select, on a workspace that
+    holds the logits. q_idx [total_q,Hi,128] f16 / bf16 (Hi 32 or 64), w [total_q,Hi] fp32, k_idx_pages [num_pages,P,128] like q_idx;
+    the three tables are flash_attention_varlen_paged's, device tensors the host never reads. Returns (indices, index_counts), which
+    flash_attention_mla_decode_sparse takes as they are. `workspace`: a uint8 device tensor of at least
+    mla_indexer_workspace_bytes(total_q, P, max_pages_per_seq) bytes (allocated here if None)."""
+    lib = load_library()
+    T, Hi, Di, wrs = _indexer_inputs("flash_attention_mla_indexer_topk", q_idx, w, k_idx_pages)
+    B = _tables("flash_attention_mla_indexer_topk", cu_seqlens_q, "cu_seqlens_q", block_table, seqlens_k)
+    num_pages, P = k_idx_pages.shape[0], k_idx_pages.shape[1]
+    mp = block_table.shape[1]
+    indices, index_counts, istride = _indexer_lists(indices, index_counts, T, int(topk), q_idx.device)
+    ws = _workspace(workspace, mla_indexer_workspace_bytes(T, P, mp), q_idx.device)
+    _call(lib, "fa_mla_indexer_topk_paged",
+          (q_idx.data_ptr(), w.data_ptr(), k_idx_pages.data_ptr(), indices.data_ptr(), index_counts.data_ptr(), cu_seqlens_q.data_ptr(),
+           block_table.data_ptr(), seqlens_k.data_ptr(), B, Hi, T, int(max_seqlen_q), Di, int(topk), P, num_pages, mp, q_idx.stride(0),
+           q_idx.stride(1), wrs, k_idx_pages.stride(0), k_idx_pages.stride(1), block_table.stride(0), istride,
+           _TORCH2FA[q_idx.dtype], ws.data_ptr(), ws.numel()), q_idx.device, stream)
+    return indices, index_counts
+
+
 def varlen_supported(dtype: str, D: int) -> bool:
     return bool(load_library().fa_fwd_varlen_supported(DTYPES[dtype], D))
 

@@ -997,6 +997,80 @@ long long fa_fwd_mla_decode_sparse_kv8_workspace_bytes(int T, int Hq, int Dv, in
 int fa_fwd_mla_decode_sparse_kv8_supported(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int page_size);
 
 /*
+ * The MLA indexer: fa_mla_indexer_logits_paged, fa_mla_indexer_select and fa_mla_indexer_topk_paged PRODUCE the lists that
+ * fa_fwd_mla_decode_sparse and fa_fwd_mla_decode_sparse_kv8 consume (DeepSeek-V3.2-style sparse attention: a light indexer scores
+ * every visible key of a token and the latent attention runs over the topk best).
+ * q_idx is the packed index query [total_q, Hi, 128], f16 or bf16, under row / head ELEMENT strides (multiples of 8, at least 128, base
+ * 16-byte aligned); w the per-token head weights [total_q, Hi] fp32 under a row stride >= Hi; k_idx_pages the index-key pool
+ * [num_pages, P, 128] of q_idx's type under page / row element strides (multiples of 8, at least 128, base 16-byte aligned). The pool
+ * may exceed 4 GiB, one page stays below 2 GiB. cu_seqlens_q, block_table, seqlens_k, B, total_q, max_seqlen_q and max_pages_per_seq
+ * behave exactly as in fa_fwd_varlen_paged: DEVICE tables the host never reads, entries of cu_seqlens_q clamped to [0, total_q], a
+ * non-increasing pair is length 0, Lq_b clamped to max_seqlen_q, L_b = seqlens_k[b] clamped to [0, max_pages_per_seq * P], key j < L_b
+ * is row j % P of page block_table[b][j / P], and a page entry outside [0, num_pages) reads as rows of zeros and touches nothing.
+ * VISIBILITY is that call's bottom-right causal rule and nothing else: token i of sequence b sees the keys j < v,
+ *     v = clamp(L_b - Lq_b + i + 1, 0, L_b)
+ * (a decode step: Lq_b = 1; a chunked-prefill step: the chunk is already appended). For a token t and a visible key j
+ *     logit[t][j] = sum_h  w[t][h] * max(0, q_idx[t, h, :] . k_idx(b, j)[:])
+ * accumulated in fp32 from the matrix core onwards. There is NO scale inside the call: the caller folds the softmax scale and the
+ * heads' own scales into w, as the models do. With exact inputs (every partial sum an integer below 2^24) the logits are exact; in
+ * general each lies within 2^-15 * sum_h |w_h| sum_d |q_hd| |k_d| of the exact value.
+ *
+ * 1. fa_mla_indexer_logits_paged writes logit[t][j], j < v, into the caller's fp32 [total_q, logits_stride] buffer (4-byte aligned,
+ *    logits_stride >= max_pages_per_seq * P) and NOTHING ELSE: columns j >= v of a row and rows of tokens nobody owns keep their bytes.
+ * 2. fa_mla_indexer_select turns such a buffer into the sparse decode's input: indices int32 [total_q, indices_stride] (the stride
+ *    at least topk and a multiple of 4, the base 16-byte aligned -- the sparse call's rules) and index_counts int32 [total_q].
+ *    index_counts[t] = min(topk, v). The selected keys are the first min(topk, v) under the total order (logit descending, position
+ *    ascending), -0 counted as +0; they are written in ASCENDING POSITION, each as its slot block_table[b][j / P] * P + j % P, or -1
+ *    where that page entry lies outside the pool (the sparse decode reads such an entry as a row of zeros). Nothing at or behind
+ *    column v of a logits row is read, nothing at or behind index_counts[t] of an indices row is written, tokens nobody owns are not
+ *    written. When v <= topk the logits are not read at all and the list is positions 0 .. v - 1. For any input bits, NaN included,
+ *    a list holds distinct visible positions; the rank of a NaN is unspecified. num_pages * P is at most 2^30 slots.
+ * 3. fa_mla_indexer_topk_paged runs 1, then 2, on a caller's workspace of fa_mla_indexer_topk_paged_workspace_bytes(total_q, P,
+ *    max_pages_per_seq) bytes that holds the logits under a row stride of max_pages_per_seq * P (0: an illegal size). Its outputs are
+ *    BIT-IDENTICAL to calling 1 and 2 by hand; they do not depend on the workspace's prior contents.
+ * All three are asynchronous on hip_stream and allocate nothing; their grids depend on host scalars alone (B, max_seqlen_q, P,
+ * max_pages_per_seq), so one captured graph serves every step; results are bitwise reproducible (no global atomics).
+ * f16 / bf16, Hi = 32 | 64, Di = 128, P in {16, 32, 64, 128, 256}, topk >= 1: anything else FA_ERR_UNSUPPORTED with a message that names
+ * what was given. Every rule shared with fa_fwd_varlen_paged (null pointers, sizes < 1, max_seqlen_q > total_q, the q and page
+ * strides, block_table_stride, alignment, a capacity above 2^30) or with fa_fwd_mla_decode_sparse (indices_stride, the alignment of
+ * indices and index_counts, the slot count) carries that call's status and its text after the function name. Of these calls' own, each
+ * FA_ERR_INVALID_ARG before any launch: w or logits not 4-byte aligned, w_row_stride < Hi, logits_stride too small, a workspace too
+ * small, a grid that does not fit an int.
+ * How it runs (csrc/fa_mla_indexer_kernel.hip). Logits: four waves per (sequence, block of 1 / 2 / 4 tokens,
+ * key chunk); heads are the rows and keys the columns of a v_mfma_f32_16x16x32 score tile, so the head sum is in-lane v_max / v_fma
+ * over the accumulators plus two cross-lane adds; a token's Hi x 128 query stays in registers; every 64-key tile is staged once into
+ * LDS by LDS-DMA under per-page range-checked descriptors, double-buffered, one barrier per tile. The chunk length is
+ * fa_mla_indexer_chunk_keys(B, max_seqlen_q, P, max_pages_per_seq) keys (0: illegal scalars): as few chunks as give 1024 items, none
+ * shorter than 8 tiles where the capacity has them. Select: one workgroup per token, a most-significant-byte-first radix select on the
+ * order-preserving integer image of the logit (four 256-bin LDS histograms), then one ordered emission pass under a workgroup scan.
+ * Not here: e4m3 index keys with per-row scales; a fused logits-and-select kernel without the buffer; non-paged keys; a window or any
+ * mask other than the causal rule; Di other than 128; the indexer's projections and rotary. No existing call is rerouted.
+ */
+int fa_mla_indexer_logits_paged(const void *q_idx, const float *w, const void *k_idx_pages, float *logits,
+                                const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                                int B, int Hi, int total_q, int max_seqlen_q, int Di,
+                                int page_size, int num_pages, int max_pages_per_seq,
+                                long long q_row_stride, long long q_head_stride, long long w_row_stride,
+                                long long k_page_stride, long long k_row_stride,
+                                long long block_table_stride, long long logits_stride, int dtype, void *hip_stream);
+int fa_mla_indexer_select(const float *logits, int *indices, int *index_counts,
+                          const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                          int B, int total_q, int max_seqlen_q, int topk,
+                          int page_size, int num_pages, int max_pages_per_seq,
+                          long long logits_stride, long long indices_stride, long long block_table_stride, void *hip_stream);
+int fa_mla_indexer_topk_paged(const void *q_idx, const float *w, const void *k_idx_pages, int *indices, int *index_counts,
+                              const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                              int B, int Hi, int total_q, int max_seqlen_q, int Di, int topk,
+                              int page_size, int num_pages, int max_pages_per_seq,
+                              long long q_row_stride, long long q_head_stride, long long w_row_stride,
+                              long long k_page_stride, long long k_row_stride,
+                              long long block_table_stride, long long indices_stride, int dtype,
+                              void *workspace, long long workspace_bytes, void *hip_stream);
+long long fa_mla_indexer_topk_paged_workspace_bytes(int total_q, int page_size, int max_pages_per_seq);
+int fa_mla_indexer_chunk_keys(int B, int max_seqlen_q, int page_size, int max_pages_per_seq);
+int fa_mla_indexer_supported(int dtype, int Hi, int Di, int page_size);   /* f16 | bf16, 32 | 64, 128, 16 .. 256 */
+
+/*
  * Multi-head latent attention (prefill): fa_fwd_varlen_mla is the NON-absorbed form of the same layer, as serving engines run its
  * prefill: the latent rows are up-projected to per-head keys and values, and ordinary multi-head attention runs over packed sequences
  * with a query / key head dim of Dqk = 192 (128 "nope" + 64 rotary) and a value head dim of Dv = 128. Per sequence the operator is
