@@ -43,6 +43,7 @@ from .ops import (  # noqa: F401
     mla_decode_sparse_supported,
     mla_decode_sparse_workspace_bytes,
     mla_indexer_chunk_keys,
+    mla_indexer_kv8_supported,
     mla_indexer_logits,
     mla_indexer_select,
     mla_indexer_supported,

@@ -941,6 +941,14 @@ int fa_fwd_mla_decode_sparse_kv8(const void *q, const void *kv_pages, void *o, f
 int fa_mla_indexer_supported(int dtype, int Hi, int Di, int page_size) {
   return (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) && (Hi == 32 || Hi == 64) && Di == 128 && fa::page_size_ok(page_size);
 }
+// The two modes of the logits stage. MLA_INDEXER_WIDE: f16 / bf16, q_idx and the pool alike (fa_mla_indexer_kernel.hip).
+// MLA_INDEXER_KV8: e4m3 queries on an e4m3 pool with a scale per key (fa_mla_indexer_kv8_kernel.hip); `dtype` is the queries' and
+// kv_dtype the pool's (the other mode: both are `dtype`). The dtype-pair rule and the strides' unit (bytes, multiples of 16) are all that
+// differ in the shared check; the scales' own rules are mla_indexer_scales_ok.
+enum { MLA_INDEXER_WIDE = 0, MLA_INDEXER_KV8 = 1 };
+int fa_mla_indexer_kv8_supported(int q_dtype, int kv_dtype, int Hi, int Di, int page_size) {
+  return q_dtype == FA_DTYPE_FP8_E4M3 && kv_dtype == FA_DTYPE_FP8_E4M3 && (Hi == 32 || Hi == 64) && Di == 128 && fa::page_size_ok(page_size);
+}
 static bool mla_indexer_scalars_ok(int page_size, int max_pages_per_seq) {
   return fa::page_size_ok(page_size) && max_pages_per_seq >= 1 && (long long)page_size * max_pages_per_seq <= (1 << 30);
 }
@@ -970,20 +978,26 @@ static int mla_indexer_logits_buffer_ok(const char *fn, const void *logits, long
                 (long long)page_size * max_pages_per_seq);
   return FA_OK;
 }
-static int mla_indexer_logits_check(const char *fn, fa::MlaIndexerParams &p, const void *q_idx, const float *w, const void *k_idx_pages,
+static int mla_indexer_logits_check(const char *fn, int mode, fa::MlaIndexerParams &p, const void *q_idx, const float *w, const void *k_idx_pages,
                                     float *logits, const int *cu_seqlens_q, const int *block_table, const int *seqlens_k, int B, int Hi,
                                     int total_q, int max_seqlen_q, int Di, int page_size, int num_pages, int max_pages_per_seq,
                                     long long q_row_stride, long long q_head_stride, long long w_row_stride, long long k_page_stride,
-                                    long long k_row_stride, long long block_table_stride, long long logits_stride, int dtype) {
+                                    long long k_row_stride, long long block_table_stride, long long logits_stride, int dtype,
+                                    int kv_dtype) {
   TRY(nonnull(fn, {q_idx, w, k_idx_pages, logits, cu_seqlens_q, block_table, seqlens_k}));
   TRY(positive(fn, {B, Hi, total_q, max_seqlen_q, Di, page_size, num_pages, max_pages_per_seq}));
-  if (!fa_mla_indexer_supported(dtype, Hi, Di, page_size))
+  if (mode == MLA_INDEXER_KV8) {
+    if (!fa_mla_indexer_kv8_supported(dtype, kv_dtype, Hi, Di, page_size))
+      return fail(FA_ERR_UNSUPPORTED, "%s: needs e4m3 index queries on an e4m3 pool, Hi = 32 | 64, Di = 128 and a page size of 16, 32, 64, "
+                  "128 or 256; got q=%s kv=%s Hi=%d Di=%d page_size=%d", fn, fa_dtype_name(dtype), fa_dtype_name(kv_dtype), Hi, Di, page_size);
+  } else if (!fa_mla_indexer_supported(dtype, Hi, Di, page_size))
     return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 (q_idx and the pool alike), Hi = 32 | 64, Di = 128 and a page size of 16, 32, 64, "
                 "128 or 256; got dtype=%s Hi=%d Di=%d page_size=%d", fn, fa_dtype_name(dtype), Hi, Di, page_size);
   if (max_seqlen_q > total_q)  // (in fa_fwd_varlen_paged's place: in front of the strides)
     return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen_q=%d exceeds the token count %d", fn, max_seqlen_q, total_q);
+  // (e4m3: strides in elements = bytes, multiples of 16, a page counted in bytes of 1 -- fa_fwd_varlen_paged_kv8's rule)
   TRY(varlen_strides_ok(fn, "", Di, q_row_stride, q_head_stride, stride_mult(dtype)));
-  TRY(page_pool_ok(fn, Di, page_size, max_pages_per_seq, k_page_stride, k_row_stride, k_row_stride, block_table_stride, dtype, block_table, seqlens_k));
+  TRY(page_pool_ok(fn, Di, page_size, max_pages_per_seq, k_page_stride, k_row_stride, k_row_stride, block_table_stride, kv_dtype, block_table, seqlens_k));
   TRY(aligned16(fn, "tensors", {q_idx, k_idx_pages}));
   if ((uintptr_t)cu_seqlens_q & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_q must be int32-aligned", fn);
   if ((uintptr_t)w & 3) return fail(FA_ERR_INVALID_ARG, "%s: w must be fp32-aligned", fn);
@@ -1002,6 +1016,14 @@ static int mla_indexer_logits_check(const char *fn, fa::MlaIndexerParams &p, con
   p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
   p.lp = log2_of(page_size);
   if ((long long)B * p.nblk > 0x7fffffffLL / p.nchunks) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  return FA_OK;
+}
+// the e4m3 calls' own rules: the per-key scales
+static int mla_indexer_scales_ok(const char *fn, const float *k_scale_pages, long long k_scale_page_stride, int page_size) {
+  TRY(nonnull(fn, {k_scale_pages}));
+  if ((uintptr_t)k_scale_pages & 3) return fail(FA_ERR_INVALID_ARG, "%s: k_scale_pages must be fp32-aligned", fn);
+  if (k_scale_page_stride < page_size)
+    return fail(FA_ERR_INVALID_ARG, "%s: k_scale_page_stride=%lld < page_size=%d", fn, k_scale_page_stride, page_size);
   return FA_OK;
 }
 static int mla_indexer_select_check(const char *fn, fa::MlaIndexerSelectParams &p, const float *logits, int *indices, int *index_counts,
@@ -1037,9 +1059,9 @@ int fa_mla_indexer_logits_paged(const void *q_idx, const float *w, const void *k
   const char *fn = "fa_mla_indexer_logits_paged";
   g_err[0] = 0;
   fa::MlaIndexerParams p;
-  TRY(mla_indexer_logits_check(fn, p, q_idx, w, k_idx_pages, logits, cu_seqlens_q, block_table, seqlens_k, B, Hi, total_q, max_seqlen_q, Di,
-                               page_size, num_pages, max_pages_per_seq, q_row_stride, q_head_stride, w_row_stride, k_page_stride,
-                               k_row_stride, block_table_stride, logits_stride, dtype));
+  TRY(mla_indexer_logits_check(fn, MLA_INDEXER_WIDE, p, q_idx, w, k_idx_pages, logits, cu_seqlens_q, block_table, seqlens_k, B, Hi, total_q,
+                               max_seqlen_q, Di, page_size, num_pages, max_pages_per_seq, q_row_stride, q_head_stride, w_row_stride,
+                               k_page_stride, k_row_stride, block_table_stride, logits_stride, dtype, dtype));
   return launched(fn, fa::launch_mla_indexer_logits(p, Hi, dtype, (hipStream_t)hip_stream));
 }
 int fa_mla_indexer_select(const float *logits, int *indices, int *index_counts, const int *cu_seqlens_q, const int *block_table,
@@ -1065,14 +1087,55 @@ int fa_mla_indexer_topk_paged(const void *q_idx, const float *w, const void *k_i
   const long long cap = (long long)page_size * max_pages_per_seq;  // the workspace is the logits buffer under a row stride of the capacity
   fa::MlaIndexerParams pl;
   fa::MlaIndexerSelectParams ps;
-  TRY(mla_indexer_logits_check(fn, pl, q_idx, w, k_idx_pages, (float *)workspace, cu_seqlens_q, block_table, seqlens_k, B, Hi, total_q,
-                               max_seqlen_q, Di, page_size, num_pages, max_pages_per_seq, q_row_stride, q_head_stride, w_row_stride,
-                               k_page_stride, k_row_stride, block_table_stride, cap, dtype));
+  TRY(mla_indexer_logits_check(fn, MLA_INDEXER_WIDE, pl, q_idx, w, k_idx_pages, (float *)workspace, cu_seqlens_q, block_table, seqlens_k, B, Hi,
+                               total_q, max_seqlen_q, Di, page_size, num_pages, max_pages_per_seq, q_row_stride, q_head_stride, w_row_stride,
+                               k_page_stride, k_row_stride, block_table_stride, cap, dtype, dtype));
   TRY(mla_indexer_select_check(fn, ps, (const float *)workspace, indices, index_counts, cu_seqlens_q, block_table, seqlens_k, B, total_q,
                                max_seqlen_q, topk, page_size, num_pages, max_pages_per_seq, cap, indices_stride, block_table_stride));
   TRY(workspace_fits(fn, workspace_bytes, fa_mla_indexer_topk_paged_workspace_bytes(total_q, page_size, max_pages_per_seq),
                      "fa_mla_indexer_topk_paged_workspace_bytes"));
   TRY(launched(fn, fa::launch_mla_indexer_logits(pl, Hi, dtype, (hipStream_t)hip_stream)));
+  return launched(fn, fa::launch_mla_indexer_select(ps, (hipStream_t)hip_stream));
+}
+int fa_mla_indexer_logits_paged_kv8(const void *q_idx, const float *w, const void *k_idx_pages, const float *k_scale_pages, float *logits,
+                                    const int *cu_seqlens_q, const int *block_table, const int *seqlens_k, int B, int Hi, int total_q,
+                                    int max_seqlen_q, int Di, int page_size, int num_pages, int max_pages_per_seq, long long q_row_stride,
+                                    long long q_head_stride, long long w_row_stride, long long k_page_stride, long long k_row_stride,
+                                    long long k_scale_page_stride, long long block_table_stride, long long logits_stride, int q_dtype,
+                                    int kv_dtype, void *hip_stream) {
+  const char *fn = "fa_mla_indexer_logits_paged_kv8";
+  g_err[0] = 0;
+  fa::MlaIndexerKv8Params pp;
+  TRY(mla_indexer_logits_check(fn, MLA_INDEXER_KV8, pp.p, q_idx, w, k_idx_pages, logits, cu_seqlens_q, block_table, seqlens_k, B, Hi, total_q,
+                               max_seqlen_q, Di, page_size, num_pages, max_pages_per_seq, q_row_stride, q_head_stride, w_row_stride,
+                               k_page_stride, k_row_stride, block_table_stride, logits_stride, q_dtype, kv_dtype));
+  TRY(mla_indexer_scales_ok(fn, k_scale_pages, k_scale_page_stride, page_size));
+  pp.k_scale = k_scale_pages; pp.scale_page_stride = k_scale_page_stride;
+  return launched(fn, fa::launch_mla_indexer_logits_kv8(pp, Hi, (hipStream_t)hip_stream));
+}
+int fa_mla_indexer_topk_paged_kv8(const void *q_idx, const float *w, const void *k_idx_pages, const float *k_scale_pages, int *indices,
+                                  int *index_counts, const int *cu_seqlens_q, const int *block_table, const int *seqlens_k, int B, int Hi,
+                                  int total_q, int max_seqlen_q, int Di, int topk, int page_size, int num_pages, int max_pages_per_seq,
+                                  long long q_row_stride, long long q_head_stride, long long w_row_stride, long long k_page_stride,
+                                  long long k_row_stride, long long k_scale_page_stride, long long block_table_stride,
+                                  long long indices_stride, int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes,
+                                  void *hip_stream) {
+  const char *fn = "fa_mla_indexer_topk_paged_kv8";
+  g_err[0] = 0;
+  TRY(nonnull(fn, {workspace}));
+  const long long cap = (long long)page_size * max_pages_per_seq;  // the workspace is the logits buffer under a row stride of the capacity
+  fa::MlaIndexerKv8Params pl;
+  fa::MlaIndexerSelectParams ps;
+  TRY(mla_indexer_logits_check(fn, MLA_INDEXER_KV8, pl.p, q_idx, w, k_idx_pages, (float *)workspace, cu_seqlens_q, block_table, seqlens_k, B, Hi,
+                               total_q, max_seqlen_q, Di, page_size, num_pages, max_pages_per_seq, q_row_stride, q_head_stride, w_row_stride,
+                               k_page_stride, k_row_stride, block_table_stride, cap, q_dtype, kv_dtype));
+  TRY(mla_indexer_scales_ok(fn, k_scale_pages, k_scale_page_stride, page_size));
+  pl.k_scale = k_scale_pages; pl.scale_page_stride = k_scale_page_stride;
+  TRY(mla_indexer_select_check(fn, ps, (const float *)workspace, indices, index_counts, cu_seqlens_q, block_table, seqlens_k, B, total_q,
+                               max_seqlen_q, topk, page_size, num_pages, max_pages_per_seq, cap, indices_stride, block_table_stride));
+  TRY(workspace_fits(fn, workspace_bytes, fa_mla_indexer_topk_paged_workspace_bytes(total_q, page_size, max_pages_per_seq),
+                     "fa_mla_indexer_topk_paged_workspace_bytes"));
+  TRY(launched(fn, fa::launch_mla_indexer_logits_kv8(pl, Hi, (hipStream_t)hip_stream)));
   return launched(fn, fa::launch_mla_indexer_select(ps, (hipStream_t)hip_stream));
 }
 

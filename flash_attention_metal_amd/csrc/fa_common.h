@@ -251,6 +251,13 @@ struct MlaIndexerParams {
   int bt_stride, num_pages, max_pages;
   int lp;  // log2 of the page size (16 .. 256)
 };
+// one fa_mla_indexer_logits_paged_kv8 call (csrc/fa_mla_indexer_kv8_kernel.hip): the same items and tables; q and k are e4m3, so q_rs,
+// q_hs, page_stride and row_stride count BYTES; key j of a page has its fp32 scale at k_scale[page * scale_page_stride + j % P]
+struct MlaIndexerKv8Params {
+  MlaIndexerParams p;
+  const float *k_scale;
+  long long scale_page_stride;  // floats
+};
 // one fa_mla_indexer_select call: fp32 logits -> the sparse decode's slot lists and counts; one workgroup per (sequence, token)
 struct MlaIndexerSelectParams {
   const float *logits;
@@ -362,6 +369,9 @@ int mla_indexer_token_block(int max_seqlen_q);
 int mla_indexer_chunk_tiles(int B, int max_seqlen_q, int page_size, int max_pages_per_seq);
 hipError_t launch_mla_indexer_logits(const MlaIndexerParams &p, int Hi, int dtype, hipStream_t s);
 hipError_t launch_mla_indexer_select(const MlaIndexerSelectParams &p, hipStream_t s);
+// fa_mla_indexer_logits_paged_kv8 (csrc/fa_mla_indexer_kv8_kernel.hip): the logits over e4m3 queries and keys with a scale per key, the
+// same grid
+hipError_t launch_mla_indexer_logits_kv8(const MlaIndexerKv8Params &pp, int Hi, hipStream_t s);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);

@@ -41,7 +41,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "fa_mfma_common.h"
+#include "fa_mla_indexer_common.h"  // IdxSeq, idx_seq, idx_visible
 
 namespace fa {
 
@@ -69,17 +69,6 @@ int mla_indexer_chunk_tiles(int B, int max_seqlen_q, int page_size, int max_page
   const long long nch = std::min(want, most);
   return (int)((nT + nch - 1) / nch);
 }
-
-// sequence b's tokens and keys, under fa_fwd_varlen_paged's clamps
-struct IdxSeq {
-  int sq, Lq, L;
-};
-__device__ __forceinline__ IdxSeq idx_seq(const int *cu_q, const int *seqlens, int b, int total_q, int max_q, int cap) {
-  const int s = min(max(__builtin_amdgcn_readfirstlane(cu_q[b]), 0), total_q), e = min(max(__builtin_amdgcn_readfirstlane(cu_q[b + 1]), 0), total_q);
-  return {s, min(max(e - s, 0), max_q), min(max(__builtin_amdgcn_readfirstlane(seqlens[b]), 0), cap)};
-}
-// keys token i of the sequence sees: the bottom-right causal rule
-__device__ __forceinline__ int idx_visible(const IdxSeq &q, int i) { return min(max(q.L - q.Lq + i + 1, 0), q.L); }
 
 template <typename Tag, int HI, int TB>
 __global__ __launch_bounds__(64 * IDX_NW) void mla_indexer_logits_kernel(MlaIndexerParams p) {

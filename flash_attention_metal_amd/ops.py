@@ -546,6 +546,10 @@ def mla_indexer_supported(dtype: str, Hi: int, Di: int, page_size: int) -> bool:
     return bool(load_library().fa_mla_indexer_supported(DTYPES[dtype], Hi, Di, page_size))
 
 
+def mla_indexer_kv8_supported(q_dtype: str, kv_dtype: str, Hi: int, Di: int, page_size: int) -> bool:
+    return bool(load_library().fa_mla_indexer_kv8_supported(DTYPES[q_dtype], DTYPES[kv_dtype], Hi, Di, page_size))
+
+
 def mla_indexer_workspace_bytes(total_q: int, page_size: int, max_pages_per_seq: int) -> int:
     return int(load_library().fa_mla_indexer_topk_paged_workspace_bytes(total_q, page_size, max_pages_per_seq))
 
@@ -555,12 +559,21 @@ def mla_indexer_chunk_keys(B: int, max_seqlen_q: int, page_size: int, max_pages_
     return int(load_library().fa_mla_indexer_chunk_keys(B, max_seqlen_q, page_size, max_pages_per_seq))
 
 
-def _indexer_inputs(entry: str, q_idx: torch.Tensor, w: torch.Tensor, k_idx_pages: torch.Tensor):
+def _indexer_inputs(entry: str, q_idx: torch.Tensor, w: torch.Tensor, k_idx_pages: torch.Tensor, k_scale_pages: Optional[torch.Tensor] = None):
+    """Shapes, devices and dtypes of either route: 16-bit tensors without scales (the fa_mla_indexer_* calls), or float8_e4m3fn q_idx and
+    pool with fp32 k_scale_pages [num_pages, P] (the *_kv8 calls). Anything between raises before the library is called."""
     if q_idx.dim() != 3 or w.dim() != 2 or k_idx_pages.dim() != 3:
         raise ValueError("q_idx [total_q,Hi,128], w [total_q,Hi] fp32, k_idx_pages [num_pages,P,128]")
     if not all(t.is_cuda and t.device == q_idx.device for t in (w, k_idx_pages)):
         raise ValueError(f"{entry} needs q_idx, w and the pool on one device: there is no CPU path")
-    if q_idx.dtype not in (torch.float16, torch.bfloat16) or k_idx_pages.dtype != q_idx.dtype or w.dtype != torch.float32:
+    if k_scale_pages is not None or (_FP8 is not None and _FP8 in (q_idx.dtype, k_idx_pages.dtype)):
+        if _FP8 is None or q_idx.dtype != _FP8 or k_idx_pages.dtype != _FP8 or k_scale_pages is None or w.dtype != torch.float32:
+            raise ValueError(f"unsupported / mixed dtypes {q_idx.dtype} {k_idx_pages.dtype} {w.dtype}: k_scale_pages goes with float8_e4m3fn "
+                             "q_idx and pool, both of them, and such tensors need k_scale_pages (w fp32)")
+        if (not k_scale_pages.is_cuda or k_scale_pages.device != q_idx.device or k_scale_pages.dtype != torch.float32
+                or k_scale_pages.shape != k_idx_pages.shape[:2] or k_scale_pages.stride(1) != 1):
+            raise ValueError("k_scale_pages must be an fp32 [num_pages, P] tensor on q_idx's device with a unit last stride")
+    elif q_idx.dtype not in (torch.float16, torch.bfloat16) or k_idx_pages.dtype != q_idx.dtype or w.dtype != torch.float32:
         raise ValueError(f"unsupported / mixed dtypes {q_idx.dtype} {k_idx_pages.dtype} {w.dtype} (f16 or bf16, q_idx and the pool alike; w fp32)")
     T, Hi, Di = q_idx.shape
     if w.shape != (T, Hi) or k_idx_pages.shape[2] != Di or q_idx.stride(2) != 1 or w.stride(1) != 1 or k_idx_pages.stride(2) != 1:
@@ -593,16 +606,26 @@ def _indexer_lists(indices, index_counts, T: int, topk: int, device: torch.devic
 
 def mla_indexer_logits(q_idx: torch.Tensor, w: torch.Tensor, k_idx_pages: torch.Tensor, cu_seqlens_q: torch.Tensor, block_table: torch.Tensor,
                        seqlens_k: torch.Tensor, max_seqlen_q: int, logits: Optional[torch.Tensor] = None,
-                       stream: Optional[int] = None) -> torch.Tensor:
+                       stream: Optional[int] = None, k_scale_pages: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The indexer's logits (include/fa_mi355.h fa_mla_indexer_logits_paged): logits[t, j] = sum_h w[t, h] relu(q_idx[t, h] . k_idx(b, j))
     for the keys j < v token t sees under the bottom-right causal rule, fp32, into `logits` [total_q, >= max_pages_per_seq * P] (allocated
-    UNINITIALISED if None: columns at or behind v and rows of tokens nobody owns are not written). No scale inside: fold it into w."""
+    UNINITIALISED if None: columns at or behind v and rows of tokens nobody owns are not written). No scale inside: fold it into w.
+    float8_e4m3fn q_idx and pool with fp32 `k_scale_pages` [num_pages, P] (any view with a unit last stride, the tail of a packed
+    132-byte-per-key page included) go to fa_mla_indexer_logits_paged_kv8: the same sum times the key's scale."""
     lib = load_library()
-    T, Hi, Di, wrs = _indexer_inputs("mla_indexer_logits", q_idx, w, k_idx_pages)
+    T, Hi, Di, wrs = _indexer_inputs("mla_indexer_logits", q_idx, w, k_idx_pages, k_scale_pages)
     B = _tables("mla_indexer_logits", cu_seqlens_q, "cu_seqlens_q", block_table, seqlens_k)
     num_pages, P = k_idx_pages.shape[0], k_idx_pages.shape[1]
     mp = block_table.shape[1]
     logits = _indexer_logits_buffer(logits, T, P * mp, q_idx.device)
+    if k_scale_pages is not None:
+        _call(lib, "fa_mla_indexer_logits_paged_kv8",
+              (q_idx.data_ptr(), w.data_ptr(), k_idx_pages.data_ptr(), k_scale_pages.data_ptr(), logits.data_ptr(), cu_seqlens_q.data_ptr(),
+               block_table.data_ptr(), seqlens_k.data_ptr(), B, Hi, T, int(max_seqlen_q), Di, P, num_pages, mp, q_idx.stride(0),
+               q_idx.stride(1), wrs, k_idx_pages.stride(0), k_idx_pages.stride(1), k_scale_pages.stride(0) if num_pages > 1 else P,
+               block_table.stride(0), logits.stride(0) if T > 1 else logits.shape[1], _TORCH2FA[q_idx.dtype], _TORCH2FA[k_idx_pages.dtype]),
+              q_idx.device, stream)
+        return logits
     _call(lib, "fa_mla_indexer_logits_paged",
           (q_idx.data_ptr(), w.data_ptr(), k_idx_pages.data_ptr(), logits.data_ptr(), cu_seqlens_q.data_ptr(), block_table.data_ptr(),
            seqlens_k.data_ptr(), B, Hi, T, int(max_seqlen_q), Di, P, num_pages, mp, q_idx.stride(0), q_idx.stride(1), wrs,
@@ -636,19 +659,29 @@ def mla_indexer_select(logits: torch.Tensor, cu_seqlens_q: torch.Tensor, block_t
 def flash_attention_mla_indexer_topk(q_idx: torch.Tensor, w: torch.Tensor, k_idx_pages: torch.Tensor, cu_seqlens_q: torch.Tensor,
                                      block_table: torch.Tensor, seqlens_k: torch.Tensor, topk: int, max_seqlen_q: int,
                                      indices: Optional[torch.Tensor] = None, index_counts: Optional[torch.Tensor] = None,
-                                     workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                                     workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None,
+                                     k_scale_pages: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The MLA indexer (include/fa_mi355.h fa_mla_indexer_topk_paged): mla_indexer_logits, then mla_indexer_select, on a workspace that
     holds the logits. q_idx [total_q,Hi,128] f16 / bf16 (Hi 32 or 64), w [total_q,Hi] fp32, k_idx_pages [num_pages,P,128] like q_idx;
     the three tables are flash_attention_varlen_paged's, device tensors the host never reads. Returns (indices, index_counts), which
     flash_attention_mla_decode_sparse takes as they are. `workspace`: a uint8 device tensor of at least
-    mla_indexer_workspace_bytes(total_q, P, max_pages_per_seq) bytes (allocated here if None)."""
+    mla_indexer_workspace_bytes(total_q, P, max_pages_per_seq) bytes (allocated here if None). float8_e4m3fn q_idx and pool with fp32
+    `k_scale_pages` go to fa_mla_indexer_topk_paged_kv8, as in mla_indexer_logits."""
     lib = load_library()
-    T, Hi, Di, wrs = _indexer_inputs("flash_attention_mla_indexer_topk", q_idx, w, k_idx_pages)
+    T, Hi, Di, wrs = _indexer_inputs("flash_attention_mla_indexer_topk", q_idx, w, k_idx_pages, k_scale_pages)
     B = _tables("flash_attention_mla_indexer_topk", cu_seqlens_q, "cu_seqlens_q", block_table, seqlens_k)
     num_pages, P = k_idx_pages.shape[0], k_idx_pages.shape[1]
     mp = block_table.shape[1]
     indices, index_counts, istride = _indexer_lists(indices, index_counts, T, int(topk), q_idx.device)
     ws = _workspace(workspace, mla_indexer_workspace_bytes(T, P, mp), q_idx.device)
+    if k_scale_pages is not None:
+        _call(lib, "fa_mla_indexer_topk_paged_kv8",
+              (q_idx.data_ptr(), w.data_ptr(), k_idx_pages.data_ptr(), k_scale_pages.data_ptr(), indices.data_ptr(), index_counts.data_ptr(),
+               cu_seqlens_q.data_ptr(), block_table.data_ptr(), seqlens_k.data_ptr(), B, Hi, T, int(max_seqlen_q), Di, int(topk), P, num_pages,
+               mp, q_idx.stride(0), q_idx.stride(1), wrs, k_idx_pages.stride(0), k_idx_pages.stride(1),
+               k_scale_pages.stride(0) if num_pages > 1 else P, block_table.stride(0), istride, _TORCH2FA[q_idx.dtype],
+               _TORCH2FA[k_idx_pages.dtype], ws.data_ptr(), ws.numel()), q_idx.device, stream)
+        return indices, index_counts
     _call(lib, "fa_mla_indexer_topk_paged",
           (q_idx.data_ptr(), w.data_ptr(), k_idx_pages.data_ptr(), indices.data_ptr(), index_counts.data_ptr(), cu_seqlens_q.data_ptr(),
            block_table.data_ptr(), seqlens_k.data_ptr(), B, Hi, T, int(max_seqlen_q), Di, int(topk), P, num_pages, mp, q_idx.stride(0),

@@ -1043,7 +1043,7 @@ int fa_fwd_mla_decode_sparse_kv8_supported(int q_dtype, int kv_dtype, int Dqk, i
  * fa_mla_indexer_chunk_keys(B, max_seqlen_q, P, max_pages_per_seq) keys (0: illegal scalars): as few chunks as give 1024 items, none
  * shorter than 8 tiles where the capacity has them. Select: one workgroup per token, a most-significant-byte-first radix select on the
  * order-preserving integer image of the logit (four 256-bin LDS histograms), then one ordered emission pass under a workgroup scan.
- * Not here: e4m3 index keys with per-row scales; a fused logits-and-select kernel without the buffer; non-paged keys; a window or any
+ * Not here (e4m3 index keys with per-key scales: the next section): a fused logits-and-select kernel without the buffer; non-paged keys; a window or any
  * mask other than the causal rule; Di other than 128; the indexer's projections and rotary. No existing call is rerouted.
  */
 int fa_mla_indexer_logits_paged(const void *q_idx, const float *w, const void *k_idx_pages, float *logits,
@@ -1069,6 +1069,57 @@ int fa_mla_indexer_topk_paged(const void *q_idx, const float *w, const void *k_i
 long long fa_mla_indexer_topk_paged_workspace_bytes(int total_q, int page_size, int max_pages_per_seq);
 int fa_mla_indexer_chunk_keys(int B, int max_seqlen_q, int page_size, int max_pages_per_seq);
 int fa_mla_indexer_supported(int dtype, int Hi, int Di, int page_size);   /* f16 | bf16, 32 | 64, 128, 16 .. 256 */
+
+/*
+ * The MLA indexer (e4m3 keys): fa_mla_indexer_logits_paged_kv8 and fa_mla_indexer_topk_paged_kv8 are the two calls above over the index
+ * cache as the models deploy it: q_idx and k_idx_pages are OCP e4m3 bytes (FA_DTYPE_FP8_E4M3, torch's float8_e4m3fn) and every key has
+ * ONE fp32 scale. For a token t of sequence b and a visible key j (the same v)
+ *     logit[t][j] = k_scale(b, j) * sum_h  w[t][h] * max(0, q_idx[t, h, :] . k_idx(b, j)[:])
+ * The dot (an exact e4m3 product on the matrix core), the ReLU and the head sum are fp32; the key's scale multiplies the finished head
+ * sum ONCE. There is no other scale inside the call: the caller folds the query's per-(token, head) scales, the softmax scale and the
+ * heads' own scales into w, as the models do. With exact inputs the logits are exact; in general each lies within
+ * 2^-15 * k_scale_j * sum_h |w_h| sum_d |q_hd| |k_d| of the exact value.
+ * What differs from the 16-bit calls, and nothing else does:
+ *  - `int dtype` is `int q_dtype, int kv_dtype`; only (e4m3, e4m3) is supported.
+ *  - q_row_stride, q_head_stride, k_page_stride and k_row_stride are in BYTES: multiples of 16, at least 128; the bases 16-byte aligned.
+ *  - const float *k_scale_pages follows k_idx_pages and long long k_scale_page_stride follows k_row_stride: key j of a page has its
+ *    scale at element page * k_scale_page_stride + j % P of k_scale_pages (4-byte aligned, k_scale_page_stride >= P, in floats). The
+ *    pointer with its own stride serves both layouts engines use: a separate [num_pages, P] fp32 array (k_scale_page_stride = P), and
+ *    the PACKED page of 132 P bytes, P * 128 value bytes followed by P * 4 scale bytes: k_page_stride = 132 P, k_row_stride = 128,
+ *    k_scale_pages = the pool's base + P * 128 bytes, k_scale_page_stride = 33 P.
+ *  - a key under a page entry outside the pool is a row of zeros: its logit is +0 and neither its bytes nor its scale are read. The
+ *    scale of a key no token of the call sees is not read either.
+ * fa_mla_indexer_topk_paged_kv8 is the logits into the workspace, then fa_mla_indexer_select itself: its lists are BIT-IDENTICAL to
+ * running the two calls by hand. The workspace is fa_mla_indexer_topk_paged_workspace_bytes, the chunk rule fa_mla_indexer_chunk_keys,
+ * the token-block rule the 16-bit call's: grids depend on host scalars alone and one captured graph serves every step.
+ * (e4m3, e4m3), Hi = 32 | 64, Di = 128, P in {16, 32, 64, 128, 256}: anything else FA_ERR_UNSUPPORTED with a message that names what was
+ * given (fa_mla_indexer_supported keeps answering 0 for e4m3). Every rule of the 16-bit calls keeps its status and its text after the
+ * function name -- a byte stride that is not a multiple of 16 is their stride rule. Of these calls' own, each FA_ERR_INVALID_ARG before
+ * any launch: k_scale_pages null or not 4-byte aligned, k_scale_page_stride < P.
+ * How it runs (csrc/fa_mla_indexer_kv8_kernel.hip): the 16-bit kernel's items, barriers and descriptor rule
+ * around a score tile of its own -- one v_mfma_f32_16x16x128_f8f6f4 (unit E8M0 scales) is the whole 128-column dot of 16 heads against
+ * 16 keys; a token's query is Hi / 16 fragments of 32 bytes per lane; a 64-key tile is 8 KiB, rows of 128 bytes under the swizzle
+ * k ^ ((r >> 1) & 7); the scale reaches the storing lane by a predicated global load one tile ahead.
+ * Not here: a quantising append for index keys; E8M0 or block scales fed to the matrix instruction; e4m3 queries against 16-bit keys or
+ * the reverse; a fused logits-and-select kernel; Di other than 128, Hi other than 32 / 64. No existing call is rerouted.
+ */
+int fa_mla_indexer_logits_paged_kv8(const void *q_idx, const float *w, const void *k_idx_pages, const float *k_scale_pages, float *logits,
+                                    const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                                    int B, int Hi, int total_q, int max_seqlen_q, int Di,
+                                    int page_size, int num_pages, int max_pages_per_seq,
+                                    long long q_row_stride, long long q_head_stride, long long w_row_stride,
+                                    long long k_page_stride, long long k_row_stride, long long k_scale_page_stride,
+                                    long long block_table_stride, long long logits_stride, int q_dtype, int kv_dtype, void *hip_stream);
+int fa_mla_indexer_topk_paged_kv8(const void *q_idx, const float *w, const void *k_idx_pages, const float *k_scale_pages,
+                                  int *indices, int *index_counts,
+                                  const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                                  int B, int Hi, int total_q, int max_seqlen_q, int Di, int topk,
+                                  int page_size, int num_pages, int max_pages_per_seq,
+                                  long long q_row_stride, long long q_head_stride, long long w_row_stride,
+                                  long long k_page_stride, long long k_row_stride, long long k_scale_page_stride,
+                                  long long block_table_stride, long long indices_stride, int q_dtype, int kv_dtype,
+                                  void *workspace, long long workspace_bytes, void *hip_stream);
+int fa_mla_indexer_kv8_supported(int q_dtype, int kv_dtype, int Hi, int Di, int page_size);   /* e4m3, e4m3, 32 | 64, 128, 16 .. 256 */
 
 /*
  * Multi-head latent attention (prefill): fa_fwd_varlen_mla is the NON-absorbed form of the same layer, as serving engines run its
