@@ -38,6 +38,8 @@ from .ops import (  # noqa: F401
     mla_decode_paged_wide_supported,
     mla_decode_paged_wide_workspace_bytes,
     mla_decode_paged_workspace_bytes,
+    mla_decode_sparse_kv8_scaled_supported,
+    mla_decode_sparse_kv8_scaled_workspace_bytes,
     mla_decode_sparse_kv8_supported,
     mla_decode_sparse_kv8_workspace_bytes,
     mla_decode_sparse_supported,
@@ -48,6 +50,7 @@ from .ops import (  # noqa: F401
     mla_indexer_select,
     mla_indexer_supported,
     mla_indexer_workspace_bytes,
+    mla_kv_append_paged_scaled,
     supported,
     varlen_backward_supported,
     varlen_backward_workspace_bytes,

@@ -847,10 +847,13 @@ long long fa_fwd_mla_decode_sparse_workspace_bytes(int T, int Hq, int Dv, int to
   if (topk < 1 || mla_sparse_cap(topk) > (1 << 30)) return 0;
   return fa_fwd_mla_decode_paged_wide_workspace_bytes(T, Hq, 1, Dv, 64, (int)(mla_sparse_cap(topk) / 64));
 }
-// The two modes of the one path. MLA_SPARSE_WIDE: f16 / bf16, q and the pool alike (fa_mla_sparse_kernel.hip). MLA_SPARSE_KV8: bf16
+// The three modes of the one path. MLA_SPARSE_WIDE: f16 / bf16, q and the pool alike (fa_mla_sparse_kernel.hip). MLA_SPARSE_KV8: bf16
 // queries on an e4m3 pool (fa_mla_sparse_kv8_kernel.hip), the same split count and workspace; `dtype` is the queries' and kv_dtype the
 // pool's (the other mode: both are `dtype`). The dtype-pair rule and the pool's stride multiple are all that differ.
-enum { MLA_SPARSE_WIDE = 0, MLA_SPARSE_KV8 = 1 };
+// MLA_SPARSE_KV8_SCALED: that mode over rows of 656 bytes (fa_mla_sparse_kv8_scaled_kernel.hip): the text of the dtype-pair rule and the
+// least row and page stride, 656 in place of 576, are all that differ from it.
+enum { MLA_SPARSE_WIDE = 0, MLA_SPARSE_KV8 = 1, MLA_SPARSE_KV8_SCALED = 2 };
+constexpr int MLA_SCALED_ROW_BYTES = 656;  // 512 e4m3 latent bytes, four fp32 scales, 64 bf16 rotary elements
 static bool mla_sparse_kv8_shape_ok(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int page_size) {
   return mla_kv8_shape_ok(q_dtype, kv_dtype, Dqk, Dv, Hq, 1, page_size);
 }
@@ -863,11 +866,11 @@ static int mla_decode_sparse_impl(const char *fn, int mode, const void *q, const
   TRY(nonnull(fn, {q, kv_pages, o, indices, workspace}));
   TRY(positive(fn, {T, Hq, Dqk, Dv, topk, page_size, num_pages}));
   TRY(scale_ok(fn, scale));
-  if (mode == MLA_SPARSE_KV8) {
+  if (mode != MLA_SPARSE_WIDE) {
     if (!mla_sparse_kv8_shape_ok(dtype, kv_dtype, Dqk, Dv, Hq, page_size))
-      return fail(FA_ERR_UNSUPPORTED, "%s: needs bf16 queries on an e4m3 pool, (Dqk, Dv) = (576, 512), Hq <= 128 heads and a page size of "
-                  "16, 32, 64, 128 or 256; got q=%s kv=%s Dqk=%d Dv=%d Hq=%d page_size=%d", fn, fa_dtype_name(dtype), fa_dtype_name(kv_dtype),
-                  Dqk, Dv, Hq, page_size);
+      return fail(FA_ERR_UNSUPPORTED, "%s: needs bf16 queries on an e4m3 pool%s, (Dqk, Dv) = (576, 512), Hq <= 128 heads and a page size of "
+                  "16, 32, 64, 128 or 256; got q=%s kv=%s Dqk=%d Dv=%d Hq=%d page_size=%d", fn,
+                  mode == MLA_SPARSE_KV8_SCALED ? " of 656-byte rows" : "", fa_dtype_name(dtype), fa_dtype_name(kv_dtype), Dqk, Dv, Hq, page_size);
   } else if (!mla_decode_shape_ok(dtype, Dqk, Dv, Hq, 1, page_size, 128))
     return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 (q and the pool alike), (Dqk, Dv) = (576, 512), Hq <= 128 heads and a page size of "
                 "16, 32, 64, 128 or 256; got dtype=%s Dqk=%d Dv=%d Hq=%d page_size=%d", fn, fa_dtype_name(dtype), Dqk, Dv, Hq, page_size);
@@ -875,8 +878,10 @@ static int mla_decode_sparse_impl(const char *fn, int mode, const void *q, const
     return fail(FA_ERR_INVALID_ARG, "%s: indices_stride=%lld must be a multiple of 4 and >= topk=%d", fn, indices_stride, topk);
   TRY(mla_strides_ok(fn, "", T, Dqk, q_token_stride, q_head_stride, Dqk));
   TRY(mla_strides_ok(fn, "output ", T, Dv, o_token_stride, o_head_stride, Dv));
-  // (an e4m3 pool: strides in elements = bytes, multiples of 16, a page counted in bytes of 1 -- fa_fwd_mla_decode_paged_kv8's rule)
-  TRY(page_strides_ok(fn, Dqk, page_size, kv_page_stride, kv_row_stride, kv_row_stride, 0, kv_dtype));
+  // (an e4m3 pool: strides in elements = bytes, multiples of 16, a page counted in bytes of 1 -- fa_fwd_mla_decode_paged_kv8's rule; the
+  // scaled rows: the same rule with a row of 656 bytes)
+  TRY(page_strides_ok(fn, mode == MLA_SPARSE_KV8_SCALED ? MLA_SCALED_ROW_BYTES : Dqk, page_size, kv_page_stride, kv_row_stride, kv_row_stride, 0,
+                      kv_dtype));
   TRY(aligned16(fn, "tensors and workspace", {q, kv_pages, o, workspace}));
   TRY(aligned16(fn, "indices", {indices}));
   if ((uintptr_t)index_counts & 3) return fail(FA_ERR_INVALID_ARG, "%s: index_counts must be int32-aligned", fn);
@@ -885,7 +890,9 @@ static int mla_decode_sparse_impl(const char *fn, int mode, const void *q, const
     return fail(FA_ERR_INVALID_ARG, "%s: num_pages * page_size = %lld slots, above 2^30", fn, (long long)num_pages * page_size);
   const int cap = (int)mla_sparse_cap(topk);
   TRY(workspace_fits(fn, workspace_bytes, fa::mla_decode_sparse_workspace_bytes(T, Hq, cap),
-                     mode == MLA_SPARSE_KV8 ? "fa_fwd_mla_decode_sparse_kv8_workspace_bytes" : "fa_fwd_mla_decode_sparse_workspace_bytes"));
+                     mode == MLA_SPARSE_KV8_SCALED ? "fa_fwd_mla_decode_sparse_kv8_scaled_workspace_bytes"
+                     : mode == MLA_SPARSE_KV8      ? "fa_fwd_mla_decode_sparse_kv8_workspace_bytes"
+                                                   : "fa_fwd_mla_decode_sparse_workspace_bytes"));
   const int rblk = (Hq + 15) / 16;
   if ((long long)T * Hq > 0x7fffffffLL || (long long)T * 256 * rblk > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
   const int nw = fa::mla_wide_waves(Hq);
@@ -893,7 +900,7 @@ static int mla_decode_sparse_impl(const char *fn, int mode, const void *q, const
   p.q = q; p.kv = kv_pages; p.ws = (float *)workspace;
   p.indices = indices; p.counts = index_counts;
   p.T = T; p.Hq = Hq; p.Nq = 1; p.RBLK = rblk; p.scale = scale;
-  // the wide call's own rule at (T, 1, cap), in both modes: both kernels run four waves for every head count, and for Hq <= 32 (rblk
+  // the wide call's own rule at (T, 1, cap), in every mode: all three kernels run four waves for every head count, and for Hq <= 32 (rblk
   // <= 2) the rule is fed ONE row block under either wave count, ceil(rblk / 2) = ceil(rblk / 4) = 1 -- the same S, the same workspace
   p.S = fa::mla_decode_splits(T, (rblk + nw - 1) / nw, cap);
   p.q_bs = q_token_stride; p.q_hs = q_head_stride; p.q_rs = Dqk;
@@ -904,8 +911,9 @@ static int mla_decode_sparse_impl(const char *fn, int mode, const void *q, const
   pc.o = o; pc.lse = lse; pc.ws = p.ws;
   pc.B = T; pc.Hq = Hq; pc.Nq = 1; pc.S = p.S; pc.RBLK = rblk;
   pc.o_bs = o_token_stride; pc.o_hs = o_head_stride; pc.o_rs = Dv;
-  return launched(fn, mode == MLA_SPARSE_KV8 ? fa::launch_mla_decode_sparse_kv8(p, pc, (hipStream_t)hip_stream)
-                                             : fa::launch_mla_decode_sparse(p, pc, dtype, (hipStream_t)hip_stream));
+  return launched(fn, mode == MLA_SPARSE_KV8_SCALED ? fa::launch_mla_decode_sparse_kv8_scaled(p, pc, (hipStream_t)hip_stream)
+                      : mode == MLA_SPARSE_KV8      ? fa::launch_mla_decode_sparse_kv8(p, pc, (hipStream_t)hip_stream)
+                                                    : fa::launch_mla_decode_sparse(p, pc, dtype, (hipStream_t)hip_stream));
 }
 int fa_fwd_mla_decode_sparse(const void *q, const void *kv_pages, void *o, float *lse, const int *indices, const int *index_counts, int T,
                              int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages, float scale, long long q_token_stride,
@@ -932,6 +940,55 @@ int fa_fwd_mla_decode_sparse_kv8(const void *q, const void *kv_pages, void *o, f
   return mla_decode_sparse_impl("fa_fwd_mla_decode_sparse_kv8", MLA_SPARSE_KV8, q, kv_pages, o, lse, indices, index_counts, T, Hq, Dqk, Dv,
                                 topk, page_size, num_pages, scale, q_token_stride, q_head_stride, o_token_stride, o_head_stride,
                                 kv_page_stride, kv_row_stride, indices_stride, q_dtype, kv_dtype, workspace, workspace_bytes, hip_stream);
+}
+
+// fa_fwd_mla_decode_sparse_kv8_scaled: the e4m3 sparse call over 656-byte rows with a scale per 128 latent elements -- the third mode
+int fa_fwd_mla_decode_sparse_kv8_scaled_supported(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int page_size) {
+  return mla_sparse_kv8_shape_ok(q_dtype, kv_dtype, Dqk, Dv, Hq, page_size);
+}
+long long fa_fwd_mla_decode_sparse_kv8_scaled_workspace_bytes(int T, int Hq, int Dv, int topk) {
+  return fa_fwd_mla_decode_sparse_workspace_bytes(T, Hq, Dv, topk);
+}
+int fa_fwd_mla_decode_sparse_kv8_scaled(const void *q, const void *kv_pages, void *o, float *lse, const int *indices, const int *index_counts,
+                                        int T, int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages, float scale,
+                                        long long q_token_stride, long long q_head_stride, long long o_token_stride, long long o_head_stride,
+                                        long long kv_page_stride, long long kv_row_stride, long long indices_stride, int q_dtype, int kv_dtype,
+                                        void *workspace, long long workspace_bytes, void *hip_stream) {
+  return mla_decode_sparse_impl("fa_fwd_mla_decode_sparse_kv8_scaled", MLA_SPARSE_KV8_SCALED, q, kv_pages, o, lse, indices, index_counts, T, Hq,
+                                Dqk, Dv, topk, page_size, num_pages, scale, q_token_stride, q_head_stride, o_token_stride, o_head_stride,
+                                kv_page_stride, kv_row_stride, indices_stride, q_dtype, kv_dtype, workspace, workspace_bytes, hip_stream);
+}
+
+// fa_mla_kv_append_paged_scaled: the append that writes those rows. fa_kv_append_paged's rules at Hkv = 1 on one pool of bytes (the shared
+// helpers in kv_append_impl's order, with its statuses and texts); the rows' type and the 656-byte row are the rules of its own
+int fa_mla_kv_append_paged_scaled(const void *kv_new, void *kv_pages, const int *cu_seqlens_new, const int *block_table, const int *seqlens_k,
+                                  int B, int total_new, int max_seqlen_new, int page_size, int num_pages, int max_pages_per_seq,
+                                  long long new_row_stride, long long kv_page_stride, long long kv_row_stride, long long block_table_stride,
+                                  int new_dtype, void *hip_stream) {
+  const char *fn = "fa_mla_kv_append_paged_scaled";
+  g_err[0] = 0;
+  TRY(nonnull(fn, {kv_new, kv_pages, cu_seqlens_new, block_table, seqlens_k}));
+  TRY(positive(fn, {B, total_new, max_seqlen_new, page_size, num_pages, max_pages_per_seq}));
+  if (new_dtype != FA_DTYPE_BF16 || !fa::page_size_ok(page_size))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs bf16 new rows of 576 elements (the rotary part is copied, the pool's rows are 656 bytes) and a "
+                "page size of 16, 32, 64, 128 or 256; got new_dtype=%s page_size=%d", fn, fa_dtype_name(new_dtype), page_size);
+  if (max_seqlen_new > total_new)
+    return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen_new=%d exceeds the token count %d", fn, max_seqlen_new, total_new);
+  TRY(varlen_strides_ok(fn, "new key/value ", 576, new_row_stride, new_row_stride, stride_mult(new_dtype)));
+  TRY(page_pool_ok(fn, MLA_SCALED_ROW_BYTES, page_size, max_pages_per_seq, kv_page_stride, kv_row_stride, kv_row_stride, block_table_stride,
+                   FA_DTYPE_FP8_E4M3, block_table, seqlens_k));
+  TRY(aligned16(fn, "tensors", {kv_new, kv_pages}));
+  if ((uintptr_t)cu_seqlens_new & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_new must be int32-aligned", fn);
+  if ((long long)B * ((max_seqlen_new + 3) / 4) > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  fa::AppendPagedParams p = {};
+  p.k_new = kv_new; p.k_pages = kv_pages;
+  p.cu_new = cu_seqlens_new; p.block_table = block_table; p.seqlens = seqlens_k;
+  p.B = B; p.Hkv = 1; p.total_new = total_new; p.max_new = max_seqlen_new; p.D = 576;
+  p.new_rs = new_row_stride;
+  p.page_stride = kv_page_stride; p.row_stride = kv_row_stride;
+  p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
+  p.lp = log2_of(page_size);
+  return launched(fn, fa::launch_mla_kv_append_paged_scaled(p, (hipStream_t)hip_stream));
 }
 
 // ---- fa_mla_indexer_*: the indexer in front of the sparse decode (csrc/fa_mla_indexer_kernel.hip). The query side and the tables carry

@@ -317,6 +317,10 @@ hipError_t launch_kv_append_paged(const AppendPagedParams &p, int elem_bytes, hi
 // fa_kv_append_paged_quant: the same placement with 16-bit new rows (new_dtype f16 / bf16) quantised into e4m3 pools,
 // byte = e4m3_rne(clamp(fp32(x) * mul, -448, 448))
 hipError_t launch_kv_append_paged_quant(const AppendPagedParams &p, int new_dtype, float k_mul, float v_mul, hipStream_t s);
+// fa_mla_kv_append_paged_scaled (csrc/fa_mla_append_scaled_kernel.hip): the same placement with Hkv = 1 and ONE pool of 656-byte rows:
+// k_new holds the bf16 rows [total_new, 576] (new_rs in elements), k_pages the pool (page_stride / row_stride in BYTES); v_*, new_hs,
+// head_stride and D are not read. Four new rows per workgroup, one wave each
+hipError_t launch_mla_kv_append_paged_scaled(const AppendPagedParams &p, hipStream_t s);
 hipError_t launch_mfma_split2(const Params &p, int dtype, hipStream_t s);
 bool mfma_split2_supported(int dtype, int D);
 hipError_t launch_mfma_h64s2(const Params &p, int dtype, hipStream_t s);
@@ -363,6 +367,10 @@ long long mla_decode_sparse_workspace_bytes(int T, int Hq, int cap);
 // queries, the tile staged through registers and widened as fa_fwd_mla_decode_paged_kv8 does; the sparse call's split count, workspace
 // and (bf16) combine kernel
 hipError_t launch_mla_decode_sparse_kv8(const MlaSparseParams &p, const MlaDecodeParams &pc, hipStream_t s);
+// fa_fwd_mla_decode_sparse_kv8_scaled (csrc/fa_mla_sparse_kv8_scaled_kernel.hip): the sparse call over a pool of 656-byte rows (512 e4m3
+// latent bytes, four fp32 scales, 64 bf16 rotary elements; p's pool strides count bytes), bf16 queries, the tile dequantised into the
+// bf16 image while staging; the sparse call's split count, workspace and (bf16) combine kernel
+hipError_t launch_mla_decode_sparse_kv8_scaled(const MlaSparseParams &p, const MlaDecodeParams &pc, hipStream_t s);
 // fa_mla_indexer_* (csrc/fa_mla_indexer_kernel.hip): the token block (1, 2, 4) and the chunk rule from host scalars, the logits kernel
 // over B * nblk * nchunks items of four waves, the select kernel over B * max_seqlen_q workgroups
 int mla_indexer_token_block(int max_seqlen_q);

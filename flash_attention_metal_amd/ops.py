@@ -466,6 +466,17 @@ def mla_decode_sparse_kv8_workspace_bytes(T: int, Hq: int, d_v: int, topk: int) 
     return int(load_library().fa_fwd_mla_decode_sparse_kv8_workspace_bytes(T, Hq, d_v, topk))
 
 
+def mla_decode_sparse_kv8_scaled_supported(q_dtype: str, kv_dtype: str, d_qk: int, d_v: int, Hq: int, page_size: int) -> bool:
+    return bool(load_library().fa_fwd_mla_decode_sparse_kv8_scaled_supported(DTYPES[q_dtype], DTYPES[kv_dtype], d_qk, d_v, Hq, page_size))
+
+
+def mla_decode_sparse_kv8_scaled_workspace_bytes(T: int, Hq: int, d_v: int, topk: int) -> int:
+    return int(load_library().fa_fwd_mla_decode_sparse_kv8_scaled_workspace_bytes(T, Hq, d_v, topk))
+
+
+MLA_SCALED_ROW_BYTES = 656  # 512 e4m3 latent bytes, four fp32 scales (one per 128 latent elements), 64 bf16 rotary elements
+
+
 def flash_attention_mla_decode_sparse(
     q: torch.Tensor,
     kv_pages: torch.Tensor,
@@ -492,28 +503,34 @@ def flash_attention_mla_decode_sparse(
     A torch.float8_e4m3fn pool under bf16 q goes to fa_fwd_mla_decode_sparse_kv8 (no scales: the bytes are read as plain e4m3 values; a
     caller that appended with k_mul = v_mul = 1 / s passes scale * s and multiplies O by s). The pool's strides are then bytes, a SLOT
     is still page * P + row, O is bf16 and the workspace is sized by mla_decode_sparse_kv8_workspace_bytes(...), the same number; f16 q
-    on such a pool raises ValueError."""
+    on such a pool raises ValueError.
+    A torch.uint8 pool [num_pages, P, 656] (or [num_pages, P, 1, 656]) under bf16 q goes to fa_fwd_mla_decode_sparse_kv8_scaled: every row
+    holds 512 e4m3 latent bytes, four fp32 scales (one per 128 latent elements) and 64 bf16 rotary elements, the layout
+    mla_kv_append_paged_scaled writes; latent element d is read as bf16(fp32(byte d) * s[d // 128]). The pool's strides are bytes, O is
+    bf16 and the workspace is sized by mla_decode_sparse_kv8_scaled_workspace_bytes(...), the same number again."""
     lib = load_library()
     if scale is None:
         raise ValueError("flash_attention_mla_decode_sparse needs the model's scale: there is no default (the head dim of the model is not 576)")
     if q.dim() != 3 or kv_pages.dim() not in (3, 4) or (kv_pages.dim() == 4 and kv_pages.shape[2] != 1):
         raise ValueError("q [T,Hq,576], kv_pages one [num_pages,P,576] or [num_pages,P,1,576] latent pool")
     kv8 = _FP8 is not None and kv_pages.dtype == _FP8
-    if kv8 and q.dtype != torch.bfloat16:
-        raise ValueError(f"unsupported dtypes {q.dtype} {kv_pages.dtype}: a float8_e4m3fn latent pool takes bf16 queries only")
+    scaled = kv_pages.dtype == torch.uint8 and kv_pages.shape[-1] == MLA_SCALED_ROW_BYTES
+    if (kv8 or scaled) and q.dtype != torch.bfloat16:
+        raise ValueError(f"unsupported dtypes {q.dtype} {kv_pages.dtype}: a float8_e4m3fn latent pool takes bf16 queries only"
+                         if kv8 else f"unsupported dtypes {q.dtype} {kv_pages.dtype}: a pool of 656-byte rows takes bf16 queries only")
     tensors = (q, kv_pages, indices) + (() if index_counts is None else (index_counts,))
     if not all(t.is_cuda and t.device == q.device for t in tensors):
         raise ValueError("flash_attention_mla_decode_sparse needs q, the pool, the index lists and their counts on one device: there is no CPU path")
     T, Hq, Dqk = q.shape
     num_pages, P, Dk = kv_pages.shape[0], kv_pages.shape[1], kv_pages.shape[-1]
     ps, rs, es = kv_pages.stride(0), kv_pages.stride(1), kv_pages.stride(-1)
-    if Dk != Dqk or es != 1 or q.stride(2) != 1:
+    if (Dk != Dqk and not scaled) or es != 1 or q.stride(2) != 1:
         raise ValueError(f"incompatible q {tuple(q.shape)} and pool {tuple(kv_pages.shape)} (same last dim, unit element strides)")
     if indices.dtype != torch.int32 or indices.dim() != 2 or indices.shape[0] != T or indices.shape[1] < 1 or indices.stride(1) != 1:
         raise ValueError("indices must be an int32 [T, topk] tensor with a unit last stride")
     if index_counts is not None and (index_counts.dtype != torch.int32 or index_counts.shape != (T,) or not index_counts.is_contiguous()):
         raise ValueError("index_counts must be a contiguous int32 [T] tensor, or None")
-    if not kv8 and (q.dtype not in (torch.float16, torch.bfloat16) or kv_pages.dtype != q.dtype):
+    if not (kv8 or scaled) and (q.dtype not in (torch.float16, torch.bfloat16) or kv_pages.dtype != q.dtype):
         raise ValueError(f"unsupported / mixed dtypes {q.dtype} {kv_pages.dtype} (f16 or bf16, q and the pool alike)")
     d_v = int(d_v)
     topk = indices.shape[1]
@@ -527,12 +544,13 @@ def flash_attention_mla_decode_sparse(
         raise ValueError("lse must be contiguous fp32 [T,Hq] on q's device")
     # (one row: its stride addresses nothing, and torch reports any value for a dimension of size 1)
     istride = indices.stride(0) if T > 1 else (topk + 3) // 4 * 4
-    if kv8:  # (the pool's strides come from the tensor: bytes)
-        ws = _workspace(workspace, mla_decode_sparse_kv8_workspace_bytes(T, Hq, d_v, topk), q.device)
-        _call(lib, "fa_fwd_mla_decode_sparse_kv8",
+    if kv8 or scaled:  # (the pool's strides come from the tensor: bytes)
+        sizer = mla_decode_sparse_kv8_scaled_workspace_bytes if scaled else mla_decode_sparse_kv8_workspace_bytes
+        ws = _workspace(workspace, sizer(T, Hq, d_v, topk), q.device)
+        _call(lib, "fa_fwd_mla_decode_sparse_kv8_scaled" if scaled else "fa_fwd_mla_decode_sparse_kv8",
               (q.data_ptr(), kv_pages.data_ptr(), out.data_ptr(), _ptr(lse), indices.data_ptr(), _ptr(index_counts), T, Hq, Dqk, d_v, topk, P,
                num_pages, float(scale), q.stride(0), q.stride(1), out.stride(0), out.stride(1), ps, rs, istride,
-               _TORCH2FA[q.dtype], _TORCH2FA[kv_pages.dtype], ws.data_ptr(), ws.numel()), q.device, stream)
+               _TORCH2FA[q.dtype], DTYPES["fp8_e4m3"] if scaled else _TORCH2FA[kv_pages.dtype], ws.data_ptr(), ws.numel()), q.device, stream)
         return out, lse
     ws = _workspace(workspace, mla_decode_sparse_workspace_bytes(T, Hq, d_v, topk), q.device)
     _call(lib, "fa_fwd_mla_decode_sparse",
@@ -1029,6 +1047,39 @@ def kv_append_paged(
           (k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), cu_seqlens_new.data_ptr(), block_table.data_ptr(),
            seqlens_k.data_ptr(), B, Hkv, k_new.shape[0], int(max_seqlen_new), D, P, num_pages, block_table.shape[1], k_new.stride(0),
            k_new.stride(1), ps, hs, rs, block_table.stride(0), *tail), k_pages.device, stream)
+
+
+def mla_kv_append_paged_scaled(
+    kv_new: torch.Tensor,
+    kv_pages: torch.Tensor,
+    cu_seqlens_new: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens_k: torch.Tensor,
+    max_seqlen_new: int,
+    stream: Optional[int] = None,
+) -> None:
+    """Quantise new latent rows into a pool of 656-byte rows, in place (include/fa_mi355.h fa_mla_kv_append_paged_scaled): kv_new
+    [total_new, 576] bf16 with a unit last stride; kv_pages torch.uint8 [num_pages, P, 656] (or [num_pages, P, 1, 656]) with a unit last
+    stride, the pool flash_attention_mla_decode_sparse reads. Per 128 latent elements a power-of-two scale 2^e, the smallest with
+    amax <= 448 * 2^e (e in [-32, 32]), the elements as e4m3_rne(clamp(x * 2^-e, -448, 448)), the 64 rotary elements copied. Tables,
+    placement and skipping are kv_append_paged's: seqlens_k holds the lengths AFTER the append; positions outside the capacity or on
+    table entries outside the pool are skipped; exactly bytes 0 .. 655 of each written row are written. Nothing here synchronises or
+    reads device values: graph-capturable."""
+    lib = load_library()
+    entry = "mla_kv_append_paged_scaled"
+    if (kv_pages.dtype != torch.uint8 or kv_pages.dim() not in (3, 4) or (kv_pages.dim() == 4 and kv_pages.shape[2] != 1)
+            or kv_pages.shape[-1] != MLA_SCALED_ROW_BYTES or kv_pages.stride(-1) != 1):
+        raise ValueError(f"kv_pages one uint8 [num_pages,P,656] or [num_pages,P,1,656] pool with a unit last stride, got {tuple(kv_pages.shape)} "
+                         f"{kv_pages.dtype}")
+    if kv_new.dtype != torch.bfloat16 or kv_new.dim() != 2 or kv_new.shape[1] != 576 or kv_new.stride(1) != 1:
+        raise ValueError(f"kv_new one bf16 [total_new,576] tensor with a unit last stride, got {tuple(kv_new.shape)} {kv_new.dtype}")
+    B = _tables(entry, cu_seqlens_new, "cu_seqlens_new", block_table, seqlens_k)
+    if not all(t.is_cuda and t.device == kv_pages.device for t in (kv_new, kv_pages, cu_seqlens_new, block_table, seqlens_k)):
+        raise RuntimeError("mla_kv_append_paged_scaled needs the new rows, the pool and the tables on one device: there is no CPU path")
+    _call(lib, "fa_mla_kv_append_paged_scaled",
+          (kv_new.data_ptr(), kv_pages.data_ptr(), cu_seqlens_new.data_ptr(), block_table.data_ptr(), seqlens_k.data_ptr(), B, kv_new.shape[0],
+           int(max_seqlen_new), kv_pages.shape[1], kv_pages.shape[0], block_table.shape[1], kv_new.stride(0), kv_pages.stride(0),
+           kv_pages.stride(1), block_table.stride(0), _TORCH2FA[kv_new.dtype]), kv_pages.device, stream)
 
 
 def varlen_backward_supported(dtype: str, D: int) -> bool:

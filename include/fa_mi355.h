@@ -931,7 +931,8 @@ int fa_fwd_mla_decode_paged_kv8_supported(int q_dtype, int kv_dtype, int Dqk, in
  * OWN, built on the row's 64-bit address (num_records = 1152, or 0 for an entry behind n_t or outside the pool); the rotary 128 bytes
  * of a row go through registers, two predicated 16-byte loads per lane and tile, written into the image behind the tile's arithmetic.
  * From LDS onwards the source text is the wide call's.
- * Not here: e4m3 pools and the 656-byte rows with per-tile scales; a mask inside the list; more than 128 heads; sinks; the indexer
+ * Not here: e4m3 pools (fa_fwd_mla_decode_sparse_kv8) and the 656-byte rows with a scale per 128 latent elements
+ * (fa_fwd_mla_decode_sparse_kv8_scaled); a mask inside the list; more than 128 heads; sinks; the indexer
  * itself; a sparse backward. No dense call is rerouted.
  */
 int fa_fwd_mla_decode_sparse(const void *q, const void *kv_pages, void *o, float *lse,
@@ -980,8 +981,8 @@ int fa_fwd_mla_decode_sparse_supported(int dtype, int Dqk, int Dv, int Hq, int p
  * (token, split). Wave w stages rows 16 * w .. + 15 of a tile through registers under that kernel's lane maps; only the nine raw loads
  * per lane differ: each lane takes its row's entry from the wave's entry register, forms the row's 64-bit byte address and issues one
  * predicated 16-byte load (an invalid entry: zeros, no load). Widening, the tile image and everything from LDS onwards are the twins'.
- * Not here: f16 or e4m3 queries; scales inside the kernel, block or per-token scales; the 656-byte rows (e4m3 latent + fp32 tile scales
- * + bf16 rotary); a mask inside the list; more than 128 heads; sinks, window and softcap; the indexer itself; a sparse backward. No
+ * Not here: f16 or e4m3 queries; scales inside the kernel, block or per-token scales (the 656-byte rows -- e4m3 latent + fp32 tile scales
+ * + bf16 rotary -- are fa_fwd_mla_decode_sparse_kv8_scaled's); a mask inside the list; more than 128 heads; sinks, window and softcap; the indexer itself; a sparse backward. No
  * dense call is rerouted.
  */
 int fa_fwd_mla_decode_sparse_kv8(const void *q, const void *kv_pages, void *o, float *lse,
@@ -995,6 +996,77 @@ int fa_fwd_mla_decode_sparse_kv8(const void *q, const void *kv_pages, void *o, f
 /* the sparse call's size on every legal input; 0 if a size is invalid or unsupported */
 long long fa_fwd_mla_decode_sparse_kv8_workspace_bytes(int T, int Hq, int Dv, int topk);
 int fa_fwd_mla_decode_sparse_kv8_supported(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int page_size);
+
+/*
+ * Multi-head latent attention (decode, sparse, 656-byte rows): fa_fwd_mla_decode_sparse_kv8_scaled is fa_fwd_mla_decode_sparse_kv8 over the
+ * row layout that models with an fp8 latent cache are served with (FlashMLA's sparse fp8 decode; vLLM's fp8_ds_mla): an e4m3 latent with
+ * one fp32 scale per 128 elements and an UNQUANTISED bf16 rotary part. The listed rows are read in place. The argument list is that
+ * call's.
+ * THE ROW, 656 bytes, little-endian:
+ *   bytes   0 .. 511   latent elements 0 .. 511 as OCP e4m3 (e4m3fn)
+ *   bytes 512 .. 527   four fp32 scales s_0 .. s_3; s_g belongs to latent elements 128 g .. 128 g + 127
+ *   bytes 528 .. 655   rotary elements 512 .. 575 as bf16
+ * THE VALUE OF A KEY: latent element d is bf16_rne(fp32(e4m3 byte d) * s_{d / 128}) -- ONE fp32 multiply rounded to nearest even, then one
+ * rounding to bf16; the rotary elements are their bf16 bits. The rule is guaranteed for finite scales with 2^-64 <= |s| <= 2^64 (no product
+ * is an fp32 subnormal); outside that range the values are unspecified, but no address depends on a scale. ANY scale of the range is read,
+ * not only powers of two: a cache written by another engine (amax / 448) is readable. A NaN code or a NaN scale in a NAMED row
+ * propagates; in a row that no list names, in the bytes between rows under a wider stride, or in entries behind n_t it is never read.
+ * Supported: (q_dtype, kv_dtype) = (FA_DTYPE_BF16, FA_DTYPE_FP8_E4M3) only, O is bf16; (Dqk, Dv) = (576, 512), 1 <= Hq <= 128, topk >= 1,
+ * T >= 1, P in {16, 32, 64, 128, 256}; anything else FA_ERR_UNSUPPORTED with a message that names what was given.
+ * The pool is [num_pages, P, 656] BYTES; kv_page_stride and kv_row_stride count bytes, are multiples of 16 and at least 656, the base is
+ * 16-byte aligned. The pool may exceed 4 GiB, one page stays below 2 GiB. A key is the SLOT x = page * P + row; its byte address is
+ * (x >> log2 P) * kv_page_stride + (x & (P - 1)) * kv_row_stride.
+ * Everything else is fa_fwd_mla_decode_sparse_kv8's, in its words: lists, counts and slots; a slot named twice enters twice; an entry
+ * among the first n_t outside [0, num_pages * P) is a key of zeros and no address is formed from it; nothing at j >= n_t or j >= topk is
+ * ever read; n_t = 0 gives O = 0 exactly and LSE = -inf; the host reads neither table and both grids depend on host scalars alone
+ * (graph-capturable); the split count S; fa_fwd_mla_decode_sparse_kv8_scaled_workspace_bytes equals
+ * fa_fwd_mla_decode_sparse_workspace_bytes(T, Hq, Dv, topk) on every legal input and is 0 elsewhere.
+ * THE CONTRACT: O and LSE are BIT-IDENTICAL to fa_fwd_mla_decode_sparse(..., FA_DTYPE_BF16) on a bf16 pool [num_pages, P, 576] that holds
+ * every row's values by the rule above, under the same lists, counts and page size. The tolerances and "LSE accuracy" are that call's on
+ * those values; no dependence on the workspace's prior contents; bitwise reproducible; asynchronous, allocates nothing.
+ * Validation runs on the sparse call's path, as a third mode: every rule shared with fa_fwd_mla_decode_sparse_kv8 carries the same status
+ * and the same text after the function name; only the text of the dtype-pair rule and the least stride, 656, differ.
+ * How it runs (csrc/fa_mla_sparse_kv8_scaled_kernel.hip): fa_fwd_mla_decode_sparse_kv8's four-wave workgroup; only
+ * the staging of a wave's sixteen rows is new. Eight 16-byte latent loads per lane under that kernel's map, each with ONE predicated
+ * dword, the scale of the chunk's group, from byte 512 + 4 * group of the same row; v_cvt_pk_f32_fp8, v_mul_f32, v_cvt_pk_bf16_f32 into
+ * that kernel's LDS writes; the rotary part, bf16 already, in two 16-byte loads per lane under fa_fwd_mla_decode_sparse's map, written
+ * unwidened. Everything from LDS onwards is the family's text.
+ * Not here: f16 or e4m3 queries; a dense (block-table) call over this layout; a mask inside the list; more than 128 heads; sinks,
+ * window and softcap; a sparse backward. No existing call is rerouted.
+ */
+int fa_fwd_mla_decode_sparse_kv8_scaled(const void *q, const void *kv_pages, void *o, float *lse,
+                                        const int *indices, const int *index_counts,
+                                        int T, int Hq, int Dqk, int Dv, int topk,
+                                        int page_size, int num_pages, float scale,
+                                        long long q_token_stride, long long q_head_stride,
+                                        long long o_token_stride, long long o_head_stride,
+                                        long long kv_page_stride, long long kv_row_stride, long long indices_stride,
+                                        int q_dtype, int kv_dtype, void *workspace, long long workspace_bytes, void *hip_stream);
+/* the sparse call's size on every legal input; 0 if a size is invalid or unsupported */
+long long fa_fwd_mla_decode_sparse_kv8_scaled_workspace_bytes(int T, int Hq, int Dv, int topk);
+int fa_fwd_mla_decode_sparse_kv8_scaled_supported(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int page_size);
+
+/*
+ * fa_mla_kv_append_paged_scaled WRITES the 656-byte rows above: the quantising append of a latent cache in that layout. Its arguments
+ * are fa_kv_append_paged's with Hkv = 1 and one pool: kv_new is [total_new, 576] bf16 under new_row_stride (elements: a multiple of 8, at
+ * least 576, base 16-byte aligned); kv_pages is [num_pages, P, 656] BYTES under kv_page_stride / kv_row_stride (bytes: multiples of 16,
+ * at least 656, base 16-byte aligned, one page below 2 GiB). cu_seqlens_new, block_table, seqlens_k, placement and skipping are word
+ * for word that call's: seqlens_k is the length AFTER the append, token i of sequence b goes to key position seqlens_k[b] - n_b + i, and
+ * a position below 0, out of capacity or on a table entry outside [0, num_pages) is skipped. The footprint is exactly bytes 0 .. 655
+ * of each written row: nothing between rows, no other slot.
+ * Per group g of 128 latent elements of a row, with amax_g its largest magnitude: e_g is the smallest integer in [-32, 32] with
+ * amax_g <= 448 * 2^e_g (an all-zero group gets -32; a group too large saturates through the clamp); s_g = 2^e_g is stored as fp32;
+ * element d is stored as e4m3_rne(clamp(fp32(x_d) * 2^-e_g, -448, 448)), fa_kv_append_paged_quant's conversion. Powers of two make every
+ * step exact. The 64 rotary elements are copied. Inputs must be finite.
+ * new_dtype must be FA_DTYPE_BF16 (anything else, or a bad page size: FA_ERR_UNSUPPORTED). Every shared rule carries fa_kv_append_paged's
+ * status and text. The kernels read the tables, the host never does; the grid, B * ceil(max_seqlen_new / 4) workgroups of four waves (one
+ * wave per new row), depends on host scalars alone. Asynchronous, allocates nothing. csrc/fa_mla_append_scaled_kernel.hip.
+ * Not here: scales that are no power of two; f16 new rows.
+ */
+int fa_mla_kv_append_paged_scaled(const void *kv_new, void *kv_pages, const int *cu_seqlens_new, const int *block_table,
+                                  const int *seqlens_k, int B, int total_new, int max_seqlen_new, int page_size, int num_pages,
+                                  int max_pages_per_seq, long long new_row_stride, long long kv_page_stride, long long kv_row_stride,
+                                  long long block_table_stride, int new_dtype, void *hip_stream);
 
 /*
  * The MLA indexer: fa_mla_indexer_logits_paged, fa_mla_indexer_select and fa_mla_indexer_topk_paged PRODUCE the lists that
