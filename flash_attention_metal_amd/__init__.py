@@ -48,6 +48,8 @@ from .ops import (  # noqa: F401
     mla_indexer_kv8_supported,
     mla_indexer_logits,
     mla_indexer_select,
+    mla_indexer_select_num_splits,
+    mla_indexer_select_split_workspace_bytes,
     mla_indexer_supported,
     mla_indexer_workspace_bytes,
     mla_kv_append_paged_scaled,

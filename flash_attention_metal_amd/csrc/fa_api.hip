@@ -1132,6 +1132,37 @@ int fa_mla_indexer_select(const float *logits, int *indices, int *index_counts, 
                                page_size, num_pages, max_pages_per_seq, logits_stride, indices_stride, block_table_stride));
   return launched(fn, fa::launch_mla_indexer_select(p, (hipStream_t)hip_stream));
 }
+// ---- fa_mla_indexer_select_split (csrc/fa_mla_indexer_select_split_kernel.hip): fa_mla_indexer_select's rules through its own check,
+// then this call's: num_splits, the workspace, the grid. num_splits = 1 is fa_mla_indexer_select's launch and looks at no workspace.
+int fa_mla_indexer_select_num_splits(int B, int max_seqlen_q, int page_size, int max_pages_per_seq) {
+  if (B < 1 || max_seqlen_q < 1 || !mla_indexer_scalars_ok(page_size, max_pages_per_seq)) return 0;
+  return fa::mla_indexer_select_num_splits(B, max_seqlen_q, page_size, max_pages_per_seq);
+}
+long long fa_mla_indexer_select_split_workspace_bytes(int total_q, int num_splits) {
+  if (total_q < 1 || num_splits < 1 || num_splits > 64) return 0;
+  return (fa::mla_indexer_select_split_workspace_ints(total_q, num_splits) * 4 + 15) / 16 * 16;  // < 2^31 * 64 * 1033 * 4
+}
+int fa_mla_indexer_select_split(const float *logits, int *indices, int *index_counts, const int *cu_seqlens_q, const int *block_table,
+                                const int *seqlens_k, int B, int total_q, int max_seqlen_q, int topk, int page_size, int num_pages,
+                                int max_pages_per_seq, long long logits_stride, long long indices_stride, long long block_table_stride,
+                                int num_splits, void *workspace, long long workspace_bytes, void *hip_stream) {
+  const char *fn = "fa_mla_indexer_select_split";
+  g_err[0] = 0;
+  fa::MlaIndexerSelectSplitParams q;
+  TRY(mla_indexer_select_check(fn, q.p, logits, indices, index_counts, cu_seqlens_q, block_table, seqlens_k, B, total_q, max_seqlen_q, topk,
+                               page_size, num_pages, max_pages_per_seq, logits_stride, indices_stride, block_table_stride));
+  if (num_splits < 1 || num_splits > 64) return fail(FA_ERR_INVALID_ARG, "%s: num_splits=%d outside 1 .. 64", fn, num_splits);
+  TRY(aligned16(fn, "workspace", {workspace}));
+  if (num_splits == 1) return launched(fn, fa::launch_mla_indexer_select(q.p, (hipStream_t)hip_stream));
+  if (!workspace) return fail(FA_ERR_INVALID_ARG, "%s: workspace is null with num_splits=%d", fn, num_splits);
+  TRY(workspace_fits(fn, workspace_bytes, fa_mla_indexer_select_split_workspace_bytes(total_q, num_splits),
+                     "fa_mla_indexer_select_split_workspace_bytes"));
+  if ((long long)B * max_seqlen_q > 0x7fffffffLL / num_splits) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  q.S = num_splits;
+  q.seg = fa::mla_indexer_select_split_seg(page_size, max_pages_per_seq, num_splits);
+  q.ws = (int *)workspace;
+  return launched(fn, fa::launch_mla_indexer_select_split(q, (hipStream_t)hip_stream));
+}
 int fa_mla_indexer_topk_paged(const void *q_idx, const float *w, const void *k_idx_pages, int *indices, int *index_counts,
                               const int *cu_seqlens_q, const int *block_table, const int *seqlens_k, int B, int Hi, int total_q,
                               int max_seqlen_q, int Di, int topk, int page_size, int num_pages, int max_pages_per_seq,

@@ -268,6 +268,13 @@ struct MlaIndexerSelectParams {
   int bt_stride, num_pages, max_pages;
   int lp;
 };
+// one fa_mla_indexer_select_split call (csrc/fa_mla_indexer_select_split_kernel.hip): the select's arguments, S workgroups per token
+// over segments of `seg` keys, and the workspace as ints (histograms, states, carries: mla_indexer_select_split_workspace_ints)
+struct MlaIndexerSelectSplitParams {
+  MlaIndexerSelectParams p;
+  int S, seg;
+  int *ws;
+};
 
 // dtype tags
 struct F32 {};
@@ -380,6 +387,12 @@ hipError_t launch_mla_indexer_select(const MlaIndexerSelectParams &p, hipStream_
 // fa_mla_indexer_logits_paged_kv8 (csrc/fa_mla_indexer_kv8_kernel.hip): the logits over e4m3 queries and keys with a scale per key, the
 // same grid
 hipError_t launch_mla_indexer_logits_kv8(const MlaIndexerKv8Params &pp, int Hi, hipStream_t s);
+// fa_mla_indexer_select_split (csrc/fa_mla_indexer_select_split_kernel.hip): the split rule and the segment length from host scalars,
+// the workspace in ints, and the chain of five launches over B * max_seqlen_q * S workgroups (S >= 2)
+int mla_indexer_select_num_splits(int B, int max_seqlen_q, int page_size, int max_pages_per_seq);
+int mla_indexer_select_split_seg(int page_size, int max_pages_per_seq, int S);
+long long mla_indexer_select_split_workspace_ints(long long total_q, int S);
+hipError_t launch_mla_indexer_select_split(const MlaIndexerSelectSplitParams &q, hipStream_t s);
 bool naive_supported(int dtype, int D);
 bool tiled_supported(int dtype, int D);
 bool tiled_v2_supported(int dtype, int D);

@@ -53,7 +53,6 @@ constexpr int IDX_RB = IDX_D * 2;       // bytes of a key row
 constexpr int IDX_TILE = BN * IDX_RB;   // one 64-key tile: 16 KiB
 constexpr int IDX_NW = 4;               // waves of a workgroup
 constexpr int IDX_KS = IDX_D / 32;      // k-steps of a dot
-constexpr int IDX_SEL_THREADS = 256;
 
 // ---- the host rules, on scalars alone
 int mla_indexer_token_block(int max_seqlen_q) { return max_seqlen_q >= 4 ? 4 : max_seqlen_q >= 2 ? 2 : 1; }
@@ -179,36 +178,7 @@ __global__ __launch_bounds__(64 * IDX_NW) void mla_indexer_logits_kernel(MlaInde
   }
 }
 
-// ---- the select kernel
-// exclusive scan of x over the 256 threads of the workgroup, and the total; ws: four ints of LDS
-__device__ __forceinline__ int idx_block_scan(int x, int &total, int *ws) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int incl = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) ws[w] = incl;
-  __syncthreads();
-  int base = 0;
-  total = 0;
-#pragma unroll
-  for (int i = 0; i < IDX_SEL_THREADS / 64; ++i) {
-    const int s = ws[i];
-    base += i < w ? s : 0;
-    total += s;
-  }
-  __syncthreads();  // (ws is rewritten by the next scan)
-  return base + incl - x;
-}
-// the order-preserving image of a logit: a > b as floats iff image(a) > image(b) as unsigned ints, -0 counted as +0
-__device__ __forceinline__ unsigned idx_image(float f) {
-  unsigned u = __builtin_bit_cast(unsigned, f);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
+// ---- the select kernel (idx_block_scan and idx_image: fa_mla_indexer_common.h)
 __global__ __launch_bounds__(IDX_SEL_THREADS) void mla_indexer_select_kernel(MlaIndexerSelectParams p) {
   __shared__ int hist[256];
   __shared__ int ws[IDX_SEL_THREADS / 64];

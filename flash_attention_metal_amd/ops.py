@@ -577,6 +577,16 @@ def mla_indexer_chunk_keys(B: int, max_seqlen_q: int, page_size: int, max_pages_
     return int(load_library().fa_mla_indexer_chunk_keys(B, max_seqlen_q, page_size, max_pages_per_seq))
 
 
+def mla_indexer_select_num_splits(B: int, max_seqlen_q: int, page_size: int, max_pages_per_seq: int) -> int:
+    """The recommended `num_splits` of mla_indexer_select under these scalars (fa_mla_indexer_select_num_splits): 1 where the tokens
+    fill the chip by themselves; 0 if the scalars are illegal."""
+    return int(load_library().fa_mla_indexer_select_num_splits(B, max_seqlen_q, page_size, max_pages_per_seq))
+
+
+def mla_indexer_select_split_workspace_bytes(total_q: int, num_splits: int) -> int:
+    return int(load_library().fa_mla_indexer_select_split_workspace_bytes(total_q, num_splits))
+
+
 def _indexer_inputs(entry: str, q_idx: torch.Tensor, w: torch.Tensor, k_idx_pages: torch.Tensor, k_scale_pages: Optional[torch.Tensor] = None):
     """Shapes, devices and dtypes of either route: 16-bit tensors without scales (the fa_mla_indexer_* calls), or float8_e4m3fn q_idx and
     pool with fp32 k_scale_pages [num_pages, P] (the *_kv8 calls). Anything between raises before the library is called."""
@@ -654,11 +664,14 @@ def mla_indexer_logits(q_idx: torch.Tensor, w: torch.Tensor, k_idx_pages: torch.
 
 def mla_indexer_select(logits: torch.Tensor, cu_seqlens_q: torch.Tensor, block_table: torch.Tensor, seqlens_k: torch.Tensor, topk: int,
                        max_seqlen_q: int, page_size: int, num_pages: int, indices: Optional[torch.Tensor] = None,
-                       index_counts: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                       index_counts: Optional[torch.Tensor] = None, stream: Optional[int] = None, num_splits: Optional[int] = None,
+                       workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """fp32 logits -> (indices int32 [total_q, >= topk], index_counts int32 [total_q]) as flash_attention_mla_decode_sparse takes them
     (include/fa_mi355.h fa_mla_indexer_select): per token the min(topk, v) best visible keys under (logit descending, position
     ascending), written in ascending position as pool slots, -1 under a page entry outside the pool. Entries behind the count are not
-    written (allocated UNINITIALISED if `indices` is None)."""
+    written (allocated UNINITIALISED if `indices` is None). `num_splits` >= 2 goes to fa_mla_indexer_select_split: that many workgroups
+    share a token's row (mla_indexer_select_num_splits recommends a value), on a uint8 `workspace` of at least
+    mla_indexer_select_split_workspace_bytes(total_q, num_splits) bytes (allocated here if None); the lists are the same bits."""
     lib = load_library()
     if logits.dim() != 2 or not logits.is_cuda:
         raise ValueError("logits must be an fp32 [total_q, >= max_pages_per_seq * P] device tensor with a unit last stride")
@@ -667,6 +680,14 @@ def mla_indexer_select(logits: torch.Tensor, cu_seqlens_q: torch.Tensor, block_t
     mp = block_table.shape[1]
     logits = _indexer_logits_buffer(logits, T, int(page_size) * mp, logits.device)
     indices, index_counts, istride = _indexer_lists(indices, index_counts, T, int(topk), logits.device)
+    if num_splits is not None and int(num_splits) != 1:
+        ws = _workspace(workspace, mla_indexer_select_split_workspace_bytes(T, int(num_splits)), logits.device)
+        _call(lib, "fa_mla_indexer_select_split",
+              (logits.data_ptr(), indices.data_ptr(), index_counts.data_ptr(), cu_seqlens_q.data_ptr(), block_table.data_ptr(),
+               seqlens_k.data_ptr(), B, T, int(max_seqlen_q), int(topk), int(page_size), int(num_pages), mp,
+               logits.stride(0) if T > 1 else logits.shape[1], istride, block_table.stride(0), int(num_splits), ws.data_ptr(), ws.numel()),
+              logits.device, stream)
+        return indices, index_counts
     _call(lib, "fa_mla_indexer_select",
           (logits.data_ptr(), indices.data_ptr(), index_counts.data_ptr(), cu_seqlens_q.data_ptr(), block_table.data_ptr(),
            seqlens_k.data_ptr(), B, T, int(max_seqlen_q), int(topk), int(page_size), int(num_pages), mp,
@@ -678,18 +699,32 @@ def flash_attention_mla_indexer_topk(q_idx: torch.Tensor, w: torch.Tensor, k_idx
                                      block_table: torch.Tensor, seqlens_k: torch.Tensor, topk: int, max_seqlen_q: int,
                                      indices: Optional[torch.Tensor] = None, index_counts: Optional[torch.Tensor] = None,
                                      workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None,
-                                     k_scale_pages: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                                     k_scale_pages: Optional[torch.Tensor] = None,
+                                     select_splits: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The MLA indexer (include/fa_mi355.h fa_mla_indexer_topk_paged): mla_indexer_logits, then mla_indexer_select, on a workspace that
     holds the logits. q_idx [total_q,Hi,128] f16 / bf16 (Hi 32 or 64), w [total_q,Hi] fp32, k_idx_pages [num_pages,P,128] like q_idx;
     the three tables are flash_attention_varlen_paged's, device tensors the host never reads. Returns (indices, index_counts), which
     flash_attention_mla_decode_sparse takes as they are. `workspace`: a uint8 device tensor of at least
     mla_indexer_workspace_bytes(total_q, P, max_pages_per_seq) bytes (allocated here if None). float8_e4m3fn q_idx and pool with fp32
-    `k_scale_pages` go to fa_mla_indexer_topk_paged_kv8, as in mla_indexer_logits."""
+    `k_scale_pages` go to fa_mla_indexer_topk_paged_kv8, as in mla_indexer_logits. With `select_splits` (not None) the two stages are
+    called one after the other, mla_indexer_logits (either dtype route) into the front of the workspace and
+    mla_indexer_select(num_splits=select_splits) on the rest: the workspace is then at least mla_indexer_workspace_bytes(total_q, P,
+    max_pages_per_seq) + mla_indexer_select_split_workspace_bytes(total_q, select_splits) bytes, the SUM of the two size functions."""
     lib = load_library()
     T, Hi, Di, wrs = _indexer_inputs("flash_attention_mla_indexer_topk", q_idx, w, k_idx_pages, k_scale_pages)
     B = _tables("flash_attention_mla_indexer_topk", cu_seqlens_q, "cu_seqlens_q", block_table, seqlens_k)
     num_pages, P = k_idx_pages.shape[0], k_idx_pages.shape[1]
     mp = block_table.shape[1]
+    if select_splits is not None:
+        front = mla_indexer_workspace_bytes(T, P, mp)
+        ws = _workspace(workspace, front + mla_indexer_select_split_workspace_bytes(T, int(select_splits)), q_idx.device)
+        if front < 1 or ws.numel() < front:
+            raise ValueError("workspace smaller than mla_indexer_workspace_bytes + mla_indexer_select_split_workspace_bytes")
+        logits = ws[:front].view(torch.float32).view(T, P * mp)
+        mla_indexer_logits(q_idx, w, k_idx_pages, cu_seqlens_q, block_table, seqlens_k, max_seqlen_q, logits=logits, stream=stream,
+                           k_scale_pages=k_scale_pages)
+        return mla_indexer_select(logits, cu_seqlens_q, block_table, seqlens_k, topk, max_seqlen_q, P, num_pages, indices=indices,
+                                  index_counts=index_counts, stream=stream, num_splits=int(select_splits), workspace=ws[front:])
     indices, index_counts, istride = _indexer_lists(indices, index_counts, T, int(topk), q_idx.device)
     ws = _workspace(workspace, mla_indexer_workspace_bytes(T, P, mp), q_idx.device)
     if k_scale_pages is not None:

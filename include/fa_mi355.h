@@ -1194,6 +1194,40 @@ int fa_mla_indexer_topk_paged_kv8(const void *q_idx, const float *w, const void 
 int fa_mla_indexer_kv8_supported(int q_dtype, int kv_dtype, int Hi, int Di, int page_size);   /* e4m3, e4m3, 32 | 64, 128, 16 .. 256 */
 
 /*
+ * The MLA indexer's select over several workgroups: fa_mla_indexer_select_split is fa_mla_indexer_select -- item 2 of "The MLA
+ * indexer", word for word: the counts, the total order, ascending position, slots and -1, every footprint, v <= topk without a read
+ * of the logits, distinct visible positions for any bits -- with a token's row split over num_splits workgroups. Because the order is
+ * total, indices and index_counts are BIT-IDENTICAL to fa_mla_indexer_select's for every input whose logits hold no NaN. It is for the
+ * serving shape on which that call leaves the chip idle: a few long sequences, one token each.
+ * The first 16 arguments are fa_mla_indexer_select's, in order. num_splits = S is in 1 .. 64; S = 1 launches fa_mla_indexer_select's
+ * kernel and looks at no workspace (NULL is legal). For S >= 2 the caller gives a 16-byte aligned workspace of
+ * fa_mla_indexer_select_split_workspace_bytes(total_q, S) bytes (0: total_q < 1 or S outside 1 .. 64); results do not depend on its
+ * prior contents. fa_mla_indexer_select_num_splits(B, max_seqlen_q, P, max_pages_per_seq) recommends S (0: illegal scalars): as few
+ * splits as give 512 workgroups, no segment under 1024 keys where the capacity has them, at most 64 -- 1 once B * max_seqlen_q
+ * reaches 512.
+ * Asynchronous on hip_stream, allocates nothing; the grid, B * max_seqlen_q * S, depends on host scalars alone, so one captured graph
+ * of the logits call and this one serves every step; results are bitwise reproducible (no global atomics).
+ * Every rule of fa_mla_indexer_select keeps its status and its text after the function name. Of this call's own, each
+ * FA_ERR_INVALID_ARG before any launch: num_splits outside 1 .. 64, a workspace that is not 16-byte aligned, NULL with S >= 2 or too
+ * small, a grid that does not fit an int.
+ * How it runs (csrc/fa_mla_indexer_select_split_kernel.hip): the capacity is cut into S segments of
+ * roundup64(ceil(capacity / S)) keys, one workgroup of 256 threads each, and the radix select is a chain of five plain launches on the
+ * stream: four that build one 256-bin histogram per segment and digit, each first re-deriving the digit before from all segments'
+ * histograms, and one that resolves the last digit and emits its segment's keys at (greater in front) + min(equals in front, need).
+ * No workgroup waits for another: no cooperative launch, no flags, no global atomics.
+ * Not here: a default that routes the existing calls here (fa_mla_indexer_topk_paged and _kv8 are unchanged: call the logits, then this);
+ * a fused logits-and-select kernel; splitting prefill-sized token counts, which fill the chip already.
+ */
+int fa_mla_indexer_select_split(const float *logits, int *indices, int *index_counts,
+                                const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
+                                int B, int total_q, int max_seqlen_q, int topk,
+                                int page_size, int num_pages, int max_pages_per_seq,
+                                long long logits_stride, long long indices_stride, long long block_table_stride,
+                                int num_splits, void *workspace, long long workspace_bytes, void *hip_stream);
+long long fa_mla_indexer_select_split_workspace_bytes(int total_q, int num_splits);   /* 0: illegal */
+int fa_mla_indexer_select_num_splits(int B, int max_seqlen_q, int page_size, int max_pages_per_seq);   /* 0: illegal scalars */
+
+/*
  * Multi-head latent attention (prefill): fa_fwd_varlen_mla is the NON-absorbed form of the same layer, as serving engines run its
  * prefill: the latent rows are up-projected to per-head keys and values, and ordinary multi-head attention runs over packed sequences
  * with a query / key head dim of Dqk = 192 (128 "nope" + 64 rotary) and a value head dim of Dv = 128. Per sequence the operator is
