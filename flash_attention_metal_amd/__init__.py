@@ -45,8 +45,11 @@ from .ops import (  # noqa: F401
     mla_decode_sparse_supported,
     mla_decode_sparse_workspace_bytes,
     mla_indexer_chunk_keys,
+    mla_indexer_k_append_quant,
     mla_indexer_kv8_supported,
     mla_indexer_logits,
+    mla_indexer_q_quant,
+    mla_indexer_quant_supported,
     mla_indexer_select,
     mla_indexer_select_num_splits,
     mla_indexer_select_split_workspace_bytes,

@@ -53,6 +53,9 @@ SYMBOLS = {
     "fa_mla_indexer_logits_paged_kv8": (c_int, [c_void_p] * 8 + [c_int] * 8 + [c_longlong] * 8 + [c_int, c_int, c_void_p]),
     "fa_mla_indexer_topk_paged_kv8": (c_int, [c_void_p] * 9 + [c_int] * 9 + [c_longlong] * 8 + [c_int, c_int, c_void_p, c_longlong, c_void_p]),
     "fa_mla_indexer_kv8_supported": (c_int, [c_int] * 5),
+    "fa_mla_indexer_k_append_paged_quant": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_longlong] * 5 + [c_int, c_int, c_void_p]),
+    "fa_mla_indexer_q_quant": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_float] + [c_longlong] * 6 + [c_int, c_int, c_void_p]),
+    "fa_mla_indexer_quant_supported": (c_int, [c_int] * 2),
     "fa_mla_indexer_select_split": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_longlong] * 3 + [c_int, c_void_p, c_longlong, c_void_p]),
     "fa_mla_indexer_select_split_workspace_bytes": (c_longlong, [c_int] * 2),
     "fa_mla_indexer_select_num_splits": (c_int, [c_int] * 4),

@@ -1226,6 +1226,69 @@ int fa_mla_indexer_topk_paged_kv8(const void *q_idx, const float *w, const void 
   TRY(launched(fn, fa::launch_mla_indexer_logits_kv8(pl, Hi, (hipStream_t)hip_stream)));
   return launched(fn, fa::launch_mla_indexer_select(ps, (hipStream_t)hip_stream));
 }
+// ---- the e4m3 indexer's input stage (csrc/fa_mla_indexer_quant_kernel.hip): what the two *_kv8 calls above read, written by the library.
+// fa_mla_indexer_k_append_paged_quant: fa_mla_kv_append_paged_scaled's rules in its order, the pool under the kv8 logits call's (byte)
+// stride rule, then the scales' rules (mla_indexer_scales_ok). fa_mla_indexer_q_quant: the 16-bit indexer call's stride rule for q_idx.
+int fa_mla_indexer_quant_supported(int dtype, int Di) { return (dtype == FA_DTYPE_F16 || dtype == FA_DTYPE_BF16) && Di == 128; }
+int fa_mla_indexer_k_append_paged_quant(const void *k_new, void *k_idx_pages, float *k_scale_pages, const int *cu_seqlens_new,
+                                        const int *block_table, const int *seqlens_k, int B, int total_new, int max_seqlen_new, int Di,
+                                        int page_size, int num_pages, int max_pages_per_seq, long long new_row_stride,
+                                        long long k_page_stride, long long k_row_stride, long long k_scale_page_stride,
+                                        long long block_table_stride, int rotate, int new_dtype, void *hip_stream) {
+  const char *fn = "fa_mla_indexer_k_append_paged_quant";
+  g_err[0] = 0;
+  TRY(nonnull(fn, {k_new, k_idx_pages, cu_seqlens_new, block_table, seqlens_k}));
+  TRY(positive(fn, {B, total_new, max_seqlen_new, Di, page_size, num_pages, max_pages_per_seq}));
+  if (!fa_mla_indexer_quant_supported(new_dtype, Di) || !fa::page_size_ok(page_size))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 new rows of Di = 128 elements (the pool is fp8_e4m3 with a scale per key) and a page "
+                "size of 16, 32, 64, 128 or 256; got new_dtype=%s Di=%d page_size=%d", fn, fa_dtype_name(new_dtype), Di, page_size);
+  if (max_seqlen_new > total_new)
+    return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen_new=%d exceeds the token count %d", fn, max_seqlen_new, total_new);
+  TRY(varlen_strides_ok(fn, "new key/value ", Di, new_row_stride, new_row_stride, stride_mult(new_dtype)));
+  TRY(page_pool_ok(fn, Di, page_size, max_pages_per_seq, k_page_stride, k_row_stride, k_row_stride, block_table_stride, FA_DTYPE_FP8_E4M3,
+                   block_table, seqlens_k));
+  TRY(aligned16(fn, "tensors", {k_new, k_idx_pages}));
+  if ((uintptr_t)cu_seqlens_new & 3) return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens_new must be int32-aligned", fn);
+  TRY(mla_indexer_scales_ok(fn, k_scale_pages, k_scale_page_stride, page_size));
+  if ((long long)B * ((max_seqlen_new + 3) / 4) > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  fa::MlaIndexerKQuantParams q = {};
+  fa::AppendPagedParams &p = q.a;
+  p.k_new = k_new; p.k_pages = k_idx_pages;
+  p.cu_new = cu_seqlens_new; p.block_table = block_table; p.seqlens = seqlens_k;
+  p.B = B; p.Hkv = 1; p.total_new = total_new; p.max_new = max_seqlen_new; p.D = Di;
+  p.new_rs = new_row_stride;
+  p.page_stride = k_page_stride; p.row_stride = k_row_stride;
+  p.bt_stride = (int)block_table_stride; p.num_pages = num_pages; p.max_pages = max_pages_per_seq;
+  p.lp = log2_of(page_size);
+  q.k_scale = k_scale_pages; q.scale_page_stride = k_scale_page_stride;
+  return launched(fn, fa::launch_mla_indexer_k_quant(q, new_dtype, rotate != 0, (hipStream_t)hip_stream));
+}
+int fa_mla_indexer_q_quant(const void *q_idx, const float *head_w, void *q_out, float *w_out, int total_q, int Hi, int Di, float w_mul,
+                           long long q_row_stride, long long q_head_stride, long long w_row_stride, long long qo_row_stride,
+                           long long qo_head_stride, long long wo_row_stride, int rotate, int dtype, void *hip_stream) {
+  const char *fn = "fa_mla_indexer_q_quant";
+  g_err[0] = 0;
+  TRY(nonnull(fn, {q_idx, head_w, q_out, w_out}));
+  TRY(positive(fn, {total_q, Hi, Di}));
+  if (!fa_mla_indexer_quant_supported(dtype, Di))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 index queries of Di = 128 elements; got dtype=%s Di=%d", fn, fa_dtype_name(dtype), Di);
+  if (!(w_mul > 0.0f && w_mul <= 3.4028234663852886e38f))  // (the negated form refuses NaN as well)
+    return fail(FA_ERR_INVALID_ARG, "%s: w_mul=%g must be > 0 and finite", fn, (double)w_mul);
+  TRY(varlen_strides_ok(fn, "", Di, q_row_stride, q_head_stride, stride_mult(dtype)));
+  TRY(varlen_strides_ok(fn, "output ", Di, qo_row_stride, qo_head_stride, stride_mult(FA_DTYPE_FP8_E4M3)));  // bytes
+  TRY(aligned16(fn, "tensors", {q_idx, q_out}));
+  if ((uintptr_t)head_w & 3) return fail(FA_ERR_INVALID_ARG, "%s: head_w must be fp32-aligned", fn);
+  if ((uintptr_t)w_out & 3) return fail(FA_ERR_INVALID_ARG, "%s: w_out must be fp32-aligned", fn);
+  if (w_row_stride < Hi) return fail(FA_ERR_INVALID_ARG, "%s: w_row_stride=%lld < Hi=%d", fn, w_row_stride, Hi);
+  if (wo_row_stride < Hi) return fail(FA_ERR_INVALID_ARG, "%s: wo_row_stride=%lld < Hi=%d", fn, wo_row_stride, Hi);
+  if ((long long)total_q * Hi > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  fa::MlaIndexerQQuantParams q = {};
+  q.q = q_idx; q.head_w = head_w; q.q_out = q_out; q.w_out = w_out;
+  q.rows = (unsigned)total_q * (unsigned)Hi; q.Hi = Hi; q.w_mul = w_mul;
+  q.q_rs = q_row_stride; q.q_hs = q_head_stride; q.w_rs = w_row_stride;
+  q.qo_rs = qo_row_stride; q.qo_hs = qo_head_stride; q.wo_rs = wo_row_stride;
+  return launched(fn, fa::launch_mla_indexer_q_quant(q, dtype, rotate != 0, (hipStream_t)hip_stream));
+}
 
 int fa_fwd_varlen_paged_supported(int dtype, int D, int page_size) { return fa::mfma_varlen_paged_supported(dtype, D, page_size); }
 // the key split's scalars: sizes >= 1, a head_dim and a page size the paged prefill has, a capacity of at most 2^30 keys

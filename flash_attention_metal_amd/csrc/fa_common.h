@@ -328,6 +328,28 @@ hipError_t launch_kv_append_paged_quant(const AppendPagedParams &p, int new_dtyp
 // k_new holds the bf16 rows [total_new, 576] (new_rs in elements), k_pages the pool (page_stride / row_stride in BYTES); v_*, new_hs,
 // head_stride and D are not read. Four new rows per workgroup, one wave each
 hipError_t launch_mla_kv_append_paged_scaled(const AppendPagedParams &p, hipStream_t s);
+// fa_mla_indexer_k_append_paged_quant (csrc/fa_mla_indexer_quant_kernel.hip): the same placement with Hkv = 1 into the e4m3 index cache:
+// a.k_new holds the 16-bit rows [total_new, 128] (new_rs in elements), a.k_pages the code bytes (page_stride / row_stride in BYTES);
+// key `row` of `page` has its fp32 scale at k_scale[page * scale_page_stride + row]. Four new rows per workgroup, one wave each
+struct MlaIndexerKQuantParams {
+  AppendPagedParams a;
+  float *k_scale;
+  long long scale_page_stride;  // floats
+};
+hipError_t launch_mla_indexer_k_quant(const MlaIndexerKQuantParams &q, int new_dtype, int rotate, hipStream_t s);
+// fa_mla_indexer_q_quant: q [total_q, Hi, 128] 16-bit under element strides -> q_out e4m3 under byte strides; w_out = (head_w * w_mul) * 2^e.
+// rows = total_q * Hi, one wave each
+struct MlaIndexerQQuantParams {
+  const void *q;
+  const float *head_w;
+  void *q_out;
+  float *w_out;
+  unsigned rows;
+  int Hi;
+  float w_mul;
+  long long q_rs, q_hs, w_rs, qo_rs, qo_hs, wo_rs;
+};
+hipError_t launch_mla_indexer_q_quant(const MlaIndexerQQuantParams &q, int dtype, int rotate, hipStream_t s);
 hipError_t launch_mfma_split2(const Params &p, int dtype, hipStream_t s);
 bool mfma_split2_supported(int dtype, int D);
 hipError_t launch_mfma_h64s2(const Params &p, int dtype, hipStream_t s);

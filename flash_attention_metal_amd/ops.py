@@ -1117,6 +1117,86 @@ def mla_kv_append_paged_scaled(
            kv_pages.stride(1), block_table.stride(0), _TORCH2FA[kv_new.dtype]), kv_pages.device, stream)
 
 
+def mla_indexer_quant_supported(dtype: str, Di: int) -> bool:
+    return bool(load_library().fa_mla_indexer_quant_supported(DTYPES[dtype], Di))
+
+
+def mla_indexer_k_append_quant(
+    k_new: torch.Tensor,
+    k_idx_pages: torch.Tensor,
+    k_scale_pages: torch.Tensor,
+    cu_seqlens_new: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens_k: torch.Tensor,
+    max_seqlen_new: int,
+    rotate: bool = True,
+    stream: Optional[int] = None,
+) -> None:
+    """Rotate, quantise and append new index keys into the e4m3 index cache, in place (include/fa_mi355.h
+    fa_mla_indexer_k_append_paged_quant): k_new [total_new, 128] f16 / bf16 with a unit last stride; k_idx_pages float8_e4m3fn (or uint8)
+    [num_pages, P, 128] and k_scale_pages fp32 [num_pages, P], any views with a unit last stride -- the two tensors mla_indexer_logits
+    takes, the views of a packed 132-byte-per-key page included. Per row: the 128-point Hadamard rotation (rotate), a power-of-two scale
+    2^e, the smallest with amax <= 448 * 2^e (e in [-32, 32]), the codes e4m3_rne(clamp(y * 2^-e, -448, 448)). Tables, placement and
+    skipping are kv_append_paged's: seqlens_k holds the lengths AFTER the append. Exactly 128 code bytes and one scale per written key
+    are written. Nothing here synchronises or reads device values: graph-capturable."""
+    lib = load_library()
+    entry = "mla_indexer_k_append_quant"
+    if (k_idx_pages.dtype not in (torch.uint8, _FP8) or k_idx_pages.dim() != 3 or k_idx_pages.shape[2] != 128 or k_idx_pages.stride(2) != 1):
+        raise ValueError(f"k_idx_pages one float8_e4m3fn / uint8 [num_pages,P,128] pool with a unit last stride, got {tuple(k_idx_pages.shape)} "
+                         f"{k_idx_pages.dtype}")
+    if k_scale_pages.dtype != torch.float32 or k_scale_pages.shape != k_idx_pages.shape[:2] or k_scale_pages.stride(1) != 1:
+        raise ValueError("k_scale_pages must be an fp32 [num_pages, P] tensor with a unit last stride")
+    if k_new.dtype not in (torch.float16, torch.bfloat16) or k_new.dim() != 2 or k_new.shape[1] != 128 or k_new.stride(1) != 1:
+        raise ValueError(f"k_new one f16 / bf16 [total_new,128] tensor with a unit last stride, got {tuple(k_new.shape)} {k_new.dtype}")
+    B = _tables(entry, cu_seqlens_new, "cu_seqlens_new", block_table, seqlens_k)
+    if not all(t.is_cuda and t.device == k_idx_pages.device for t in (k_new, k_idx_pages, k_scale_pages, cu_seqlens_new, block_table, seqlens_k)):
+        raise RuntimeError("mla_indexer_k_append_quant needs the new rows, the pool, the scales and the tables on one device: there is no CPU path")
+    num_pages, P = k_idx_pages.shape[0], k_idx_pages.shape[1]
+    _call(lib, "fa_mla_indexer_k_append_paged_quant",
+          (k_new.data_ptr(), k_idx_pages.data_ptr(), k_scale_pages.data_ptr(), cu_seqlens_new.data_ptr(), block_table.data_ptr(),
+           seqlens_k.data_ptr(), B, k_new.shape[0], int(max_seqlen_new), 128, P, num_pages, block_table.shape[1], k_new.stride(0),
+           k_idx_pages.stride(0), k_idx_pages.stride(1), k_scale_pages.stride(0) if num_pages > 1 else P, block_table.stride(0),
+           int(bool(rotate)), _TORCH2FA[k_new.dtype]), k_idx_pages.device, stream)
+
+
+def mla_indexer_q_quant(
+    q_idx: torch.Tensor,
+    head_w: torch.Tensor,
+    w_mul: float = 1.0,
+    rotate: bool = True,
+    q_out: Optional[torch.Tensor] = None,
+    w_out: Optional[torch.Tensor] = None,
+    stream: Optional[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Rotate and quantise index queries for the e4m3 indexer (include/fa_mi355.h fa_mla_indexer_q_quant): q_idx [total_q, Hi, 128]
+    f16 / bf16, head_w [total_q, Hi] fp32, unit last strides. Returns (q_fp8, w): q_fp8 float8_e4m3fn [total_q, Hi, 128] holds every
+    (token, head) row under mla_indexer_k_append_quant's row rule, and w[t, h] = (head_w[t, h] * w_mul) * 2^e carries the row's scale --
+    the q_idx and w mla_indexer_logits takes beside an e4m3 pool. Fold the softmax scale and Hi^-0.5 into w_mul (> 0, finite). q_out /
+    w_out: preallocated outputs (views with a unit last stride; w_out may be head_w itself), allocated here if None."""
+    lib = load_library()
+    if q_idx.dtype not in (torch.float16, torch.bfloat16) or q_idx.dim() != 3 or q_idx.shape[2] != 128 or q_idx.stride(2) != 1:
+        raise ValueError(f"q_idx one f16 / bf16 [total_q,Hi,128] tensor with a unit last stride, got {tuple(q_idx.shape)} {q_idx.dtype}")
+    T, Hi, _ = q_idx.shape
+    if head_w.dtype != torch.float32 or head_w.shape != (T, Hi) or head_w.stride(1) != 1:
+        raise ValueError(f"head_w must be an fp32 [total_q, Hi] tensor with a unit last stride, got {tuple(head_w.shape)} {head_w.dtype}")
+    if q_out is None:
+        q_out = torch.empty((T, Hi, 128), dtype=_FP8, device=q_idx.device)
+    elif q_out.dtype not in (torch.uint8, _FP8) or q_out.shape != q_idx.shape or q_out.stride(2) != 1:
+        raise ValueError("q_out must be a float8_e4m3fn / uint8 [total_q, Hi, 128] tensor with a unit last stride")
+    if w_out is None:
+        w_out = torch.empty((T, Hi), dtype=torch.float32, device=q_idx.device)
+    elif w_out.dtype != torch.float32 or w_out.shape != (T, Hi) or w_out.stride(1) != 1:
+        raise ValueError("w_out must be an fp32 [total_q, Hi] tensor with a unit last stride")
+    if not all(t.is_cuda and t.device == q_idx.device for t in (q_idx, head_w, q_out, w_out)):
+        raise RuntimeError("mla_indexer_q_quant needs q_idx, head_w and the outputs on one device: there is no CPU path")
+    row = lambda t: t.stride(0) if T > 1 else Hi * t.shape[-1] if t.dim() == 3 else Hi
+    _call(lib, "fa_mla_indexer_q_quant",
+          (q_idx.data_ptr(), head_w.data_ptr(), q_out.data_ptr(), w_out.data_ptr(), T, Hi, 128, float(w_mul), row(q_idx),
+           q_idx.stride(1) if Hi > 1 else 128, row(head_w), row(q_out), q_out.stride(1) if Hi > 1 else 128, row(w_out), int(bool(rotate)),
+           _TORCH2FA[q_idx.dtype]), q_idx.device, stream)
+    return q_out, w_out
+
+
 def varlen_backward_supported(dtype: str, D: int) -> bool:
     return bool(load_library().fa_bwd_varlen_supported(DTYPES[dtype], D))
 

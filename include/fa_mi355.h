@@ -1172,8 +1172,9 @@ int fa_mla_indexer_supported(int dtype, int Hi, int Di, int page_size);   /* f16
  * around a score tile of its own -- one v_mfma_f32_16x16x128_f8f6f4 (unit E8M0 scales) is the whole 128-column dot of 16 heads against
  * 16 keys; a token's query is Hi / 16 fragments of 32 bytes per lane; a 64-key tile is 8 KiB, rows of 128 bytes under the swizzle
  * k ^ ((r >> 1) & 7); the scale reaches the storing lane by a predicated global load one tile ahead.
- * Not here: a quantising append for index keys; E8M0 or block scales fed to the matrix instruction; e4m3 queries against 16-bit keys or
- * the reverse; a fused logits-and-select kernel; Di other than 128, Hi other than 32 / 64. No existing call is rerouted.
+ * Not here (the quantising append for index keys and the query's quantisation: "The MLA indexer's input stage", below): E8M0 or block
+ * scales fed to the matrix instruction; e4m3 queries against 16-bit keys or the reverse; a fused logits-and-select kernel; Di other than
+ * 128, Hi other than 32 / 64. No existing call is rerouted.
  */
 int fa_mla_indexer_logits_paged_kv8(const void *q_idx, const float *w, const void *k_idx_pages, const float *k_scale_pages, float *logits,
                                     const int *cu_seqlens_q, const int *block_table, const int *seqlens_k,
@@ -1192,6 +1193,74 @@ int fa_mla_indexer_topk_paged_kv8(const void *q_idx, const float *w, const void 
                                   long long block_table_stride, long long indices_stride, int q_dtype, int kv_dtype,
                                   void *workspace, long long workspace_bytes, void *hip_stream);
 int fa_mla_indexer_kv8_supported(int q_dtype, int kv_dtype, int Hi, int Di, int page_size);   /* e4m3, e4m3, 32 | 64, 128, 16 .. 256 */
+
+/*
+ * The MLA indexer's input stage: fa_mla_indexer_k_append_paged_quant and fa_mla_indexer_q_quant WRITE what the two e4m3 calls above read
+ * -- the index cache of e4m3 keys with one fp32 scale per key, and the e4m3 index query whose per-(token, head) scale is folded into w --
+ * from the 16-bit rows the indexer's projections produce: rotate, quantise, append. The arithmetic is fixed operation by operation, so
+ * a plain fp32 model reproduces every byte.
+ * THE ROW RULE (both calls). A row is 128 elements of f16 or bf16, widened to fp32 as x[0..127].
+ *  1. rotate != 0: seven butterfly stages s = 0 .. 6 in that order; in stage s, for every i with bit s clear,
+ *         (x[i], x[i + 2^s]) <- (x[i] + x[i + 2^s], x[i] - x[i + 2^s]),
+ *     each one IEEE fp32 add or subtract as written; then y[i] = x[i] * c, c = fp32(128^-0.5), one fp32 multiply. This is the
+ *     Sylvester-ordered Hadamard transform H[i][j] = (-1)^popcount(i & j), scaled to be orthonormal -- the rotation the models apply
+ *     to index queries and keys before quantising, so that outliers are spread. rotate == 0: y = x.
+ *  2. amax = max_i |y[i]|; e is the smallest integer in [-32, 32] with amax <= 448 * 2^e (an all-zero row gets -32; a row too large
+ *     saturates through the clamp).
+ *  3. s = 2^e as fp32; code[i] = e4m3_rne(clamp(y[i] * 2^-e, -448, 448)), clamped BEFORE the conversion: fa_mla_kv_append_paged_scaled's
+ *     rule on one group of 128, with its conversion.
+ * The results are guaranteed BIT FOR BIT for finite inputs whose non-zero magnitudes lie in [2^-60, 2^60] (no fp32 subnormal can arise);
+ * outside that range the values are unspecified, but no address depends on them. The matrix core is deliberately not used for the
+ * rotation: its accumulation order is not part of any contract, and the bytes of a cache must not depend on it.
+ *
+ * 1. fa_mla_indexer_k_append_paged_quant. k_new is [total_new, 128] f16 or bf16 under new_row_stride (elements: a multiple of 8, at
+ *    least 128, base 16-byte aligned). cu_seqlens_new, block_table, seqlens_k, placement and skipping are fa_mla_kv_append_paged_scaled's
+ *    word for word: seqlens_k is the length AFTER the append, token i of sequence b goes to key position seqlens_k[b] - n_b + i, and a
+ *    position below 0, at or above the capacity, or on a table entry outside [0, num_pages) is skipped. The output is addressed exactly
+ *    as fa_mla_indexer_logits_paged_kv8 reads it: the codes at BYTE page * k_page_stride + row * k_row_stride of k_idx_pages (bytes:
+ *    multiples of 16, at least 128, base 16-byte aligned, one page below 2 GiB), the scale at FLOAT page * k_scale_page_stride + row of
+ *    k_scale_pages (4-byte aligned, k_scale_page_stride >= P). Both layouts documented there work unchanged: a separate [num_pages, P]
+ *    fp32 array, and the packed page of 132 P bytes (k_scale_pages = the pool's base + 128 P bytes, k_scale_page_stride = 33 P).
+ *    The footprint is exactly 128 code bytes and 4 scale bytes per written key: no other slot, nothing between rows or pages, nothing
+ *    for tokens nobody owns.
+ *    new_dtype f16 | bf16, Di = 128, P in {16, 32, 64, 128, 256}: anything else FA_ERR_UNSUPPORTED with a message that names what was
+ *    given. Every rule shared with fa_mla_kv_append_paged_scaled or the e4m3 logits call keeps that call's status and its text after
+ *    the function name. Of this call's own, each FA_ERR_INVALID_ARG before any launch: k_scale_pages null or not 4-byte aligned,
+ *    k_scale_page_stride < P.
+ * 2. fa_mla_indexer_q_quant. q_idx is [total_q, Hi, 128] f16 or bf16 under the row / head ELEMENT strides of fa_mla_indexer_logits_paged
+ *    (multiples of 8, at least 128, base 16-byte aligned); q_out receives the e4m3 bytes under row / head BYTE strides (multiples of 16,
+ *    at least 128, base 16-byte aligned) -- what the e4m3 calls take as q_idx. Every (token, head) row goes through the row rule, and
+ *        w_out[t][h] = fl(head_w[t][h] * w_mul) * 2^e
+ *    one rounded fp32 multiply, then an exact one -- what the e4m3 calls take as w. head_w and w_out are fp32 [total_q, Hi] under row
+ *    strides >= Hi (4-byte aligned); w_mul is finite and > 0: the caller folds the softmax scale and Hi^-0.5 into it. w_out == head_w
+ *    under equal strides is legal. Hi >= 1. q_out's rows and w_out[t][0 .. Hi) are written and nothing else.
+ *    dtype f16 | bf16, Di = 128: anything else FA_ERR_UNSUPPORTED with a message that names what was given. q_idx's strides carry the
+ *    16-bit indexer call's status and text. Of this call's own, each FA_ERR_INVALID_ARG before any launch: w_mul not finite or not > 0,
+ *    bad output strides, head_w or w_out not 4-byte aligned, w_row_stride or wo_row_stride < Hi, total_q * Hi above 2^31 - 1.
+ * Both calls: the kernels read the tables, the host never does; the grids (B * ceil(max_seqlen_new / 4), ceil(total_q * Hi / 4)
+ * workgroups of four waves, one wave per row) depend on host scalars alone. Asynchronous on hip_stream, allocate nothing, can be
+ * captured in a graph, bitwise reproducible (no atomics).
+ * How it runs (csrc/fa_mla_indexer_quant_kernel.hip): lane l of a row's wave holds elements 2 l and 2 l + 1, so
+ * one butterfly stage is in-lane and six are lane exchanges (DPP for lane ^ 1, 2, 4, 8; v_permlane16_swap / v_permlane32_swap for
+ * lane ^ 16, 32); the lane holding the upper element of a pair computes partner - own; amax is an integer max over the same exchanges,
+ * the exponent integer arithmetic on its bits; the codes leave the wave as 32 stores of 4 bytes.
+ * fa_mla_indexer_quant_supported(dtype, Di): 1 for (f16 | bf16, 128).
+ * Not here: scales that are no power of two (amax / 448); the indexer's projections, LayerNorm and rotary; Di other than 128; E8M0
+ * scale bytes; a fused quantise-and-logits kernel. No existing call is rerouted.
+ */
+int fa_mla_indexer_k_append_paged_quant(const void *k_new, void *k_idx_pages, float *k_scale_pages,
+                                        const int *cu_seqlens_new, const int *block_table, const int *seqlens_k,
+                                        int B, int total_new, int max_seqlen_new, int Di,
+                                        int page_size, int num_pages, int max_pages_per_seq,
+                                        long long new_row_stride, long long k_page_stride, long long k_row_stride,
+                                        long long k_scale_page_stride, long long block_table_stride,
+                                        int rotate, int new_dtype, void *hip_stream);
+int fa_mla_indexer_q_quant(const void *q_idx, const float *head_w, void *q_out, float *w_out,
+                           int total_q, int Hi, int Di, float w_mul,
+                           long long q_row_stride, long long q_head_stride, long long w_row_stride,
+                           long long qo_row_stride, long long qo_head_stride, long long wo_row_stride,
+                           int rotate, int dtype, void *hip_stream);
+int fa_mla_indexer_quant_supported(int dtype, int Di);   /* f16 | bf16, 128 */
 
 /*
  * The MLA indexer's select over several workgroups: fa_mla_indexer_select_split is fa_mla_indexer_select -- item 2 of "The MLA
