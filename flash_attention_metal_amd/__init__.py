@@ -25,6 +25,7 @@ from .ops import (  # noqa: F401
     flash_attention_mla_decode_paged,
     flash_attention_mla_decode_sparse,
     flash_attention_mla_indexer_topk,
+    flash_attention_mla_sparse_backward,
     flash_attention_varlen,
     flash_attention_varlen_backward,
     flash_attention_varlen_mla,
@@ -56,6 +57,8 @@ from .ops import (  # noqa: F401
     mla_indexer_supported,
     mla_indexer_workspace_bytes,
     mla_kv_append_paged_scaled,
+    mla_sparse_backward_supported,
+    mla_sparse_backward_workspace_bytes,
     supported,
     varlen_backward_supported,
     varlen_backward_workspace_bytes,

@@ -852,7 +852,42 @@ long long fa_fwd_mla_decode_sparse_workspace_bytes(int T, int Hq, int Dv, int to
 // pool's (the other mode: both are `dtype`). The dtype-pair rule and the pool's stride multiple are all that differ.
 // MLA_SPARSE_KV8_SCALED: that mode over rows of 656 bytes (fa_mla_sparse_kv8_scaled_kernel.hip): the text of the dtype-pair rule and the
 // least row and page stride, 656 in place of 576, are all that differ from it.
-enum { MLA_SPARSE_WIDE = 0, MLA_SPARSE_KV8 = 1, MLA_SPARSE_KV8_SCALED = 2 };
+// MLA_SPARSE_BWD: fa_bwd_mla_sparse (fa_mla_sparse_bwd_kernel.hip): MLA_SPARSE_WIDE's rules on q, o, the pool, the lists and the counts,
+// then that call's own (mla_sparse_bwd_tail) in place of the forward's workspace and grid.
+enum { MLA_SPARSE_WIDE = 0, MLA_SPARSE_KV8 = 1, MLA_SPARSE_KV8_SCALED = 2, MLA_SPARSE_BWD = 3 };
+struct MlaSparseBwdArgs {  // what the backward passes besides the forward's arguments
+  const void *d_o;
+  float *dq, *dkv;
+  long long dkv_page_stride, dkv_row_stride;
+};
+static int mla_sparse_bwd_tail(const char *fn, const MlaSparseBwdArgs &bw, const void *q, const void *kv_pages, const void *o, const float *lse,
+                               const int *indices, const int *index_counts, int T, int Hq, int Dqk, int topk, int page_size, int num_pages,
+                               float scale, long long q_token_stride, long long q_head_stride, long long o_token_stride, long long o_head_stride,
+                               long long kv_page_stride, long long kv_row_stride, long long indices_stride, int dtype, void *workspace,
+                               long long workspace_bytes, void *hip_stream) {
+  TRY(nonnull(fn, {bw.d_o, lse, bw.dq, bw.dkv}));
+  if (bw.dkv_row_stride < Dqk || bw.dkv_page_stride < Dqk || (bw.dkv_page_stride % 4) || (bw.dkv_row_stride % 4))
+    return fail(FA_ERR_INVALID_ARG, "%s: bad dkv strides (page %lld, row %lld): a row holds %d fp32 elements, strides are multiples of 4", fn,
+                bw.dkv_page_stride, bw.dkv_row_stride, Dqk);
+  if ((double)page_size * bw.dkv_row_stride * 4 >= 2147483648.0) return fail(FA_ERR_INVALID_ARG, "%s: one page of dkv exceeds 2 GiB", fn);
+  TRY(aligned16(fn, "d_o, dq and dkv", {bw.d_o, bw.dq, bw.dkv}));
+  if ((uintptr_t)lse & 3) return fail(FA_ERR_INVALID_ARG, "%s: lse must be fp32-aligned", fn);
+  TRY(workspace_fits(fn, workspace_bytes, fa::mla_sparse_bwd_workspace_bytes(T, Hq), "fa_bwd_mla_sparse_workspace_bytes"));
+  // (the forward's rule, on the forward's numbers: o and lse come from a call that passed it)
+  if ((long long)T * Hq > 0x7fffffffLL || (long long)T * 256 * ((Hq + 15) / 16) > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  fa::MlaSparseBwdParams p;
+  p.q = q; p.kv = kv_pages; p.o = o; p.d_o = bw.d_o; p.lse = lse;
+  p.dq = bw.dq; p.dkv = bw.dkv; p.delta = (float *)workspace;
+  p.indices = indices; p.counts = index_counts;
+  p.T = T; p.Hq = Hq; p.Nq = 1; p.scale = scale;
+  p.q_bs = q_token_stride; p.q_hs = q_head_stride; p.q_rs = Dqk;
+  p.o_bs = o_token_stride; p.o_hs = o_head_stride;
+  p.page_stride = kv_page_stride; p.row_stride = kv_row_stride;
+  p.dkv_page_stride = bw.dkv_page_stride; p.dkv_row_stride = bw.dkv_row_stride; p.idx_stride = indices_stride;
+  p.topk = topk; p.num_slots = num_pages * page_size;
+  p.lp = log2_of(page_size);
+  return launched(fn, fa::launch_bwd_mla_sparse(p, dtype, (hipStream_t)hip_stream));
+}
 constexpr int MLA_SCALED_ROW_BYTES = 656;  // 512 e4m3 latent bytes, four fp32 scales, 64 bf16 rotary elements
 static bool mla_sparse_kv8_shape_ok(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int page_size) {
   return mla_kv8_shape_ok(q_dtype, kv_dtype, Dqk, Dv, Hq, 1, page_size);
@@ -861,12 +896,12 @@ static int mla_decode_sparse_impl(const char *fn, int mode, const void *q, const
                                   const int *index_counts, int T, int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages, float scale,
                                   long long q_token_stride, long long q_head_stride, long long o_token_stride, long long o_head_stride,
                                   long long kv_page_stride, long long kv_row_stride, long long indices_stride, int dtype, int kv_dtype,
-                                  void *workspace, long long workspace_bytes, void *hip_stream) {
+                                  void *workspace, long long workspace_bytes, void *hip_stream, const MlaSparseBwdArgs *bw = nullptr) {
   g_err[0] = 0;
   TRY(nonnull(fn, {q, kv_pages, o, indices, workspace}));
   TRY(positive(fn, {T, Hq, Dqk, Dv, topk, page_size, num_pages}));
   TRY(scale_ok(fn, scale));
-  if (mode != MLA_SPARSE_WIDE) {
+  if (mode == MLA_SPARSE_KV8 || mode == MLA_SPARSE_KV8_SCALED) {
     if (!mla_sparse_kv8_shape_ok(dtype, kv_dtype, Dqk, Dv, Hq, page_size))
       return fail(FA_ERR_UNSUPPORTED, "%s: needs bf16 queries on an e4m3 pool%s, (Dqk, Dv) = (576, 512), Hq <= 128 heads and a page size of "
                   "16, 32, 64, 128 or 256; got q=%s kv=%s Dqk=%d Dv=%d Hq=%d page_size=%d", fn,
@@ -888,6 +923,10 @@ static int mla_decode_sparse_impl(const char *fn, int mode, const void *q, const
   if (mla_sparse_cap(topk) > (1 << 30)) return fail(FA_ERR_INVALID_ARG, "%s: capacity above 2^30 keys", fn);
   if ((long long)num_pages * page_size > (1 << 30))
     return fail(FA_ERR_INVALID_ARG, "%s: num_pages * page_size = %lld slots, above 2^30", fn, (long long)num_pages * page_size);
+  if (mode == MLA_SPARSE_BWD)
+    return mla_sparse_bwd_tail(fn, *bw, q, kv_pages, o, lse, indices, index_counts, T, Hq, Dqk, topk, page_size, num_pages, scale, q_token_stride,
+                               q_head_stride, o_token_stride, o_head_stride, kv_page_stride, kv_row_stride, indices_stride, dtype, workspace,
+                               workspace_bytes, hip_stream);
   const int cap = (int)mla_sparse_cap(topk);
   TRY(workspace_fits(fn, workspace_bytes, fa::mla_decode_sparse_workspace_bytes(T, Hq, cap),
                      mode == MLA_SPARSE_KV8_SCALED ? "fa_fwd_mla_decode_sparse_kv8_scaled_workspace_bytes"
@@ -923,6 +962,26 @@ int fa_fwd_mla_decode_sparse(const void *q, const void *kv_pages, void *o, float
   return mla_decode_sparse_impl("fa_fwd_mla_decode_sparse", MLA_SPARSE_WIDE, q, kv_pages, o, lse, indices, index_counts, T, Hq, Dqk, Dv, topk,
                                 page_size, num_pages, scale, q_token_stride, q_head_stride, o_token_stride, o_head_stride, kv_page_stride,
                                 kv_row_stride, indices_stride, dtype, dtype, workspace, workspace_bytes, hip_stream);
+}
+
+// fa_bwd_mla_sparse: the backward of the call above -- the fourth mode of its path, then the rules of its own
+int fa_bwd_mla_sparse_supported(int dtype, int Dqk, int Dv, int Hq, int page_size) {
+  return mla_decode_shape_ok(dtype, Dqk, Dv, Hq, 1, page_size, 128);
+}
+long long fa_bwd_mla_sparse_workspace_bytes(int T, int Hq) {
+  if (T < 1 || Hq < 1 || Hq > 128 || (long long)T * Hq > 0x7fffffffLL) return 0;
+  return fa::mla_sparse_bwd_workspace_bytes(T, Hq);
+}
+int fa_bwd_mla_sparse(const void *q, const void *kv_pages, const void *o, const void *d_o, const float *lse, float *dq, float *dkv,
+                      const int *indices, const int *index_counts, int T, int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages,
+                      float scale, long long q_token_stride, long long q_head_stride, long long o_token_stride, long long o_head_stride,
+                      long long kv_page_stride, long long kv_row_stride, long long dkv_page_stride, long long dkv_row_stride,
+                      long long indices_stride, int dtype, void *workspace, long long workspace_bytes, void *hip_stream) {
+  const MlaSparseBwdArgs bw = {d_o, dq, dkv, dkv_page_stride, dkv_row_stride};
+  return mla_decode_sparse_impl("fa_bwd_mla_sparse", MLA_SPARSE_BWD, q, kv_pages, const_cast<void *>(o), const_cast<float *>(lse), indices,
+                                index_counts, T, Hq, Dqk, Dv, topk, page_size, num_pages, scale, q_token_stride, q_head_stride, o_token_stride,
+                                o_head_stride, kv_page_stride, kv_row_stride, indices_stride, dtype, dtype, workspace, workspace_bytes, hip_stream,
+                                &bw);
 }
 
 // fa_fwd_mla_decode_sparse_kv8: the sparse call on an e4m3 pool under bf16 queries -- the second mode of the path above

@@ -236,6 +236,21 @@ struct MlaSparseParams {
   int lp;               // log2 of the page size (16 .. 256)
 };
 
+// one fa_bwd_mla_sparse call (csrc/fa_mla_sparse_bwd_kernel.hip): the forward's view of q, the pool and the lists (fa_mla_body.h reads
+// q, q_bs, q_hs, q_rs, Nq (= 1), Hq and scale under these names); o and d_o under o's strides, dq under q's, dkv under its own
+struct MlaSparseBwdParams {
+  const void *q, *kv, *o, *d_o;
+  const float *lse;  // [T, Hq]
+  float *dq, *dkv;
+  float *delta;  // the workspace: [T, Hq]
+  const int *indices, *counts;
+  int T, Hq, Nq;
+  float scale;
+  long long q_bs, q_hs, q_rs, o_bs, o_hs, page_stride, row_stride, dkv_page_stride, dkv_row_stride, idx_stride;  // elements
+  int topk, num_slots;
+  int lp;
+};
+
 // one fa_mla_indexer_logits_paged call (csrc/fa_mla_indexer_kernel.hip): q is the packed index query [total_q, Hi, 128] under (row, head)
 // element strides, w the fp32 head weights [total_q, Hi] under a row stride, k the index-key pool [num_pages, P, 128] of q's type; the
 // three tables are fa_fwd_varlen_paged's. An item is (sequence, block of tb tokens, chunk of chunk_tiles 64-key tiles).
@@ -400,6 +415,10 @@ hipError_t launch_mla_decode_sparse_kv8(const MlaSparseParams &p, const MlaDecod
 // latent bytes, four fp32 scales, 64 bf16 rotary elements; p's pool strides count bytes), bf16 queries, the tile dequantised into the
 // bf16 image while staging; the sparse call's split count, workspace and (bf16) combine kernel
 hipError_t launch_mla_decode_sparse_kv8_scaled(const MlaSparseParams &p, const MlaDecodeParams &pc, hipStream_t s);
+// fa_bwd_mla_sparse (csrc/fa_mla_sparse_bwd_kernel.hip): one launch over T x ceil(Hq / 32) workgroups of four waves; the workspace holds
+// delta [T, Hq]
+hipError_t launch_bwd_mla_sparse(const MlaSparseBwdParams &p, int dtype, hipStream_t s);
+long long mla_sparse_bwd_workspace_bytes(int T, int Hq);
 // fa_mla_indexer_* (csrc/fa_mla_indexer_kernel.hip): the token block (1, 2, 4) and the chunk rule from host scalars, the logits kernel
 // over B * nblk * nchunks items of four waves, the select kernel over B * max_seqlen_q workgroups
 int mla_indexer_token_block(int max_seqlen_q);

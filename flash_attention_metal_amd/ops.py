@@ -560,6 +560,79 @@ def flash_attention_mla_decode_sparse(
     return out, lse
 
 
+def mla_sparse_backward_supported(dtype: str, d_qk: int, d_v: int, Hq: int, page_size: int) -> bool:
+    return bool(load_library().fa_bwd_mla_sparse_supported(DTYPES[dtype], d_qk, d_v, Hq, page_size))
+
+
+def mla_sparse_backward_workspace_bytes(T: int, Hq: int) -> int:
+    return int(load_library().fa_bwd_mla_sparse_workspace_bytes(T, Hq))
+
+
+def flash_attention_mla_sparse_backward(
+    q: torch.Tensor,
+    kv_pages: torch.Tensor,
+    o: torch.Tensor,
+    d_o: torch.Tensor,
+    lse: torch.Tensor,
+    indices: torch.Tensor,
+    index_counts: Optional[torch.Tensor] = None,
+    *,
+    scale: Optional[float] = None,
+    dq: Optional[torch.Tensor] = None,
+    dkv: Optional[torch.Tensor] = None,
+    workspace: Optional[torch.Tensor] = None,
+    stream: Optional[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The backward of flash_attention_mla_decode_sparse on an f16 / bf16 pool (include/fa_mi355.h fa_bwd_mla_sparse): q [T,Hq,576], the
+    pool [num_pages,P,576] or [num_pages,P,1,576], o [T,Hq,512] and lse [T,Hq] fp32 contiguous as the forward returned them, d_o like o
+    (copied under o's strides if it has others), indices / index_counts as in the forward. `scale` is required. Returns (dq, dkv), both
+    fp32: dq [T,Hq,576] under q's strides, written (allocated here if None); dkv [num_pages,P,576], ACCUMULATED INTO when given -- one
+    buffer can take several chunks of tokens -- and zero-filled when allocated here. A slot named twice receives its gradient twice; rows
+    that no list names are not touched. dq is bitwise reproducible, dkv (fp32 atomic adds) is not. `workspace`: a uint8 device tensor of
+    at least mla_sparse_backward_workspace_bytes(T, Hq) bytes (allocated here if None). Nothing here synchronises."""
+    lib = load_library()
+    if scale is None:
+        raise ValueError("flash_attention_mla_sparse_backward needs the model's scale: there is no default (the head dim of the model is not 576)")
+    if q.dim() != 3 or o.dim() != 3 or kv_pages.dim() not in (3, 4) or (kv_pages.dim() == 4 and kv_pages.shape[2] != 1):
+        raise ValueError("q [T,Hq,576], o [T,Hq,512], kv_pages one [num_pages,P,576] or [num_pages,P,1,576] latent pool")
+    tensors = (q, kv_pages, o, d_o, lse, indices) + (() if index_counts is None else (index_counts,))
+    if not all(t.is_cuda and t.device == q.device for t in tensors):
+        raise ValueError("flash_attention_mla_sparse_backward needs every tensor on one device: there is no CPU path")
+    if q.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q.dtype for t in (kv_pages, o, d_o)):
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {kv_pages.dtype} {o.dtype} {d_o.dtype} (f16 or bf16; q, the pool, o and d_o alike)")
+    T, Hq, Dqk = q.shape
+    d_v = o.shape[2]
+    num_pages, P = kv_pages.shape[0], kv_pages.shape[1]
+    if kv_pages.shape[-1] != Dqk or kv_pages.stride(-1) != 1 or q.stride(2) != 1 or o.shape[:2] != (T, Hq) or o.stride(2) != 1 or d_o.shape != o.shape:
+        raise ValueError(f"incompatible q {tuple(q.shape)}, o {tuple(o.shape)}, d_o {tuple(d_o.shape)} and pool {tuple(kv_pages.shape)}")
+    if indices.dtype != torch.int32 or indices.dim() != 2 or indices.shape[0] != T or indices.shape[1] < 1 or indices.stride(1) != 1:
+        raise ValueError("indices must be an int32 [T, topk] tensor with a unit last stride")
+    if index_counts is not None and (index_counts.dtype != torch.int32 or index_counts.shape != (T,) or not index_counts.is_contiguous()):
+        raise ValueError("index_counts must be a contiguous int32 [T] tensor, or None")
+    if lse.dtype != torch.float32 or lse.shape != (T, Hq) or not lse.is_contiguous():
+        raise ValueError("lse must be contiguous fp32 [T,Hq]")
+    if d_o.stride() != o.stride():  # d_o is addressed under o's strides
+        d_o = torch.empty_strided(o.shape, o.stride(), dtype=o.dtype, device=o.device).copy_(d_o)
+    if dq is None:
+        dq = torch.empty_strided(q.shape, q.stride(), dtype=torch.float32, device=q.device)
+    elif not dq.is_cuda or dq.device != q.device or dq.dtype != torch.float32 or dq.shape != q.shape or dq.stride() != q.stride():
+        raise ValueError("dq must be an fp32 device tensor of q's shape and strides")
+    if dkv is None:
+        dkv = torch.zeros((num_pages, P, Dqk), dtype=torch.float32, device=q.device)
+    elif (not dkv.is_cuda or dkv.device != q.device or dkv.dtype != torch.float32 or dkv.dim() != 3 or dkv.shape != (num_pages, P, Dqk)
+          or dkv.stride(2) != 1):
+        raise ValueError("dkv must be an fp32 [num_pages,P,576] device tensor with a unit last stride")
+    topk = indices.shape[1]
+    istride = indices.stride(0) if T > 1 else (topk + 3) // 4 * 4
+    ws = _workspace(workspace, mla_sparse_backward_workspace_bytes(T, Hq), q.device)
+    _call(lib, "fa_bwd_mla_sparse",
+          (q.data_ptr(), kv_pages.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dq.data_ptr(), dkv.data_ptr(), indices.data_ptr(),
+           _ptr(index_counts), T, Hq, Dqk, d_v, topk, P, num_pages, float(scale), q.stride(0), q.stride(1), o.stride(0), o.stride(1),
+           kv_pages.stride(0), kv_pages.stride(1), dkv.stride(0), dkv.stride(1), istride, _TORCH2FA[q.dtype], ws.data_ptr(), ws.numel()),
+          q.device, stream)
+    return dq, dkv
+
+
 def mla_indexer_supported(dtype: str, Hi: int, Di: int, page_size: int) -> bool:
     return bool(load_library().fa_mla_indexer_supported(DTYPES[dtype], Hi, Di, page_size))
 

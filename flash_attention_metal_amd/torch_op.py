@@ -35,6 +35,13 @@ attention_varlen(..., sinks=) dispatches to it.
 
 The MLA prefill (fa_fwd_varlen_mla / fa_bwd_varlen_mla): q [total_q, Hq, 192], k [total_k, Hkv, 192], v [total_k, Hkv, 128], o
 [total_q, Hq, 128], each under its own strides; scale = 0.0 means 192 ** -0.5. Differentiable in q, k, v like attention_varlen.
+
+    torch.ops.fa_mi355.attention_mla_sparse(q, kv_pages, indices, index_counts, scale) -> (o, lse)
+
+The absorbed MLA step over a list of keys per token (fa_fwd_mla_decode_sparse / fa_bwd_mla_sparse): q [T, Hq, 576], kv_pages
+[num_pages, P, 576] f16 / bf16 like q, indices int32 [T, topk] of slots, index_counts int32 [T] or None; o [T, Hq, 512], lse [T, Hq].
+`scale` is the model's and must be greater than 0. Differentiable in q and kv_pages: the pool's gradient is pool-shaped, in the pool's
+dtype, zero in rows that no list names. The integer inputs get no gradient.
 """
 from __future__ import annotations
 
@@ -42,8 +49,9 @@ from typing import Tuple
 
 import torch
 
-from .ops import (_TORCH2FA, FaError, _out_dtype, _sink_window, _window, flash_attention_backward, flash_attention_forward, flash_attention_varlen,
-                  flash_attention_varlen_backward, flash_attention_varlen_mla, flash_attention_varlen_mla_backward, load_library)
+from .ops import (_TORCH2FA, FaError, _out_dtype, _sink_window, _window, flash_attention_backward, flash_attention_forward,
+                  flash_attention_mla_decode_sparse, flash_attention_mla_sparse_backward, flash_attention_varlen, flash_attention_varlen_backward,
+                  flash_attention_varlen_mla, flash_attention_varlen_mla_backward, load_library)
 
 _LIB = torch.library.Library("fa_mi355", "DEF")
 _LIB.define("attention_forward(Tensor q, Tensor k, Tensor v, bool is_causal=False, float scale=0.0) -> (Tensor, Tensor)")
@@ -365,6 +373,61 @@ torch.library.register_autograd("fa_mi355::attention_varlen_mla", _varlen_mla_ba
 def attention_varlen_mla(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_seqlen_k: int, is_causal: bool = False, scale: float = 0.0):
     """fa_mi355::attention_varlen_mla: the MLA prefill (head dims 192 / 128), differentiable in q, k, v through fa_bwd_varlen_mla."""
     return torch.ops.fa_mi355.attention_varlen_mla(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, scale)
+
+
+_LIB.define("attention_mla_sparse(Tensor q, Tensor kv_pages, Tensor indices, Tensor? index_counts, float scale=0.0) -> (Tensor, Tensor)")
+
+
+def _mla_sparse_scale(scale):
+    if not scale > 0:
+        raise ValueError("fa_mi355::attention_mla_sparse needs the model's scale: there is no default (the head dim of the model is not 576)")
+    return float(scale)
+
+
+def _mla_sparse_impl(q, kv_pages, indices, index_counts, scale=0.0):
+    return flash_attention_mla_decode_sparse(q, kv_pages, indices, _mla_sparse_scale(scale), index_counts=index_counts)
+
+
+def _mla_sparse_meta(q, kv_pages, indices, index_counts, scale=0.0):
+    return q.new_empty((q.shape[0], q.shape[1], 512)), q.new_empty((q.shape[0], q.shape[1]), dtype=torch.float32)
+
+
+_LIB.impl("attention_mla_sparse", _mla_sparse_impl, "CUDA")
+_LIB.impl("attention_mla_sparse", _mla_sparse_meta, "Meta")
+
+
+def _mla_sparse_setup_context(ctx, inputs, output):
+    q, kv_pages, indices, index_counts, scale = inputs
+    o, lse = output
+    ctx.save_for_backward(q, kv_pages, indices, index_counts, o, lse)
+    ctx.scale = float(scale)
+    ctx.set_materialize_grads(False)
+
+
+def _mla_sparse_backward(ctx, grad_o, grad_lse):
+    q, kv_pages, indices, index_counts, o, lse = ctx.saved_tensors
+    if grad_lse is not None:
+        raise NotImplementedError("fa_mi355::attention_mla_sparse: no gradient through the LSE output")
+    none = (None,) * 5
+    if grad_o is None:
+        return none
+    pool = kv_pages[:, :, 0] if kv_pages.dim() == 4 else kv_pages
+    if q.dtype not in _TORCH2FA or not load_library().fa_bwd_mla_sparse_supported(_TORCH2FA[q.dtype], q.shape[2], o.shape[2], q.shape[1],
+                                                                                  pool.shape[1]):
+        raise FaError(-2, f"no sparse MLA backward kernel for q {tuple(q.shape)} {q.dtype} on a pool {tuple(kv_pages.shape)} {kv_pages.dtype} "
+                      "(f16 / bf16, head dims 576 / 512, up to 128 heads)", "fa_bwd_mla_sparse")
+    # (dkv zero-initialised by the wrapper: rows that no list names get a zero gradient)
+    dq, dkv = flash_attention_mla_sparse_backward(q, pool, o, grad_o.to(o.dtype), lse, indices, index_counts, scale=_mla_sparse_scale(ctx.scale))
+    return (dq.to(q.dtype), dkv.to(kv_pages.dtype).reshape(kv_pages.shape)) + none[2:]
+
+
+torch.library.register_autograd("fa_mi355::attention_mla_sparse", _mla_sparse_backward, setup_context=_mla_sparse_setup_context, lib=_LIB)
+
+
+def attention_mla_sparse(q, kv_pages, indices, index_counts=None, scale: float = 0.0):
+    """fa_mi355::attention_mla_sparse: the absorbed MLA step over a list of keys per token, differentiable in q and kv_pages through
+    fa_bwd_mla_sparse. `scale` is the model's (required: greater than 0)."""
+    return torch.ops.fa_mi355.attention_mla_sparse(q, kv_pages, indices, index_counts, scale)
 
 
 def attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_seqlen_k: int, is_causal: bool = False, scale: float = 0.0,

@@ -933,7 +933,7 @@ int fa_fwd_mla_decode_paged_kv8_supported(int q_dtype, int kv_dtype, int Dqk, in
  * From LDS onwards the source text is the wide call's.
  * Not here: e4m3 pools (fa_fwd_mla_decode_sparse_kv8) and the 656-byte rows with a scale per 128 latent elements
  * (fa_fwd_mla_decode_sparse_kv8_scaled); a mask inside the list; more than 128 heads; sinks; the indexer
- * itself; a sparse backward. No dense call is rerouted.
+ * itself. The backward is fa_bwd_mla_sparse. No dense call is rerouted.
  */
 int fa_fwd_mla_decode_sparse(const void *q, const void *kv_pages, void *o, float *lse,
                              const int *indices, const int *index_counts,
@@ -1067,6 +1067,59 @@ int fa_mla_kv_append_paged_scaled(const void *kv_new, void *kv_pages, const int 
                                   const int *seqlens_k, int B, int total_new, int max_seqlen_new, int page_size, int num_pages,
                                   int max_pages_per_seq, long long new_row_stride, long long kv_page_stride, long long kv_row_stride,
                                   long long block_table_stride, int new_dtype, void *hip_stream);
+
+/*
+ * Multi-head latent attention (sparse, backward): fa_bwd_mla_sparse is the backward of fa_fwd_mla_decode_sparse (f16 / bf16 pool, rows of
+ * 576 elements), for continued training and RL post-training of models that run their sparse stage in the absorbed (MQA, 576 / 512)
+ * form. The listed rows are read in place and their gradients are added in place: no gather, nothing of size [T, topk, 576].
+ * For token t and head h, with n_t = clamp(index_counts[t], 0, topk) (topk under NULL) and x_j = indices[t][j], j < n_t:
+ *   s_j   = q[t,h,0:576] . row(x_j)[0:576]          P_j  = exp(scale * s_j - lse[t,h])
+ *   delta = sum_d dO[t,h,d] * O[t,h,d]              dP_j = dO[t,h,0:512] . row(x_j)[0:512]          dS_j = P_j * (dP_j - delta)
+ *   dQ[t,h,0:576]     = scale * sum_j dS_j * row(x_j)[0:576]
+ *   dKV[x_j, 0:576]  += scale * sum_h dS_j * q[t,h,0:576]       (the key side of the row)
+ *   dKV[x_j, 0:512]  += sum_h P_j * dO[t,h,0:512]               (the value side of the same row)
+ * q, o, kv_pages, indices, index_counts and their strides follow fa_fwd_mla_decode_sparse exactly; lse is [T, Hq] fp32 contiguous, in
+ * natural log, as that call wrote it, and is required here. Validation runs on that call's path: every rule the two calls share carries
+ * the same status and the same text after the function name. The rules of the list carry over in the forward's words: the list is a
+ * list, not a set -- a slot named twice receives its gradient twice; an entry among the first n_t outside [0, num_pages * P) is the
+ * forward's key of zeros: its P_j exists (it took part in the softmax and so in O), it adds nothing to dQ, its dKV is dropped and no
+ * address is formed from it; nothing at j >= n_t or j >= topk is ever read; n_t = 0 is recognised by the integer, never by its LSE, and
+ * gives dq = 0 exactly and nothing added to dkv; pool rows that no list names are never read and their dkv rows are never touched. The
+ * kernel reads both tables, the host never does, and the grid depends on host scalars alone: graph-capturable, asynchronous, allocates
+ * nothing.
+ * d_o is dO in q's type, [T, Hq, 512] addressed under o's strides. dq is fp32 [T, Hq, 576] addressed under q's ELEMENT strides (the
+ * backward family's convention); it is WRITTEN, not accumulated. dkv is fp32 [num_pages, P, 576] under dkv_page_stride / dkv_row_stride
+ * (elements: multiples of 4, at least 576, base 16-byte aligned, one page below 2 GiB); it is ACCUMULATED INTO: the caller zeroes it, and
+ * one buffer can take several chunks of tokens of the same layer. The footprint is columns 0 .. 575 of named in-pool rows only.
+ * Supported: f16 / bf16 (q, o, d_o and the pool of one type), (Dqk, Dv) = (576, 512), 1 <= Hq <= 128, P in {16, 32, 64, 128, 256};
+ * anything else FA_ERR_UNSUPPORTED with a message that names what was given. Rules of this call's own, each FA_ERR_INVALID_ARG before any
+ * launch: null d_o, lse, dq or dkv; a dkv stride below 576 or not a multiple of 4, a dkv page of 2 GiB or more; misaligned d_o, dq, dkv
+ * (16 bytes) or lse (4); a workspace below fa_bwd_mla_sparse_workspace_bytes(T, Hq) = 4 * T * Hq bytes rounded up to 16 (it holds delta
+ * [T, Hq] fp32, which the call leaves there; nothing depends on the workspace's prior contents).
+ * Rounding (the existing backward's, tests/backward_bound.py): O as given in the type, LSE in fp32 times log2 e, Q~ = round(scale * log2 e
+ * * Q) for the scores, P and dS rounded to the type before the second products, fp32 accumulation everywhere else.
+ * REPRODUCIBILITY: dq is bitwise reproducible. dkv is NOT: it leaves the workgroups by fp32 atomic adds to global memory -- one per
+ * (token, block of 32 heads, listed row, column), the sum over the block's heads complete before it -- and the order in which fp32
+ * additions meet in memory varies from run to run.
+ * How it runs (csrc/fa_mla_sparse_bwd_kernel.hip): one launch, a four-wave workgroup per (token, 32 heads), key
+ * tiles of 64 listed rows staged by the forward's scheme; Q and dO in registers as MFMA operands by head rows and by columns; all five
+ * products on the matrix cores.
+ * Not here: e4m3 pools and the 656-byte rows (the gradient of a quantised cache); a gradient into the indexer; a deterministic dkv; a
+ * key split for very few tokens; more than 128 heads.
+ */
+int fa_bwd_mla_sparse(const void *q, const void *kv_pages, const void *o, const void *d_o, const float *lse,
+                      float *dq, float *dkv,
+                      const int *indices, const int *index_counts,
+                      int T, int Hq, int Dqk, int Dv, int topk,
+                      int page_size, int num_pages, float scale,
+                      long long q_token_stride, long long q_head_stride,
+                      long long o_token_stride, long long o_head_stride,
+                      long long kv_page_stride, long long kv_row_stride,
+                      long long dkv_page_stride, long long dkv_row_stride, long long indices_stride,
+                      int dtype, void *workspace, long long workspace_bytes, void *hip_stream);
+/* 4 * T * Hq rounded up to 16 on every legal input (T >= 1, 1 <= Hq <= 128, T * Hq below 2^31); 0 elsewhere */
+long long fa_bwd_mla_sparse_workspace_bytes(int T, int Hq);
+int fa_bwd_mla_sparse_supported(int dtype, int Dqk, int Dv, int Hq, int page_size);
 
 /*
  * The MLA indexer: fa_mla_indexer_logits_paged, fa_mla_indexer_select and fa_mla_indexer_topk_paged PRODUCE the lists that
@@ -1279,7 +1332,7 @@ int fa_mla_indexer_quant_supported(int dtype, int Di);   /* f16 | bf16, 128 */
  * Every rule of fa_mla_indexer_select keeps its status and its text after the function name. Of this call's own, each
  * FA_ERR_INVALID_ARG before any launch: num_splits outside 1 .. 64, a workspace that is not 16-byte aligned, NULL with S >= 2 or too
  * small, a grid that does not fit an int.
- * How it runs (csrc/fa_mla_indexer_select_split_kernel.hip, DESIGN.md section 4.7w): the capacity is cut into S segments of
+ * How it runs (csrc/fa_mla_indexer_select_split_kernel.hip, DESIGN.md section 4.7y): the capacity is cut into S segments of
  * roundup64(ceil(capacity / S)) keys, one workgroup of 256 threads each, and the radix select is a chain of five plain launches on the
  * stream: four that build one 256-bin histogram per segment and digit, each first re-deriving the digit before from all segments'
  * histograms, and one that resolves the last digit and emits its segment's keys at (greater in front) + min(equals in front, need).
