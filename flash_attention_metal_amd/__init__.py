@@ -49,6 +49,8 @@ from .ops import (  # noqa: F401
     mla_indexer_k_append_quant,
     mla_indexer_kv8_supported,
     mla_indexer_logits,
+    mla_indexer_loss_sparse,
+    mla_indexer_loss_sparse_supported,
     mla_indexer_q_quant,
     mla_indexer_quant_supported,
     mla_indexer_select,
@@ -59,6 +61,8 @@ from .ops import (  # noqa: F401
     mla_kv_append_paged_scaled,
     mla_sparse_backward_supported,
     mla_sparse_backward_workspace_bytes,
+    mla_sparse_head_probs,
+    mla_sparse_head_probs_supported,
     supported,
     varlen_backward_supported,
     varlen_backward_workspace_bytes,

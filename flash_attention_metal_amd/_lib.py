@@ -47,6 +47,10 @@ SYMBOLS = {
     "fa_bwd_mla_sparse": (c_int, [c_void_p] * 9 + [c_int] * 7 + [c_float] + [c_longlong] * 9 + [c_int, c_void_p, c_longlong, c_void_p]),
     "fa_bwd_mla_sparse_workspace_bytes": (c_longlong, [c_int] * 2),
     "fa_bwd_mla_sparse_supported": (c_int, [c_int] * 5),
+    "fa_mla_sparse_head_probs": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_float] + [c_longlong] * 6 + [c_int, c_void_p]),
+    "fa_mla_sparse_head_probs_supported": (c_int, [c_int] * 5),
+    "fa_mla_indexer_loss_sparse": (c_int, [c_void_p] * 11 + [c_int] * 6 + [c_longlong] * 9 + [c_int, c_void_p]),
+    "fa_mla_indexer_loss_sparse_supported": (c_int, [c_int] * 5),
     "fa_mla_indexer_logits_paged": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_longlong] * 7 + [c_int, c_void_p]),
     "fa_mla_indexer_select": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_longlong] * 3 + [c_void_p]),
     "fa_mla_indexer_topk_paged": (c_int, [c_void_p] * 8 + [c_int] * 9 + [c_longlong] * 7 + [c_int, c_void_p, c_longlong, c_void_p]),

@@ -854,7 +854,9 @@ long long fa_fwd_mla_decode_sparse_workspace_bytes(int T, int Hq, int Dv, int to
 // least row and page stride, 656 in place of 576, are all that differ from it.
 // MLA_SPARSE_BWD: fa_bwd_mla_sparse (fa_mla_sparse_bwd_kernel.hip): MLA_SPARSE_WIDE's rules on q, o, the pool, the lists and the counts,
 // then that call's own (mla_sparse_bwd_tail) in place of the forward's workspace and grid.
-enum { MLA_SPARSE_WIDE = 0, MLA_SPARSE_KV8 = 1, MLA_SPARSE_KV8_SCALED = 2, MLA_SPARSE_BWD = 3 };
+// MLA_SPARSE_PROBS: fa_mla_sparse_head_probs (fa_mla_sparse_probs_kernel.hip): MLA_SPARSE_WIDE's rules on q, the pool, the lists and the
+// counts -- the call has no o and no workspace, so their rules are not asked --, then that call's own (mla_sparse_probs_tail).
+enum { MLA_SPARSE_WIDE = 0, MLA_SPARSE_KV8 = 1, MLA_SPARSE_KV8_SCALED = 2, MLA_SPARSE_BWD = 3, MLA_SPARSE_PROBS = 4 };
 struct MlaSparseBwdArgs {  // what the backward passes besides the forward's arguments
   const void *d_o;
   float *dq, *dkv;
@@ -888,6 +890,32 @@ static int mla_sparse_bwd_tail(const char *fn, const MlaSparseBwdArgs &bw, const
   p.lp = log2_of(page_size);
   return launched(fn, fa::launch_bwd_mla_sparse(p, dtype, (hipStream_t)hip_stream));
 }
+struct MlaSparseProbsArgs {  // what fa_mla_sparse_head_probs passes besides the forward's arguments
+  float *probs;
+  long long probs_stride;
+};
+static int mla_sparse_probs_tail(const char *fn, const MlaSparseProbsArgs &pa, const void *q, const void *kv_pages, const float *lse,
+                                 const int *indices, const int *index_counts, int T, int Hq, int topk, int page_size, int num_pages, float scale,
+                                 long long q_token_stride, long long q_head_stride, long long kv_page_stride, long long kv_row_stride,
+                                 long long indices_stride, int dtype, void *hip_stream) {
+  TRY(nonnull(fn, {lse, pa.probs}));
+  if (pa.probs_stride < topk) return fail(FA_ERR_INVALID_ARG, "%s: probs_stride=%lld < topk=%d", fn, pa.probs_stride, topk);
+  if ((uintptr_t)lse & 3) return fail(FA_ERR_INVALID_ARG, "%s: lse must be fp32-aligned", fn);
+  if ((uintptr_t)pa.probs & 3) return fail(FA_ERR_INVALID_ARG, "%s: probs must be fp32-aligned", fn);
+  // (the forward's rule, on the forward's numbers: lse comes from a call that passed it)
+  if ((long long)T * Hq > 0x7fffffffLL || (long long)T * 256 * ((Hq + 15) / 16) > 0x7fffffffLL) return fail(FA_ERR_INVALID_ARG, "%s: grid too large", fn);
+  fa::MlaSparseProbsParams p;
+  p.q = q; p.kv = kv_pages; p.lse = lse; p.probs = pa.probs;
+  p.indices = indices; p.counts = index_counts;
+  p.T = T; p.Hq = Hq; p.scale = scale;
+  p.q_bs = q_token_stride; p.q_hs = q_head_stride;
+  p.page_stride = kv_page_stride; p.row_stride = kv_row_stride; p.idx_stride = indices_stride; p.probs_stride = pa.probs_stride;
+  p.topk = topk; p.num_slots = num_pages * page_size;
+  p.lp = log2_of(page_size);
+  p.chunk_tiles = fa::mla_sparse_probs_chunk_tiles(T, topk);
+  p.nchunks = (int)(((mla_sparse_cap(topk) / 64) + p.chunk_tiles - 1) / p.chunk_tiles);  // at most 512
+  return launched(fn, fa::launch_mla_sparse_head_probs(p, dtype, (hipStream_t)hip_stream));
+}
 constexpr int MLA_SCALED_ROW_BYTES = 656;  // 512 e4m3 latent bytes, four fp32 scales, 64 bf16 rotary elements
 static bool mla_sparse_kv8_shape_ok(int q_dtype, int kv_dtype, int Dqk, int Dv, int Hq, int page_size) {
   return mla_kv8_shape_ok(q_dtype, kv_dtype, Dqk, Dv, Hq, 1, page_size);
@@ -896,9 +924,12 @@ static int mla_decode_sparse_impl(const char *fn, int mode, const void *q, const
                                   const int *index_counts, int T, int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages, float scale,
                                   long long q_token_stride, long long q_head_stride, long long o_token_stride, long long o_head_stride,
                                   long long kv_page_stride, long long kv_row_stride, long long indices_stride, int dtype, int kv_dtype,
-                                  void *workspace, long long workspace_bytes, void *hip_stream, const MlaSparseBwdArgs *bw = nullptr) {
+                                  void *workspace, long long workspace_bytes, void *hip_stream, const MlaSparseBwdArgs *bw = nullptr,
+                                  const MlaSparseProbsArgs *pa = nullptr) {
   g_err[0] = 0;
-  TRY(nonnull(fn, {q, kv_pages, o, indices, workspace}));
+  const bool probs = mode == MLA_SPARSE_PROBS;
+  if (probs) TRY(nonnull(fn, {q, kv_pages, indices}));
+  else TRY(nonnull(fn, {q, kv_pages, o, indices, workspace}));
   TRY(positive(fn, {T, Hq, Dqk, Dv, topk, page_size, num_pages}));
   TRY(scale_ok(fn, scale));
   if (mode == MLA_SPARSE_KV8 || mode == MLA_SPARSE_KV8_SCALED) {
@@ -912,12 +943,13 @@ static int mla_decode_sparse_impl(const char *fn, int mode, const void *q, const
   if (indices_stride < topk || (indices_stride % 4))
     return fail(FA_ERR_INVALID_ARG, "%s: indices_stride=%lld must be a multiple of 4 and >= topk=%d", fn, indices_stride, topk);
   TRY(mla_strides_ok(fn, "", T, Dqk, q_token_stride, q_head_stride, Dqk));
-  TRY(mla_strides_ok(fn, "output ", T, Dv, o_token_stride, o_head_stride, Dv));
+  if (!probs) TRY(mla_strides_ok(fn, "output ", T, Dv, o_token_stride, o_head_stride, Dv));
   // (an e4m3 pool: strides in elements = bytes, multiples of 16, a page counted in bytes of 1 -- fa_fwd_mla_decode_paged_kv8's rule; the
   // scaled rows: the same rule with a row of 656 bytes)
   TRY(page_strides_ok(fn, mode == MLA_SPARSE_KV8_SCALED ? MLA_SCALED_ROW_BYTES : Dqk, page_size, kv_page_stride, kv_row_stride, kv_row_stride, 0,
                       kv_dtype));
-  TRY(aligned16(fn, "tensors and workspace", {q, kv_pages, o, workspace}));
+  if (probs) TRY(aligned16(fn, "tensors and workspace", {q, kv_pages}));
+  else TRY(aligned16(fn, "tensors and workspace", {q, kv_pages, o, workspace}));
   TRY(aligned16(fn, "indices", {indices}));
   if ((uintptr_t)index_counts & 3) return fail(FA_ERR_INVALID_ARG, "%s: index_counts must be int32-aligned", fn);
   if (mla_sparse_cap(topk) > (1 << 30)) return fail(FA_ERR_INVALID_ARG, "%s: capacity above 2^30 keys", fn);
@@ -927,6 +959,9 @@ static int mla_decode_sparse_impl(const char *fn, int mode, const void *q, const
     return mla_sparse_bwd_tail(fn, *bw, q, kv_pages, o, lse, indices, index_counts, T, Hq, Dqk, topk, page_size, num_pages, scale, q_token_stride,
                                q_head_stride, o_token_stride, o_head_stride, kv_page_stride, kv_row_stride, indices_stride, dtype, workspace,
                                workspace_bytes, hip_stream);
+  if (probs)
+    return mla_sparse_probs_tail(fn, *pa, q, kv_pages, lse, indices, index_counts, T, Hq, topk, page_size, num_pages, scale, q_token_stride,
+                                 q_head_stride, kv_page_stride, kv_row_stride, indices_stride, dtype, hip_stream);
   const int cap = (int)mla_sparse_cap(topk);
   TRY(workspace_fits(fn, workspace_bytes, fa::mla_decode_sparse_workspace_bytes(T, Hq, cap),
                      mode == MLA_SPARSE_KV8_SCALED ? "fa_fwd_mla_decode_sparse_kv8_scaled_workspace_bytes"
@@ -982,6 +1017,20 @@ int fa_bwd_mla_sparse(const void *q, const void *kv_pages, const void *o, const 
                                 index_counts, T, Hq, Dqk, Dv, topk, page_size, num_pages, scale, q_token_stride, q_head_stride, o_token_stride,
                                 o_head_stride, kv_page_stride, kv_row_stride, indices_stride, dtype, dtype, workspace, workspace_bytes, hip_stream,
                                 &bw);
+}
+
+// fa_mla_sparse_head_probs: the forward's probabilities on the listed keys, summed over heads -- the fifth mode of its path
+int fa_mla_sparse_head_probs_supported(int dtype, int Dqk, int Dv, int Hq, int page_size) {
+  return mla_decode_shape_ok(dtype, Dqk, Dv, Hq, 1, page_size, 128);
+}
+int fa_mla_sparse_head_probs(const void *q, const void *kv_pages, const float *lse, float *probs, const int *indices, const int *index_counts,
+                             int T, int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages, float scale, long long q_token_stride,
+                             long long q_head_stride, long long kv_page_stride, long long kv_row_stride, long long indices_stride,
+                             long long probs_stride, int dtype, void *hip_stream) {
+  const MlaSparseProbsArgs pa = {probs, probs_stride};
+  return mla_decode_sparse_impl("fa_mla_sparse_head_probs", MLA_SPARSE_PROBS, q, kv_pages, nullptr, const_cast<float *>(lse), indices, index_counts,
+                                T, Hq, Dqk, Dv, topk, page_size, num_pages, scale, q_token_stride, q_head_stride, 0, 0, kv_page_stride,
+                                kv_row_stride, indices_stride, dtype, dtype, nullptr, 0, hip_stream, nullptr, &pa);
 }
 
 // fa_fwd_mla_decode_sparse_kv8: the sparse call on an e4m3 pool under bf16 queries -- the second mode of the path above
@@ -1285,6 +1334,65 @@ int fa_mla_indexer_topk_paged_kv8(const void *q_idx, const float *w, const void 
   TRY(launched(fn, fa::launch_mla_indexer_logits_kv8(pl, Hi, (hipStream_t)hip_stream)));
   return launched(fn, fa::launch_mla_indexer_select(ps, (hipStream_t)hip_stream));
 }
+// ---- fa_mla_indexer_loss_sparse (csrc/fa_mla_indexer_loss_kernel.hip): the indexer's KL loss over the sparse forward's lists and its
+// gradients. q_idx, w and the pool carry fa_mla_indexer_logits_paged's rules, the lists fa_fwd_mla_decode_sparse's (statuses and texts);
+// the rules of its own (topk's limit, target, loss, the gradient trio, dk's strides) follow them.
+int fa_mla_indexer_loss_sparse_supported(int dtype, int Hi, int Di, int page_size, int topk) {
+  return fa_mla_indexer_supported(dtype, Hi, Di, page_size) && topk >= 1 && topk <= fa::mla_indexer_loss_max_topk();
+}
+int fa_mla_indexer_loss_sparse(const void *q_idx, const float *w, const void *k_idx_pages, const int *indices, const int *index_counts,
+                               const float *target, const float *loss_grad, float *loss, float *dq_idx, float *dw, float *dk_idx, int T, int Hi,
+                               int Di, int topk, int page_size, int num_pages, long long q_row_stride, long long q_head_stride,
+                               long long w_row_stride, long long k_page_stride, long long k_row_stride, long long dk_page_stride,
+                               long long dk_row_stride, long long indices_stride, long long target_stride, int dtype, void *hip_stream) {
+  const char *fn = "fa_mla_indexer_loss_sparse";
+  g_err[0] = 0;
+  TRY(nonnull(fn, {q_idx, w, k_idx_pages, indices, target, loss}));
+  TRY(positive(fn, {T, Hi, Di, topk, page_size, num_pages}));
+  if (!fa_mla_indexer_supported(dtype, Hi, Di, page_size))
+    return fail(FA_ERR_UNSUPPORTED, "%s: needs f16 / bf16 (q_idx and the pool alike), Hi = 32 | 64, Di = 128 and a page size of 16, 32, 64, "
+                "128 or 256; got dtype=%s Hi=%d Di=%d page_size=%d", fn, fa_dtype_name(dtype), Hi, Di, page_size);
+  if (topk > fa::mla_indexer_loss_max_topk())
+    return fail(FA_ERR_UNSUPPORTED, "%s: topk=%d above the %d list entries the kernel's LDS row holds", fn, topk, fa::mla_indexer_loss_max_topk());
+  TRY(varlen_strides_ok(fn, "", Di, q_row_stride, q_head_stride, stride_mult(dtype)));
+  TRY(page_strides_ok(fn, Di, page_size, k_page_stride, k_row_stride, k_row_stride, 0, dtype));
+  TRY(aligned16(fn, "tensors", {q_idx, k_idx_pages}));
+  if ((uintptr_t)w & 3) return fail(FA_ERR_INVALID_ARG, "%s: w must be fp32-aligned", fn);
+  if (w_row_stride < Hi) return fail(FA_ERR_INVALID_ARG, "%s: w_row_stride=%lld < Hi=%d", fn, w_row_stride, Hi);
+  if (indices_stride < topk || (indices_stride % 4))
+    return fail(FA_ERR_INVALID_ARG, "%s: indices_stride=%lld must be a multiple of 4 and >= topk=%d", fn, indices_stride, topk);
+  TRY(aligned16(fn, "indices", {indices}));
+  if ((uintptr_t)index_counts & 3) return fail(FA_ERR_INVALID_ARG, "%s: index_counts must be int32-aligned", fn);
+  if ((long long)num_pages * page_size > (1 << 30))
+    return fail(FA_ERR_INVALID_ARG, "%s: num_pages * page_size = %lld slots, above 2^30", fn, (long long)num_pages * page_size);
+  if (target_stride < topk) return fail(FA_ERR_INVALID_ARG, "%s: target_stride=%lld < topk=%d", fn, target_stride, topk);
+  if (((uintptr_t)target | (uintptr_t)loss_grad | (uintptr_t)loss) & 3)
+    return fail(FA_ERR_INVALID_ARG, "%s: target, loss_grad and loss must be fp32-aligned", fn);
+  const int ngrads = (dq_idx != nullptr) + (dw != nullptr) + (dk_idx != nullptr);
+  if (ngrads != 0 && ngrads != 3)
+    return fail(FA_ERR_INVALID_ARG, "%s: dq_idx, dw and dk_idx are given all three (gradients) or none (a loss-only call)", fn);
+  if (ngrads) {
+    if (dk_row_stride < Di || dk_page_stride < Di || (dk_page_stride % 4) || (dk_row_stride % 4))
+      return fail(FA_ERR_INVALID_ARG, "%s: bad dk strides (page %lld, row %lld): a row holds %d fp32 elements, strides are multiples of 4", fn,
+                  dk_page_stride, dk_row_stride, Di);
+    if ((double)page_size * dk_row_stride * 4 >= 2147483648.0) return fail(FA_ERR_INVALID_ARG, "%s: one page of dk exceeds 2 GiB", fn);
+    TRY(aligned16(fn, "dq_idx and dk_idx", {dq_idx, dk_idx}));
+    if ((uintptr_t)dw & 3) return fail(FA_ERR_INVALID_ARG, "%s: dw must be fp32-aligned", fn);
+  }
+  fa::MlaIndexerLossParams p;
+  p.q = q_idx; p.k = k_idx_pages; p.w = w;
+  p.indices = indices; p.counts = index_counts;
+  p.target = target; p.loss_grad = loss_grad;
+  p.loss = loss; p.dq = dq_idx; p.dw = dw; p.dk = dk_idx;
+  p.T = T; p.topk = topk; p.num_slots = num_pages * page_size;
+  p.lp = log2_of(page_size);
+  p.q_rs = q_row_stride; p.q_hs = q_head_stride; p.w_rs = w_row_stride;
+  p.page_stride = k_page_stride; p.row_stride = k_row_stride;
+  p.dk_page_stride = dk_page_stride; p.dk_row_stride = dk_row_stride;
+  p.idx_stride = indices_stride; p.target_stride = target_stride;
+  return launched(fn, fa::launch_mla_indexer_loss(p, Hi, dtype, (hipStream_t)hip_stream));
+}
+
 // ---- the e4m3 indexer's input stage (csrc/fa_mla_indexer_quant_kernel.hip): what the two *_kv8 calls above read, written by the library.
 // fa_mla_indexer_k_append_paged_quant: fa_mla_kv_append_paged_scaled's rules in its order, the pool under the kv8 logits call's (byte)
 // stride rule, then the scales' rules (mla_indexer_scales_ok). fa_mla_indexer_q_quant: the 16-bit indexer call's stride rule for q_idx.

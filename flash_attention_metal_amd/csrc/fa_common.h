@@ -251,6 +251,33 @@ struct MlaSparseBwdParams {
   int lp;
 };
 
+// one fa_mla_sparse_head_probs call (csrc/fa_mla_sparse_probs_kernel.hip): the sparse forward's view of q, the pool and the lists, its lse
+// [T, Hq], and probs [T, probs_stride] fp32. An item is (token, chunk of chunk_tiles 64-key tiles)
+struct MlaSparseProbsParams {
+  const void *q, *kv;
+  const float *lse;
+  float *probs;
+  const int *indices, *counts;
+  int T, Hq;
+  float scale;
+  long long q_bs, q_hs, page_stride, row_stride, idx_stride, probs_stride;  // elements
+  int topk, num_slots;
+  int lp;
+  int chunk_tiles, nchunks;  // tiles of a chunk; ceil(ceil(topk / 64) / chunk_tiles)
+};
+// one fa_mla_indexer_loss_sparse call (csrc/fa_mla_indexer_loss_kernel.hip): q, w and the index-key pool as the logits call sees them, the
+// lists as the sparse forward does; dq under q's strides, dw under w's, dk under its own. dq == nullptr: a loss-only call
+struct MlaIndexerLossParams {
+  const void *q, *k;
+  const float *w;
+  const int *indices, *counts;
+  const float *target, *loss_grad;  // [T, target_stride]; [T] or null (1)
+  float *loss, *dq, *dw, *dk;
+  int T, topk, num_slots;
+  int lp;
+  long long q_rs, q_hs, w_rs, page_stride, row_stride, dk_page_stride, dk_row_stride, idx_stride, target_stride;  // elements
+};
+
 // one fa_mla_indexer_logits_paged call (csrc/fa_mla_indexer_kernel.hip): q is the packed index query [total_q, Hi, 128] under (row, head)
 // element strides, w the fp32 head weights [total_q, Hi] under a row stride, k the index-key pool [num_pages, P, 128] of q's type; the
 // three tables are fa_fwd_varlen_paged's. An item is (sequence, block of tb tokens, chunk of chunk_tiles 64-key tiles).
@@ -419,6 +446,14 @@ hipError_t launch_mla_decode_sparse_kv8_scaled(const MlaSparseParams &p, const M
 // delta [T, Hq]
 hipError_t launch_bwd_mla_sparse(const MlaSparseBwdParams &p, int dtype, hipStream_t s);
 long long mla_sparse_bwd_workspace_bytes(int T, int Hq);
+// fa_mla_sparse_head_probs (csrc/fa_mla_sparse_probs_kernel.hip): the chunk rule from host scalars, one launch over T x nchunks
+// workgroups of four waves
+int mla_sparse_probs_chunk_tiles(int T, int topk);
+hipError_t launch_mla_sparse_head_probs(const MlaSparseProbsParams &p, int dtype, hipStream_t s);
+// fa_mla_indexer_loss_sparse (csrc/fa_mla_indexer_loss_kernel.hip): one launch over T workgroups of four waves; the most list entries
+// its LDS row holds
+int mla_indexer_loss_max_topk();
+hipError_t launch_mla_indexer_loss(const MlaIndexerLossParams &p, int Hi, int dtype, hipStream_t s);
 // fa_mla_indexer_* (csrc/fa_mla_indexer_kernel.hip): the token block (1, 2, 4) and the chunk rule from host scalars, the logits kernel
 // over B * nblk * nchunks items of four waves, the select kernel over B * max_seqlen_q workgroups
 int mla_indexer_token_block(int max_seqlen_q);

@@ -633,6 +633,99 @@ def flash_attention_mla_sparse_backward(
     return dq, dkv
 
 
+def mla_sparse_head_probs_supported(dtype: str, d_qk: int, d_v: int, Hq: int, page_size: int) -> bool:
+    return bool(load_library().fa_mla_sparse_head_probs_supported(DTYPES[dtype], d_qk, d_v, Hq, page_size))
+
+
+def _sparse_lists(entry: str, indices: torch.Tensor, index_counts: Optional[torch.Tensor], T: int, device: torch.device) -> Tuple[int, int]:
+    """The sparse forward's list rules as the wrappers state them; returns (topk, indices_stride)."""
+    if (not indices.is_cuda or indices.device != device or indices.dtype != torch.int32 or indices.dim() != 2 or indices.shape[0] != T
+            or indices.shape[1] < 1 or indices.stride(1) != 1):
+        raise ValueError(f"{entry}: indices must be an int32 [T, topk] tensor on the inputs' device with a unit last stride: there is no CPU path")
+    if index_counts is not None and (not index_counts.is_cuda or index_counts.device != device or index_counts.dtype != torch.int32
+                                     or index_counts.shape != (T,) or not index_counts.is_contiguous()):
+        raise ValueError(f"{entry}: index_counts must be a contiguous int32 [T] tensor on the inputs' device, or None")
+    topk = indices.shape[1]
+    return topk, (indices.stride(0) if T > 1 else (topk + 3) // 4 * 4)
+
+
+def mla_sparse_head_probs(q: torch.Tensor, kv_pages: torch.Tensor, lse: torch.Tensor, indices: torch.Tensor,
+                          index_counts: Optional[torch.Tensor] = None, scale: float = 0.0, stream: Optional[int] = None) -> torch.Tensor:
+    """The main attention's probability on every listed key, summed over heads (include/fa_mi355.h fa_mla_sparse_head_probs):
+    probs[t, j] = sum_h exp(scale q[t,h] . row(indices[t,j]) - lse[t,h]), fp32 [T, topk], zeros behind n_t. q, the pool, the lists and
+    `scale` (required) are flash_attention_mla_decode_sparse's, `lse` [T, Hq] fp32 what it returned. A row sums to Hq: probs / Hq is the
+    target distribution of the indexer's loss, and mla_indexer_loss_sparse takes probs as it is. Nothing here synchronises."""
+    lib = load_library()
+    if not scale > 0:
+        raise ValueError("mla_sparse_head_probs needs the model's scale: there is no default (the head dim of the model is not 576)")
+    if q.dim() != 3 or kv_pages.dim() not in (3, 4) or (kv_pages.dim() == 4 and kv_pages.shape[2] != 1):
+        raise ValueError("q [T,Hq,576], kv_pages one [num_pages,P,576] or [num_pages,P,1,576] latent pool")
+    if not all(t.is_cuda and t.device == q.device for t in (q, kv_pages, lse)):
+        raise ValueError("mla_sparse_head_probs needs every tensor on one device: there is no CPU path")
+    if q.dtype not in (torch.float16, torch.bfloat16) or kv_pages.dtype != q.dtype:
+        raise ValueError(f"unsupported / mixed dtypes {q.dtype} {kv_pages.dtype} (f16 or bf16, q and the pool alike)")
+    T, Hq, Dqk = q.shape
+    num_pages, P = kv_pages.shape[0], kv_pages.shape[1]
+    if kv_pages.shape[-1] != Dqk or kv_pages.stride(-1) != 1 or q.stride(2) != 1:
+        raise ValueError(f"incompatible q {tuple(q.shape)} and pool {tuple(kv_pages.shape)}")
+    if lse.dtype != torch.float32 or lse.shape != (T, Hq) or not lse.is_contiguous():
+        raise ValueError("lse must be contiguous fp32 [T,Hq]")
+    topk, istride = _sparse_lists("mla_sparse_head_probs", indices, index_counts, T, q.device)
+    probs = torch.zeros((T, topk), dtype=torch.float32, device=q.device)
+    _call(lib, "fa_mla_sparse_head_probs",
+          (q.data_ptr(), kv_pages.data_ptr(), lse.data_ptr(), probs.data_ptr(), indices.data_ptr(), _ptr(index_counts), T, Hq, Dqk, 512, topk, P,
+           num_pages, float(scale), q.stride(0), q.stride(1), kv_pages.stride(0), kv_pages.stride(1), istride, topk, _TORCH2FA[q.dtype]),
+          q.device, stream)
+    return probs
+
+
+def mla_indexer_loss_sparse_supported(dtype: str, Hi: int, Di: int, page_size: int, topk: int) -> bool:
+    return bool(load_library().fa_mla_indexer_loss_sparse_supported(DTYPES[dtype], Hi, Di, page_size, topk))
+
+
+def mla_indexer_loss_sparse(q_idx: torch.Tensor, w: torch.Tensor, k_idx_pages: torch.Tensor, indices: torch.Tensor,
+                            index_counts: Optional[torch.Tensor], target: torch.Tensor, loss_grad: Optional[torch.Tensor] = None,
+                            dk_idx: Optional[torch.Tensor] = None, need_grads: bool = True, stream: Optional[int] = None):
+    """The indexer's loss KL(target / sum target || softmax(index logits on the list)) per token and its gradients (include/fa_mi355.h
+    fa_mla_indexer_loss_sparse). q_idx [T,Hi,128] f16 / bf16, w [T,Hi] fp32, k_idx_pages [num_pages,P,128] like q_idx; indices /
+    index_counts are the sparse forward's lists (the same slots address both pools); target fp32 [T, >= topk], non-negative, normalised
+    here (mla_sparse_head_probs' output goes in as it is); loss_grad fp32 [T] scales each token's gradients (None: 1). Returns
+    (loss [T], dq_idx [T,Hi,128] under q_idx's strides, dw [T,Hi], dk_idx [num_pages,P,128]), fp32; dk_idx is ACCUMULATED INTO when given
+    and zero-filled when allocated here. need_grads=False is the loss-only call: (loss, None, None, None). loss, dq_idx and dw are
+    bitwise reproducible, dk_idx (fp32 atomic adds) is not. Nothing here synchronises."""
+    lib = load_library()
+    T, Hi, Di, wrs = _indexer_inputs("mla_indexer_loss_sparse", q_idx, w, k_idx_pages)
+    if not q_idx.is_cuda:
+        raise ValueError("mla_indexer_loss_sparse needs its tensors on one device: there is no CPU path")
+    num_pages, P = k_idx_pages.shape[0], k_idx_pages.shape[1]
+    topk, istride = _sparse_lists("mla_indexer_loss_sparse", indices, index_counts, T, q_idx.device)
+    if (not target.is_cuda or target.device != q_idx.device or target.dtype != torch.float32 or target.dim() != 2 or target.shape[0] != T
+            or target.shape[1] < topk or target.stride(1) != 1):
+        raise ValueError("target must be an fp32 [T, >= topk] tensor on q_idx's device with a unit last stride")
+    if loss_grad is not None and (not loss_grad.is_cuda or loss_grad.device != q_idx.device or loss_grad.dtype != torch.float32
+                                  or loss_grad.shape != (T,) or not loss_grad.is_contiguous()):
+        raise ValueError("loss_grad must be a contiguous fp32 [T] tensor on q_idx's device, or None")
+    loss = torch.empty((T,), dtype=torch.float32, device=q_idx.device)
+    dq = dw = None
+    if need_grads:
+        dq = torch.empty_strided(q_idx.shape, q_idx.stride(), dtype=torch.float32, device=q_idx.device)
+        dw = torch.empty((T, Hi), dtype=torch.float32, device=q_idx.device)
+        if dk_idx is None:
+            dk_idx = torch.zeros((num_pages, P, Di), dtype=torch.float32, device=q_idx.device)
+        elif (not dk_idx.is_cuda or dk_idx.device != q_idx.device or dk_idx.dtype != torch.float32 or dk_idx.shape != (num_pages, P, Di)
+              or dk_idx.stride(2) != 1):
+            raise ValueError("dk_idx must be an fp32 [num_pages,P,128] device tensor with a unit last stride")
+    elif dk_idx is not None:
+        raise ValueError("dk_idx goes with need_grads=True")
+    _call(lib, "fa_mla_indexer_loss_sparse",
+          (q_idx.data_ptr(), w.data_ptr(), k_idx_pages.data_ptr(), indices.data_ptr(), _ptr(index_counts), target.data_ptr(), _ptr(loss_grad),
+           loss.data_ptr(), _ptr(dq), _ptr(dw), _ptr(dk_idx), T, Hi, Di, topk, P, num_pages, q_idx.stride(0), q_idx.stride(1), wrs,
+           k_idx_pages.stride(0), k_idx_pages.stride(1), dk_idx.stride(0) if need_grads else 0, dk_idx.stride(1) if need_grads else 0, istride,
+           target.stride(0) if T > 1 else target.shape[1], _TORCH2FA[q_idx.dtype]),
+          q_idx.device, stream)
+    return loss, dq, dw, dk_idx
+
+
 def mla_indexer_supported(dtype: str, Hi: int, Di: int, page_size: int) -> bool:
     return bool(load_library().fa_mla_indexer_supported(DTYPES[dtype], Hi, Di, page_size))
 

@@ -42,6 +42,12 @@ The absorbed MLA step over a list of keys per token (fa_fwd_mla_decode_sparse / 
 [num_pages, P, 576] f16 / bf16 like q, indices int32 [T, topk] of slots, index_counts int32 [T] or None; o [T, Hq, 512], lse [T, Hq].
 `scale` is the model's and must be greater than 0. Differentiable in q and kv_pages: the pool's gradient is pool-shaped, in the pool's
 dtype, zero in rows that no list names. The integer inputs get no gradient.
+
+    torch.ops.fa_mi355.mla_indexer_kl_loss(q_idx, w, k_idx_pages, indices, index_counts, target) -> loss
+
+The indexer's training loss over the same lists (fa_mla_indexer_loss_sparse): q_idx [T, Hi, 128], w [T, Hi] fp32, k_idx_pages
+[num_pages, P, 128] like q_idx, target fp32 [T, >= topk] (mla_sparse_head_probs' output as it is); loss [T] fp32. Differentiable in q_idx,
+w and k_idx_pages, under attention_mla_sparse's conventions for the pool's gradient.
 """
 from __future__ import annotations
 
@@ -51,7 +57,7 @@ import torch
 
 from .ops import (_TORCH2FA, FaError, _out_dtype, _sink_window, _window, flash_attention_backward, flash_attention_forward,
                   flash_attention_mla_decode_sparse, flash_attention_mla_sparse_backward, flash_attention_varlen, flash_attention_varlen_backward,
-                  flash_attention_varlen_mla, flash_attention_varlen_mla_backward, load_library)
+                  flash_attention_varlen_mla, flash_attention_varlen_mla_backward, load_library, mla_indexer_loss_sparse)
 
 _LIB = torch.library.Library("fa_mi355", "DEF")
 _LIB.define("attention_forward(Tensor q, Tensor k, Tensor v, bool is_causal=False, float scale=0.0) -> (Tensor, Tensor)")
@@ -428,6 +434,49 @@ def attention_mla_sparse(q, kv_pages, indices, index_counts=None, scale: float =
     """fa_mi355::attention_mla_sparse: the absorbed MLA step over a list of keys per token, differentiable in q and kv_pages through
     fa_bwd_mla_sparse. `scale` is the model's (required: greater than 0)."""
     return torch.ops.fa_mi355.attention_mla_sparse(q, kv_pages, indices, index_counts, scale)
+
+
+_LIB.define("mla_indexer_kl_loss(Tensor q_idx, Tensor w, Tensor k_idx_pages, Tensor indices, Tensor? index_counts, Tensor target) -> Tensor")
+
+
+def _mla_indexer_kl_loss_impl(q_idx, w, k_idx_pages, indices, index_counts, target):
+    return mla_indexer_loss_sparse(q_idx, w, k_idx_pages, indices, index_counts, target, need_grads=False)[0]
+
+
+def _mla_indexer_kl_loss_meta(q_idx, w, k_idx_pages, indices, index_counts, target):
+    return q_idx.new_empty((q_idx.shape[0],), dtype=torch.float32)
+
+
+_LIB.impl("mla_indexer_kl_loss", _mla_indexer_kl_loss_impl, "CUDA")
+_LIB.impl("mla_indexer_kl_loss", _mla_indexer_kl_loss_meta, "Meta")
+
+
+def _mla_indexer_kl_loss_setup_context(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+    ctx.set_materialize_grads(False)
+
+
+def _mla_indexer_kl_loss_backward(ctx, grad_loss):
+    q_idx, w, k_idx_pages, indices, index_counts, target = ctx.saved_tensors
+    none = (None,) * 6
+    if grad_loss is None:
+        return none
+    # (dk_idx zero-initialised by the wrapper: rows that no list names get a zero gradient; the target is detached)
+    _, dq, dw, dk = mla_indexer_loss_sparse(q_idx, w, k_idx_pages, indices, index_counts, target,
+                                            loss_grad=grad_loss.to(torch.float32).contiguous())
+    return (dq.to(q_idx.dtype), dw.to(w.dtype), dk.to(k_idx_pages.dtype)) + none[3:]
+
+
+torch.library.register_autograd("fa_mi355::mla_indexer_kl_loss", _mla_indexer_kl_loss_backward, setup_context=_mla_indexer_kl_loss_setup_context,
+                                lib=_LIB)
+
+
+def mla_indexer_kl_loss(q_idx, w, k_idx_pages, indices, index_counts, target):
+    """fa_mi355::mla_indexer_kl_loss: loss [T] = KL(target / sum target || softmax(index logits on the list)), differentiable in q_idx, w
+    and k_idx_pages through fa_mla_indexer_loss_sparse (forward: its loss-only call; backward: the full call with loss_grad = the
+    incoming gradient). The pool's gradient is pool-shaped, in the pool's dtype, zero in rows that no list names; the target and the
+    integer inputs get no gradient."""
+    return torch.ops.fa_mi355.mla_indexer_kl_loss(q_idx, w, k_idx_pages, indices, index_counts, target)
 
 
 def attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_seqlen_k: int, is_causal: bool = False, scale: float = 0.0,

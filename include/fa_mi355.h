@@ -1104,7 +1104,7 @@ int fa_mla_kv_append_paged_scaled(const void *kv_new, void *kv_pages, const int 
  * How it runs (csrc/fa_mla_sparse_bwd_kernel.hip): one launch, a four-wave workgroup per (token, 32 heads), key
  * tiles of 64 listed rows staged by the forward's scheme; Q and dO in registers as MFMA operands by head rows and by columns; all five
  * products on the matrix cores.
- * Not here: e4m3 pools and the 656-byte rows (the gradient of a quantised cache); a gradient into the indexer; a deterministic dkv; a
+ * Not here: e4m3 pools and the 656-byte rows (the gradient of a quantised cache); a deterministic dkv; a
  * key split for very few tokens; more than 128 heads.
  */
 int fa_bwd_mla_sparse(const void *q, const void *kv_pages, const void *o, const void *d_o, const float *lse,
@@ -1120,6 +1120,82 @@ int fa_bwd_mla_sparse(const void *q, const void *kv_pages, const void *o, const 
 /* 4 * T * Hq rounded up to 16 on every legal input (T >= 1, 1 <= Hq <= 128, T * Hq below 2^31); 0 elsewhere */
 long long fa_bwd_mla_sparse_workspace_bytes(int T, int Hq);
 int fa_bwd_mla_sparse_supported(int dtype, int Dqk, int Dv, int Hq, int page_size);
+
+/*
+ * Training the MLA indexer, call 1: fa_mla_sparse_head_probs gives the TARGET of the indexer's loss -- the main attention's probability
+ * on every listed key, summed over heads -- without a gather of [T, topk, 576] rows. With n_t = clamp(index_counts[t], 0, topk) (topk
+ * under NULL) and x_j = indices[t][j]:
+ *   probs[t][j] = sum_h exp(scale * q[t,h,0:576] . row(x_j)[0:576] - lse[t,h])        for j < n_t
+ * Over a token's list the values sum to Hq (up to rounding): the target distribution is probs / Hq, and fa_mla_indexer_loss_sparse
+ * normalises whatever it is given, so this call's output goes in as it is.
+ * q, kv_pages, indices, index_counts, their strides and the slot, list and count rules are fa_fwd_mla_decode_sparse's, word for word;
+ * validation runs on that call's path, so every rule the calls share carries the same status and text after the function name. lse is
+ * that call's output, [T, Hq] fp32 contiguous, natural log: required, 4-byte aligned. probs is fp32 [T, probs_stride], probs_stride >=
+ * topk, base 4-byte aligned. Nothing else is written: columns j >= n_t keep their bytes. Nothing at j >= n_t of a list is read. A slot
+ * named twice gets the same value in both places. An in-count entry outside [0, num_pages * P) is the forward's key of zeros: its value
+ * is sum_h exp(-lse[t,h]) and no address is formed from it. n_t = 0 is recognised by the integer and writes nothing.
+ * Rounding (fa_bwd_mla_sparse's, so P here is the P that call uses): Q~ = round(scale * log2 e * Q) to the type, fp32 scores from the
+ * matrix core, exp2(s - lse * log2 e), an fp32 sum over heads in a fixed order.
+ * Bitwise reproducible, no global atomics; asynchronous, allocates nothing, no workspace; the grid depends on host scalars alone
+ * (graph-capturable). Supported: what fa_fwd_mla_decode_sparse supports (fa_mla_sparse_head_probs_supported gives its answers).
+ * How it runs (csrc/fa_mla_sparse_probs_kernel.hip): a four-wave workgroup per (token, chunk of 64-key tiles),
+ * tiles staged by the forward's scheme, a block of 32 heads of Q~ per wave in registers, one score product per tile, exp2 and the head
+ * sum on the accumulators, one store of 64 floats per tile.
+ * Not here: e4m3 pools; per-head probabilities; a normalised output.
+ */
+int fa_mla_sparse_head_probs(const void *q, const void *kv_pages, const float *lse, float *probs,
+                             const int *indices, const int *index_counts,
+                             int T, int Hq, int Dqk, int Dv, int topk, int page_size, int num_pages, float scale,
+                             long long q_token_stride, long long q_head_stride,
+                             long long kv_page_stride, long long kv_row_stride,
+                             long long indices_stride, long long probs_stride, int dtype, void *hip_stream);
+int fa_mla_sparse_head_probs_supported(int dtype, int Dqk, int Dv, int Hq, int page_size);
+
+/*
+ * Training the MLA indexer, call 2: fa_mla_indexer_loss_sparse is the indexer's loss KL(target || softmax(index logits on the list)) per
+ * token and its gradients, without a gather of [T, topk, 128] index keys. For token t, with n_t and x_j as above, all sums over j < n_t:
+ *   s_hj = q_idx[t,h,:] . k_idx(x_j)[:]      I_j = sum_h w[t,h] * max(0, s_hj)      pi = softmax_j(I) (natural)
+ *   tau_j = target[t][j] / sum_j target[t][j]
+ *   loss[t]         = sum_j tau_j * (ln tau_j - ln pi_j)                 (terms with tau_j = 0 are 0)
+ *   g_j             = u_t * (pi_j - tau_j),  u_t = loss_grad[t], or 1 under NULL
+ *   dw[t,h]         = sum_j g_j * max(0, s_hj)
+ *   dq_idx[t,h,:]   = sum_j g_j * w[t,h] * [s_hj > 0] * k_idx(x_j)[:]
+ *   dk_idx[x_j,:]  += sum_h g_j * w[t,h] * [s_hj > 0] * q_idx[t,h,:]
+ * q_idx, w, k_idx_pages and their stride and alignment rules are fa_mla_indexer_logits_paged's (f16 / bf16, Hi = 32 | 64, Di = 128, P
+ * in {16, 32, 64, 128, 256}); indices and index_counts follow fa_fwd_mla_decode_sparse's rules, with those calls' statuses and texts. A
+ * slot x addresses the index pool exactly as it addresses the latent pool, (x >> log2 P) * k_page_stride + (x & (P - 1)) * k_row_stride:
+ * the select emits slots under the shared block table and page size, so one list serves both pools. target is fp32 [T, target_stride],
+ * target_stride >= topk: non-negative weights, not necessarily normalised; only columns j < n_t are read.
+ * loss is [T] fp32, required. dq_idx is fp32 under q_idx's ELEMENT strides and dw fp32 under w_row_stride: both WRITTEN. dk_idx is an
+ * fp32 pool [num_pages, P, 128] under dk_page_stride / dk_row_stride (multiples of 4, at least 128, base 16-byte aligned, one page
+ * below 2 GiB): ACCUMULATED INTO by fp32 atomic adds, the caller zeroes it. dq_idx, dw and dk_idx are given all three, or all three
+ * NULL: a loss-only call that does no gradient work; any other mix is FA_ERR_INVALID_ARG.
+ * n_t = 0 (by the integer) or a target row whose sum is 0: loss 0, dq and dw rows 0 exactly, nothing added to dk. An in-count entry
+ * outside the pool is a key of zeros: I_j = 0, it takes part in the softmax, adds nothing to dq, its dk is dropped and no address is
+ * formed from it. A duplicate slot receives its gradient twice. Rows no list names are never read and their dk rows never touched.
+ * Negative or NaN targets: an unspecified result, but nothing outside the footprint is touched.
+ * Rounding: fp32 scores from the matrix core; I, the softmax, tau and the loss in fp32; G_hj = g_j * w_h * [s_hj > 0] rounded to the
+ * type before the two gradient products; fp32 accumulation.
+ * REPRODUCIBILITY: loss, dq_idx and dw are bitwise reproducible. dk_idx is NOT: it leaves the workgroups by fp32 atomic adds -- one per
+ * (token, listed row, column), the sum over heads complete before it -- whose order in memory varies from run to run.
+ * Support: topk above 4096, the list entries the kernel's LDS row holds, is FA_ERR_UNSUPPORTED with the limit named
+ * (fa_mla_indexer_loss_sparse_supported is fa_mla_indexer_supported and 1 <= topk <= 4096). Asynchronous, allocates nothing, no
+ * workspace, graph-capturable.
+ * How it runs (csrc/fa_mla_indexer_loss_kernel.hip): one four-wave workgroup per token, two passes over the
+ * list; all three products on the matrix cores.
+ * Not here: e4m3 index keys; a key split for very few tokens; a deterministic dk_idx; the gradient of the main attention with respect to
+ * the target (the indexer's inputs and the target are detached in the models that train this way).
+ */
+int fa_mla_indexer_loss_sparse(const void *q_idx, const float *w, const void *k_idx_pages,
+                               const int *indices, const int *index_counts,
+                               const float *target, const float *loss_grad,
+                               float *loss, float *dq_idx, float *dw, float *dk_idx,
+                               int T, int Hi, int Di, int topk, int page_size, int num_pages,
+                               long long q_row_stride, long long q_head_stride, long long w_row_stride,
+                               long long k_page_stride, long long k_row_stride,
+                               long long dk_page_stride, long long dk_row_stride,
+                               long long indices_stride, long long target_stride, int dtype, void *hip_stream);
+int fa_mla_indexer_loss_sparse_supported(int dtype, int Hi, int Di, int page_size, int topk);
 
 /*
  * The MLA indexer: fa_mla_indexer_logits_paged, fa_mla_indexer_select and fa_mla_indexer_topk_paged PRODUCE the lists that
